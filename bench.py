@@ -6,7 +6,11 @@ A "step" is one full frame of the hot path: the synthetic Cornell box (S1, SURVE
 4-row bands (RT_SHARD_ROWS), no collective on the data path, and gathered at the end of the frame: every rank sends the rows it touched to rank 0
 over RCCL point-to-point sends, inside the timed region.
 
-Prints ONE JSON line (rank 0). `roofline` is for the dominant kernel stage of the workload: algorithmic bytes (a ray cast =
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps frames and prints the headline: `value` (Msamples/s over the timed
+frames) and `ms_per_step` (wall milliseconds of one timed frame). `--dump-outputs DIR` writes the film of the last timed frame to DIR/film.npy
+(the full-size S1 film is not bit-reproducible: a few pixels in a million differ in their last bit from frame to frame - compare with a tolerance).
+Everything else the benchmark measures runs only with `--full`:
+`roofline` is for the dominant kernel stage of the workload: algorithmic bytes (a ray cast =
 48 B + 32 B per BVH node visited + 36 B per triangle tested, counted by an untimed counting frame of the same workload; a shaded vertex =
 128 B + 32 B per ray it emits + 48 B of sampler tables per path) / the stage's HIP-event time measured in the timed frames.
 `cpu_baseline` is the C++ oracle in its reference-faithful tile-sequential sampler mode on all host cores, built on this box with
@@ -17,7 +21,7 @@ started as a plain `python bench.py --gpus N` the ONE process drives N devices i
 a shared queue, touched rows peer-copied to device 0) - renderer::render's worker pool with GPUs as the workers (rc/renderer.rs:22-29, 47-71). Either way the
 run fails when fewer than N devices are visible; `n_gpus` in the line is the number of devices that actually traced camera rays.
 
-At N = 1 the line also carries, under "other_configs", the same measurement for BASELINE configs[2..4] (S2 blob-1M, S3 mis-plates, S4 room-env;
+With --full at N = 1 the line also carries, under "other_configs", the same measurement for BASELINE configs[2..4] (S2 blob-1M, S3 mis-plates, S4 room-env;
 2 timed frames each whatever --steps says) and, under "config_c1", configs[0] exactly (cornell 400x400, 64 spp) on the GPU and on the CPU port.
 `--headline-only` skips those; `--scene X` makes X the headline instead.
 """
@@ -270,8 +274,27 @@ class Runner:
         return st
 
 
-def run_workload(scene_name, runner, workload, steps, warmup):
-    """Times `steps` frames of one workload; returns the result dict (rank 0) or None."""
+DUMP_LIMIT = 64 * 2 ** 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, film):
+    """What the timed path returned in its last frame: the film (H, W, 4) float32 -> path/film.npy. A film over DUMP_LIMIT is written as a fixed,
+    seeded sample of its pixels instead (path/film_sample.npy, (n, 4), pixels in raster order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    film = np.ascontiguousarray(film, np.float32)
+    if film.nbytes <= DUMP_LIMIT:
+        np.save(os.path.join(path, "film.npy"), film)
+        return
+    flat = film.reshape(-1, film.shape[-1])
+    n = DUMP_LIMIT // 2 // flat[0].nbytes
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], n, replace=False))
+    np.save(os.path.join(path, "film_sample.npy"), flat[idx])
+
+
+def run_workload(scene_name, runner, workload, steps, warmup, full=True, dump_dir=None):
+    """Times `steps` frames of one workload; returns the result dict (rank 0) or None. `full`: also the clock readings, the counting frame and
+    the rooflines; `dump_dir`: where rank 0 writes the film of the last timed frame (dump_outputs)."""
     import numpy as np
     import torch
     rank, world, dist = runner.rank, runner.world, runner.dist
@@ -283,16 +306,20 @@ def run_workload(scene_name, runner, workload, steps, warmup):
         if k == 0:
             lightdist_first_ms = st.get("ms_lightdist")
     kstats = []
-    clocks = ClockSampler()
-    clocks.sample()  # (before the opening barrier: the sysfs reads are outside the timed region)
+    clocks = ClockSampler() if full else None
+    if full:
+        clocks.sample()  # (before the opening barrier: the sysfs reads are outside the timed region)
     runner.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         kstats.append(runner.step(True))
     runner.barrier()
     dt = time.perf_counter() - t0
-    clocks.sample()
-    cst = runner.count()
+    if full:
+        clocks.sample()
+    if dump_dir is not None and rank == 0:  # before the counting frame, which renders into the same film
+        dump_outputs(dump_dir, runner.film.cpu().numpy())
+    cst = runner.count() if full else {}
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{runner.local_rank}")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -340,6 +367,32 @@ def run_workload(scene_name, runner, workload, steps, warmup):
     launches_shade = kstats[-1]["launches_shade"] // ldiv
     if lightdist_first_ms is None:  # no warm-up: the first timed frame built the tables, its time is inside the timed region
         lightdist_first_ms = kstats[0].get("ms_lightdist")
+    kernels_ms = {k[3:]: round(v, 2) for k, v in ms_mean.items()}
+    verts = {k[9:]: int(kstats[-1][k]) for k in kstats[-1] if k.startswith("vertices_") and kstats[-1][k]}
+    sharding = {"single": "single GPU",
+                "dist": "interleaved tile rows, one process per GPU, touched rows gathered on rank 0 (RCCL send/recv)",
+                "multi": f"one process (rt_multi_render), {runner.chunks} chunk(s) of interleaved tile rows per device, touched rows peer-copied to device 0"}[runner.mode]
+    out = {
+        "metric": "Msamples/s", "value": round(value, 2), "unit": "Msamples/s", "n_gpus": n_gpus, "steps": steps, "warmup": warmup,
+        "ms_per_step": round(ms_step, 2), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload, "sharding": sharding, "sampler_mode": "pixel-keyed",
+                   "light_distribution": ("cached across frames; first-frame build %.1f ms%s" % (lightdist_first_ms, "" if warmup else " (inside the first timed frame)")) if lightdist_first_ms is not None else "cached across frames"},
+        "lightdist_ms_first_frame": lightdist_first_ms,
+        "s_per_frame": round(ms_step / 1e3, 4),
+        "kernel_ms_per_step": kernels_ms, "vertices_by_shade_front_end": verts, "shade_kernel_launches_per_step": int(launches_shade),
+        "camera_samples_per_step": int(samples_per_step),
+    }
+    if n_gpus_asked > 1:
+        out["n_gpus_requested"] = n_gpus_asked
+        out["per_device_ms"] = per_rank_ms
+        out["imbalance_max_over_mean"] = round(max(per_rank_ms) / max(float(np.mean(per_rank_ms)), 1e-9), 3)
+        out["gather_ms"] = round(ms_mean.get("ms_gather", 0.0), 3)  # multi: last device done -> merged frame in place; dist: the slowest rank's share of the RCCL gather (rank 0: receives + additions)
+        if runner.mode == "multi":
+            out["devices"] = [int(d) for d in runner.devices]
+        else:
+            out["rccl_world_size"] = world
+    if not full:
+        return out
 
     # SURVEY §8d bytes of the three ray classes, each divided by the time of ITS launches. The counting frame walks what the timed frames walk
     # (RT_FLAG_COUNT_AS_RENDERED): path rays and MIS rays toward area lights closest-hit, shadow rays and MIS rays toward the environment any-hit.
@@ -424,33 +477,12 @@ def run_workload(scene_name, runner, workload, steps, warmup):
         return r
     roofline = roof(*(trace_roofline() if ms_tc >= ms_sh else shade_roofline()))
     roofline_other = roof(*(shade_roofline() if ms_tc >= ms_sh else trace_roofline()))  # the runner-up of the two heavy stages
-    kernels_ms = {k[3:]: round(v, 2) for k, v in ms_mean.items()}
-    verts = {k[9:]: int(kstats[-1][k]) for k in kstats[-1] if k.startswith("vertices_") and kstats[-1][k]}
-    sharding = {"single": "single GPU",
-                "dist": "interleaved tile rows, one process per GPU, touched rows gathered on rank 0 (RCCL send/recv)",
-                "multi": f"one process (rt_multi_render), {runner.chunks} chunk(s) of interleaved tile rows per device, touched rows peer-copied to device 0"}[runner.mode]
-    out = {
-        "metric": "Msamples/s", "value": round(value, 2), "unit": "Msamples/s", "n_gpus": n_gpus, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_step, 2), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload, "sharding": sharding, "sampler_mode": "pixel-keyed",
-                   "light_distribution": ("cached across frames; first-frame build %.1f ms%s" % (lightdist_first_ms, "" if warmup else " (inside the first timed frame)")) if lightdist_first_ms is not None else "cached across frames"},
-        "lightdist_ms_first_frame": lightdist_first_ms,
-        "s_per_frame": round(ms_step / 1e3, 4),
+    out.update({
         "Mrays_per_s": round((cst["rays_closest"] + cst["rays_shadow"] + cst["rays_mis"] - not_cast - tail_nc) / (ms_step * 1e-3) / 1e6, 1),
         "mis_rays_not_cast": int(not_cast), "tail_rays_not_cast": int(tail_nc),
-        "kernel_ms_per_step": kernels_ms, "vertices_by_shade_front_end": verts, "shade_kernel_launches_per_step": int(launches_shade),
         "roofline": roofline, "roofline_second_kernel": roofline_other, "traversal_by_ray_class": classes, "traversal_hbm_share": groups,
-        "camera_samples_per_step": int(samples_per_step), "gpu_clocks": clocks.summary(),
-    }
-    if n_gpus_asked > 1:
-        out["n_gpus_requested"] = n_gpus_asked
-        out["per_device_ms"] = per_rank_ms
-        out["imbalance_max_over_mean"] = round(max(per_rank_ms) / max(float(np.mean(per_rank_ms)), 1e-9), 3)
-        out["gather_ms"] = round(ms_mean.get("ms_gather", 0.0), 3)  # multi: last device done -> merged frame in place; dist: the slowest rank's share of the RCCL gather (rank 0: receives + additions)
-        if runner.mode == "multi":
-            out["devices"] = [int(d) for d in runner.devices]
-        else:
-            out["rccl_world_size"] = world
+        "gpu_clocks": clocks.summary(),
+    })
     return out
 
 
@@ -475,12 +507,13 @@ def compact_line(full):
     where it stands. Everything else a run measures (per-class traversal rates, stage times, register tables, provenance) is in the detail file."""
     out = {k: full[k] for k in TOP_KEYS if k in full}
     out["config"] = {k: v for k, v in full["config"].items() if k in ("workload", "sharding", "sampler_mode", "light_distribution")}
-    out["roofline"] = _roof(full["roofline"])
+    if "roofline" in full:  # (--full)
+        out["roofline"] = _roof(full["roofline"])
+        if full["roofline"].get("warning"):
+            out["roofline"]["traffic_stale"] = True
     r2 = full.get("roofline_second_kernel")
     if r2:  # the runner-up of the two heavy stages, in four numbers
         out["roofline_second_kernel"] = {"kernel": r2["kernel"], "frac": r2["frac"], "avg_launch_ms": r2["avg_launch_ms"], "traffic_ratio": _traffic_ratio(r2)}
-    if full["roofline"].get("warning"):
-        out["roofline"]["traffic_stale"] = True
     if "cpu_baseline" in full:
         out["cpu_baseline"] = {k: full["cpu_baseline"][k] for k in CPU_KEYS}
         out["speedup"] = full.get("speedup_vs_cpu_baseline")
@@ -537,7 +570,15 @@ def main():
                                                     "twice puts two workers with their own scene replicas on one GPU - a way to exercise the N > 1 path on a 1-GPU box, not a measurement")
     ap.add_argument("--chunks-per-device", type=int, default=1, help="in-process multi-GPU mode: tile-row chunks per device on the shared queue (1 = static interleaved split)")
     ap.add_argument("--detail", default=None, help="where the full measurement goes (default gpurun_out/bench_detail.json); the printed line stays under 4 KB")
+    ap.add_argument("--full", action="store_true", help="measure beyond the headline: clock readings, the counting frame and the rooflines, the CPU baseline, "
+                                                        "configs[0] and configs[2..4], the detail file (--no-cpu-baseline / --headline-only drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the film of the last timed frame to DIR/film.npy (float32, (H, W, 4); "
+                                                                        "over 64 MB a fixed, seeded sample of its pixels, DIR/film_sample.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.detail and not args.full:
+        ap.error("--detail is the full measurement: add --full")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -589,9 +630,9 @@ def main():
         desc, workload = make_desc(args.scene, args.spp, args.res)
         scene = host.HostScene(desc)
     r0 = runner_for(scene)
-    out = run_workload(args.scene, r0, workload, args.steps, args.warmup)
+    out = run_workload(args.scene, r0, workload, args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
     del r0, scene
-    if rank == 0 and mode == "single":
+    if args.full and rank == 0 and mode == "single":
         if not args.no_cpu_baseline and desc is not None:
             cpu_spp = args.cpu_spp if args.scene != "room" else max(8, args.cpu_spp // 2)
             out["cpu_baseline"] = cpu_baseline(desc, cpu_spp)
@@ -619,7 +660,8 @@ def main():
                 c1["cpu_port"] = cpu_baseline(d, 64, what="whole")
             out["config_c1"] = c1
     if rank == 0:
-        out["detail"] = write_detail(out, args.detail)
+        if args.full:
+            out["detail"] = write_detail(out, args.detail)
         print(compact_line(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -2,7 +2,7 @@
 import glob, json, os, re, collections
 import numpy as np
 rows = collections.defaultdict(list)
-for f in sorted(glob.glob("gpurun_out/ab/*_*_*.json")):
+for f in sorted(glob.glob(os.path.join(os.environ.get("RESULTS", "results"), "ab", "*_*_*.json"))):  # (scripts/ab_bench.sh: $RESULTS/ab)
     m = re.match(r"(.+)_([a-z0-9-]+)_(\d+)\.json$", os.path.basename(f))
     try:
         j = json.load(open(f))

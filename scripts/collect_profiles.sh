@@ -1,12 +1,13 @@
 #!/bin/bash
-# After `bash scripts/round_profiles.sh <tag>` ran on the GPU box and gpurun merged gpurun_out/ back: copy what the judge reads into profiles/ (tracked). Usage: bash scripts/collect_profiles.sh r05
+# After `bash scripts/round_profiles.sh <tag>` ran on the GPU box and its $RESULTS/ folder (default results/) was copied back: copy what a round reports into profiles/ (tracked). Usage: bash scripts/collect_profiles.sh r05
+RESULTS=${RESULTS:-results}  # where the runs' outputs go
 TAG=${1:-r06}
 cd "$(dirname "$0")/.." || exit 1
-cp gpurun_out/final/profiles/${TAG}_* gpurun_out/final/profiles/pmc_*.json profiles/ || exit 1
-cp gpurun_out/final/bench_default.json profiles/${TAG}_bench_default.json
-cp gpurun_out/final/bench_default_detail.json profiles/${TAG}_bench_default_detail.json
-for sc in cornell room blob mis; do cp gpurun_out/${TAG}_$sc/stats_detail.json profiles/${TAG}_bench_${sc}_detail.json; done
-for sc in mis-spheres instances-10k; do cp gpurun_out/final/bench_$sc.json profiles/${TAG}_bench_$sc.json; done
+cp $RESULTS/final/profiles/${TAG}_* $RESULTS/final/profiles/pmc_*.json profiles/ || exit 1
+cp $RESULTS/final/bench_default.json profiles/${TAG}_bench_default.json
+cp $RESULTS/final/bench_default_detail.json profiles/${TAG}_bench_default_detail.json
+for sc in cornell room blob mis; do cp $RESULTS/${TAG}_$sc/stats_detail.json profiles/${TAG}_bench_${sc}_detail.json; done
+for sc in mis-spheres instances-10k; do cp $RESULTS/final/bench_$sc.json profiles/${TAG}_bench_$sc.json; done
 python - <<PY
 import json, sys
 sys.path.insert(0, '.')

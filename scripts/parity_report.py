@@ -22,5 +22,6 @@ for name, d in [("cornell", cornell_box(128, 128, 64)), ("blob", blob_scene(256,
                      rays_oracle=[int(so[k]) for k in ("rays_closest", "rays_shadow", "rays_mis")], rays_gpu=[int(sh[k]) for k in ("rays_closest", "rays_shadow", "rays_mis")],
                      mis_rays_not_cast=int(sh.get("rays_mis_not_cast", 0)))
     print(name, res[name], flush=True)
-os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-json.dump(res, open(os.path.join(ROOT, "gpurun_out", f"{tag}_parity.json"), "w"), indent=1)
+out_dir = os.path.join(ROOT, os.environ.get("RESULTS", "results"))  # (scripts/round_profiles.sh copies it into profiles/)
+os.makedirs(out_dir, exist_ok=True)
+json.dump(res, open(os.path.join(out_dir, f"{tag}_parity.json"), "w"), indent=1)

@@ -2,11 +2,12 @@
 # Usage (GPU box, repo root): bash scripts/tcc_scene.sh <scene> <spp>
 # L2 hit rate and fabric read requests of a scene's trace kernels (is the tree resident under the streams' cache policy?): one --pmc pass
 # (TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum; counters only), per kernel: hits / (hits + misses), L2-miss read requests, and requests per ray of its class.
+RESULTS=${RESULTS:-results}  # where the runs' outputs go
 SC=${1:-blob}; SPP=${2:-64}
-OUT=gpurun_out/tcc_$SC; mkdir -p $OUT
+OUT=$RESULTS/tcc_$SC; mkdir -p $OUT
 ROOT=$(pwd); cd /tmp && export TMPDIR=/tmp && cd $ROOT
 export RTX_K0_OVERLAP=0
-rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d $OUT/p -- python3 bench.py --scene $SC --spp $SPP --steps 1 --warmup 0 --no-cpu-baseline --headline-only --detail $OUT/detail.json > $OUT/p.log 2>&1
+rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d $OUT/p -- python3 bench.py --full --scene $SC --spp $SPP --steps 1 --warmup 0 --no-cpu-baseline --headline-only --detail $OUT/detail.json > $OUT/p.log 2>&1
 python3 - "$OUT" "$SC" "$SPP" <<'PY'
 import csv, glob, json, sys, collections
 d, sc, spp = sys.argv[1:4]

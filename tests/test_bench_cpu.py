@@ -84,3 +84,41 @@ def test_detail_file_holds_what_the_line_leaves_out(tmp_path):
     rel = bench.write_detail(full, str(tmp_path / "d.json"))
     j = json.load(open(tmp_path / "d.json"))
     assert rel and set(j["traversal_by_ray_class"]) == {"path_closest", "shadow_any", "mis_closest", "mis_any"} and "kernel_resources" in j and len(j["kernel_source_sha"]) == 16
+
+
+def test_detail_file_needs_full_and_steps_must_be_positive():
+    r = _run(["--detail", "d.json"])
+    assert r.returncode != 0 and "--full" in r.stderr and r.stdout.strip() == ""
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_plain_line_holds_the_headline_without_full_measurements():
+    """What a plain run returns (run_workload(full=False)): the line carries the headline and nothing that needs the counting frame or other runs."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    full = _fake_workload("cornell")
+    for k in ("roofline", "roofline_second_kernel", "traversal_by_ray_class", "traversal_hbm_share", "Mrays_per_s", "mis_rays_not_cast"):
+        full.pop(k)
+    j = json.loads(bench.compact_line(full))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert j[k] == full[k], k
+    assert "roofline" not in j and "cpu_baseline" not in j and "other_configs" not in j
+
+
+def test_dump_outputs_writes_the_film_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    film = np.random.default_rng(1).random((40, 30, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), film)
+    assert np.array_equal(np.load(tmp_path / "whole" / "film.npy"), film)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)  # a film over the limit: a seeded sample of its pixels, the same every time
+    bench.dump_outputs(str(tmp_path / "s1"), film)
+    bench.dump_outputs(str(tmp_path / "s2"), film)
+    a, b = np.load(tmp_path / "s1" / "film_sample.npy"), np.load(tmp_path / "s2" / "film_sample.npy")
+    assert a.dtype == np.float32 and a.shape == (128, 4) and a.nbytes <= 4096 and np.array_equal(a, b)
+    assert not (tmp_path / "s1" / "film.npy").exists()
+    rows = {tuple(r) for r in film.reshape(-1, 4)}
+    assert all(tuple(r) in rows for r in a)
