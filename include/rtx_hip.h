@@ -241,6 +241,9 @@ typedef struct rt_stats {
    * the path rays, the any-hit launches of the shadow rays, the closest-hit launches of the BSDF-sampled MIS rays, the any-hit launches of the MIS rays toward
    * an infinite light, and the k_shade launches of all front-ends together (binning and the miss bin not counted). What a per-launch average divides by. */
   uint64_t launches_trace_path, launches_trace_shadow, launches_trace_mis, launches_trace_mis_any, launches_shade;
+  /* of rays_shadow: segments whose voxel / light pair the shadow sets mark EMPTY (rt_shadow_sets) - unoccluded for certain, answered by k_shade without a
+   * walk. Zero on frames that count the reference's walk and where RTX_SHADOW_SETS=0. */
+  uint64_t rays_shadow_not_cast;
 } rt_stats;
 
 #define RT_FLAG_COUNT_TRAVERSAL 1u /* fill nodes_ and tris_ counters (slower)                  */
@@ -343,7 +346,9 @@ int rt_light_distribution(rt_scene* scene, int32_t n_voxels[3], float* func, flo
  * primitives in LDS (k_trace; the roofline of such a scene's traversal is VALU issue, its HBM bytes are ray records only), else 0. < 0: bad argument. */
 enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident scenes: the nodes the stackless walks test (<= n_nodes: interior nodes whose test rarely fails are passed over) */,
        RT_QUERY_LDS_OCCLUSION = 2 /* 1 if the scene is too large for RT_QUERY_LDS_RESIDENT but fits ONE workgroup's 160 KB per CU (<= 2816 nodes, <= 1408 plain triangles): occlusion rays walk an LDS copy of it, closest-hit rays its bounds and link tables;
-                                      RT_QUERY_LDS_NODES_TESTED then counts the occlusion walk's nodes */ };
+                                      RT_QUERY_LDS_NODES_TESTED then counts the occlusion walk's nodes */,
+       RT_QUERY_SHADOW_PAIRS = 3 /* shadow sets (rt_shadow_sets): voxel / light pairs of the voxels a surface reaches; 0 where the scene has none */,
+       RT_QUERY_SHADOW_EMPTY = 4 /* ... of them EMPTY: no shadow segment of the pair can be occluded */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,
@@ -351,6 +356,11 @@ int rt_scene_query(rt_scene* scene, int32_t what);
  * range | the same low half) over the nodes the calibration kept / over all nodes. stats (27 doubles, may be NULL): per set of calibration rays 0 - 8 the number of rays, their
  * simulated node tests with every node tested, and with the kept ones. mid != 0: the mid-size packing of a leaf's primitive range. RT_ERR_INVALID when capacity_words is short. */
 int rt_link_tables(const rt_scene_desc* desc, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats);
+/* The shadow sets rt_scene_create builds for an LDS-resident plain-triangle scene of two triangle lights (host only, no device): per voxel of the light
+ * distribution's grid (n_voxels, x fastest) and light, one word - RT_SHADOW_EMPTY (1): no shadow segment from a surface point of the voxel to the light
+ * can be occluded; 0: walk. words: 2 per voxel (capacity_words >= 2 * voxels), or NULL; stats[0] = pairs of voxels a surface reaches and lights, stats[1] = of
+ * them EMPTY. RT_ERR_INVALID for any other scene. */
+int rt_shadow_sets(const rt_scene_desc* desc, uint32_t* words, uint64_t capacity_words, int32_t n_voxels[3], uint64_t* stats);
 /* sizeof() of an ABI struct by its C name ("rt_stats", "rt_scene_desc", ...), or -1: lets a binding in another language check its mirror of the
  * header against the library it actually loaded (rustracer_amd/host.py does at load time; tests/test_abi_cpu.py checks every struct). */
 int rt_sizeof(const char* struct_name);

@@ -21,6 +21,7 @@
 #include "rtx_shade_launch.h"
 #include "rtx_ref_launch.h"
 #include "rtx_link_tables.h"
+#include "rtx_shadow_sets.h"
 
 using namespace rtx;
 
@@ -92,6 +93,8 @@ struct rt_scene {
   std::vector<DLight> h_lights;
   // light distribution tables (built per render, rc/integrator/path.rs:86-94)
   DevBuf ld_func, ld_cdf, ld_int, ld_mark, ld_list, ld_slot, ld_guide, ld_rows8, ld_dense8;
+  // shadow sets (rtx_shadow_sets.h): LDS-resident plain-triangle scenes of two triangle lights - per voxel and light, EMPTY or WALK; written into ld_rows8's spare words
+  bool shadow_sets = false; RtShadowSets shadow; DevBuf ld_shadow;
   DevBuf self;  // `d` in device memory (DScene::self), rewritten whenever `d` changes
   int ld_strategy_built = -1; bool ld_all_voxels = false;  // the tables are a function of the scene alone: built once per strategy, kept across frames
   std::mutex render_mutex;  // rt_render shares the workspace below: concurrent calls on one rt_scene take turns
@@ -190,6 +193,19 @@ static bool sphere_lights_clear(const rt_scene_desc* desc) {
       else { const double den = 1.0 / (va + vb + vc), v = vb * den, w = vc * den; for (int j = 0; j < 3; ++j) best[j] = a[j] + ab[j] * v + ac[j] * w; }
       if (!(dot3(best, best) > r2)) return false;  // (a NaN vertex fails too)
     }
+  }
+  return true;
+}
+
+// The scenes the shadow sets serve (rtx_shadow_sets.h): LDS-resident plain triangles (plain: no quadric, instance or mask) whose sampled lights are exactly two
+// area lights on triangles - the light-distribution records then have a spare word per light (ld_rows8, k_lightdist_rows8). One light: the distribution is
+// uniform (build_light_distribution), its single record is shared by every voxel and carries no per-voxel word.
+#define RT_SHADOW_PLAIN_FLAGS (RT_TRI_FLIP | RT_TRI_HAS_N | RT_TRI_HAS_UV | RT_TRI_HAS_S)
+static bool shadow_sets_apply(const rt_scene_desc* desc, bool plain) {
+  if (!plain || desc->n_lights != 2 || !desc->lights) return false;
+  for (uint32_t k = 0; k < desc->n_lights; ++k) {
+    const rt_light& l = desc->lights[k];
+    if (l.kind != 0 || l.prim < 0 || (uint32_t)l.prim >= desc->n_tris || (desc->tri_meta[l.prim].flags & ~(uint32_t)RT_SHADOW_PLAIN_FLAGS)) return false;
   }
   return true;
 }
@@ -632,6 +648,12 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
     if (rcl != RT_OK) { delete s; return rcl; }
     d.link8_full = s->link8_full.as<unsigned>(); d.link8 = s->link8.as<unsigned>();
   }
+  if (shadow_sets_apply(desc, s->small && !s->general_prims && !s->has_instances) && !(env_is("RTX_SHADOW_SETS", '0'))) {  // (measurement knob, read per scene: 0 = every segment walks)
+    int32_t lp[2] = {0, 0};
+    for (uint32_t k = 0; k < desc->n_lights; ++k) lp[k] = desc->lights[k].prim;
+    rt_build_shadow_sets(desc->tri_p, desc->n_tris, lp, (int)desc->n_lights, desc->nodes[0].bmin, desc->nodes[0].bmax, s->shadow);
+    s->shadow_sets = s->shadow.empty > 0;
+  }
   if (!s->small && !s->deep_column) {  // LDS-resident scenes keep the one-node-per-step loop: the pair form measured no faster there
     // With object instances the records cover the top-level tree (objects are walked one node per step, their child offsets are relative to the object).
     // A leaf of a GENERAL scene that holds anything but plain triangles carries RT_PAIR_GENERAL.
@@ -846,11 +868,31 @@ extern "C" int rt_link_tables(const rt_scene_desc* desc, int32_t mid, uint32_t* 
   if (stats) for (int w = 0; w < 9; ++w) { stats[w] = (double)lt.n_rays[w]; stats[9 + w] = lt.tests_all[w]; stats[18 + w] = lt.tests_kept[w]; }
   return RT_OK;
 }
+extern "C" int rt_shadow_sets(const rt_scene_desc* desc, uint32_t* words, uint64_t capacity_words, int32_t n_voxels[3], uint64_t* stats) {
+  if (!desc || !desc->nodes || desc->n_nodes == 0 || !desc->tri_p || !desc->tri_meta) return fail(RT_ERR_INVALID, "null argument");
+  bool plain = desc->n_instances == 0 && desc->n_spheres == 0 && desc->n_nodes <= RT_SMALL_NODES && desc->n_tris <= RT_SMALL_TRIS;
+  for (uint32_t i = 0; i < desc->n_tris && plain; ++i) if (desc->tri_meta[i].flags & ~(uint32_t)RT_SHADOW_PLAIN_FLAGS) plain = false;
+  if (!shadow_sets_apply(desc, plain)) return fail(RT_ERR_INVALID, "not a scene the shadow sets serve (LDS-resident plain triangles, two triangle lights)");
+  int32_t lp[2] = {0, 0};
+  for (uint32_t k = 0; k < desc->n_lights; ++k) lp[k] = desc->lights[k].prim;
+  RtShadowSets ss;
+  rt_build_shadow_sets(desc->tri_p, desc->n_tris, lp, (int)desc->n_lights, desc->nodes[0].bmin, desc->nodes[0].bmax, ss);
+  if (n_voxels) { n_voxels[0] = ss.nvox[0]; n_voxels[1] = ss.nvox[1]; n_voxels[2] = ss.nvox[2]; }
+  if (stats) { stats[0] = ss.pairs; stats[1] = ss.empty; }
+  if (words) {
+    if (capacity_words < ss.word.size()) return fail(RT_ERR_INVALID, "rt_shadow_sets: capacity too small");
+    std::memcpy(words, ss.word.data(), ss.word.size() * 4);
+  }
+  return RT_OK;
+}
+
 extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (!s) return fail(RT_ERR_INVALID, "null scene");
   if (what == RT_QUERY_LDS_RESIDENT) return s->small ? 1 : 0;
   if (what == RT_QUERY_LDS_NODES_TESTED) return (s->small || s->mid) ? (int)s->lds_nodes_tested : 0;
   if (what == RT_QUERY_LDS_OCCLUSION) return s->mid ? 1 : 0;
+  if (what == RT_QUERY_SHADOW_PAIRS) return s->shadow_sets ? (int)s->shadow.pairs : 0;
+  if (what == RT_QUERY_SHADOW_EMPTY) return s->shadow_sets ? (int)s->shadow.empty : 0;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -942,6 +984,15 @@ static int build_light_distribution(rt_scene* s, int strategy, hipStream_t strea
       HIP_TRY(hipGetLastError());
       d.ld_dense8 = s->ld_dense8.as<float4>();
     }
+  }
+  if (d.ld_rows8 != nullptr && !uniform && s->shadow_sets && nl == 2 && d.nvox[0] == s->shadow.nvox[0] && d.nvox[1] == s->shadow.nvox[1] && d.nvox[2] == s->shadow.nvox[2]) {
+    // the voxels' shadow-set words into the spare words of their records (r0.w: light 0, r1.w: light 1), then into the dense copy
+    const unsigned long long n_vox = (unsigned long long)d.nvox[0] * d.nvox[1] * d.nvox[2];
+    int rc = upload(s->ld_shadow, s->shadow.word.data(), s->shadow.word.size() * 4);
+    if (rc != RT_OK) return rc;
+    hipLaunchKernelGGL(k_lightdist_shadow_words, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, stream, s->ld_shadow.as<unsigned>(), s->ld_slot.as<int>(), n_vox, s->ld_rows8.as<float4>(),
+                       d.ld_dense8 != nullptr ? s->ld_dense8.as<float4>() : nullptr);
+    HIP_TRY(hipGetLastError());
   }
   s->ld_strategy_built = strategy; s->ld_all_voxels = all_voxels;
   HIP_TRY(hipMemcpyAsync(s->self.p, &s->d, sizeof(DScene), hipMemcpyHostToDevice, stream));
@@ -1623,6 +1674,7 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
       const int fresh_planes = all_in_bounds ? ((s->lambert_only && s->lds_records) ? RT_FRESH_RECORDS_LDS : RT_FRESH_RECORDS) : 0;  // which records k_raygen leaves out (PassState::fresh)
       ps.fresh = fresh_planes;
       // a frame that counts node visits keeps the reference's closest-hit walk for every MIS ray, unless it is asked to count what a production frame walks
+      ps.shadow_sets = (s->shadow_sets && !count) ? 1 : 0;
       ps.mis_any = (has_infinite && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
       static const bool reach_off = env_is("RTX_MIS_REACH", '0');  // measurement knob
       ps.skip_unreachable_mis = (!reach_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
@@ -1712,7 +1764,7 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
     if (ovf) { (void)hipMemset(s->sampler_plan.dirty.p, 0, (2 + RT_DIRTY_CAP) * 4); return fail(RT_ERR_INVALID, "sampler retry list overflow"); } }
   stats.camera_rays = h[ST_CAMERA];  // counted by k_raygen: samples inside pixel_bounds and the film's sample rows
   stats.rays_mis_any = h[ST_RAYS_MISANY]; stats.nodes_mis_any = h[ST_NODES_MISANY]; stats.tris_mis_any = h[ST_TRIS_MISANY];
-  stats.rays_closest = h[ST_RAYS_CLOSEST] + h[ST_TAIL_UNCAST]; stats.rays_tail_not_cast = h[ST_TAIL_UNCAST]; stats.rays_shadow = h[ST_RAYS_SHADOW]; stats.rays_mis = h[ST_RAYS_MIS] + h[ST_RAYS_MISANY] + h[ST_MIS_UNREACHED];
+  stats.rays_closest = h[ST_RAYS_CLOSEST] + h[ST_TAIL_UNCAST]; stats.rays_tail_not_cast = h[ST_TAIL_UNCAST]; stats.rays_shadow = h[ST_RAYS_SHADOW] + h[ST_SHADOW_SETS]; stats.rays_shadow_not_cast = h[ST_SHADOW_SETS]; stats.rays_mis = h[ST_RAYS_MIS] + h[ST_RAYS_MISANY] + h[ST_MIS_UNREACHED];
   stats.rays_mis_not_cast = h[ST_MIS_UNREACHED];
   stats.nodes_closest = h[ST_NODES_CLOSEST]; stats.nodes_shadow = h[ST_NODES_SHADOW]; stats.nodes_mis = h[ST_NODES_MIS] + h[ST_NODES_MISANY];
   stats.tris_closest = h[ST_TRIS_CLOSEST]; stats.tris_shadow = h[ST_TRIS_SHADOW]; stats.tris_mis = h[ST_TRIS_MIS] + h[ST_TRIS_MISANY];
@@ -1740,7 +1792,7 @@ __global__ void k_film_add(float4* __restrict__ dst, const float4* __restrict__ 
 }
 // every counter and every timer of b added into a
 static void stats_add(rt_stats& a, const rt_stats& b) {
-  a.camera_rays += b.camera_rays; a.rays_closest += b.rays_closest; a.rays_shadow += b.rays_shadow; a.rays_mis += b.rays_mis; a.rays_mis_not_cast += b.rays_mis_not_cast; a.rays_tail_not_cast += b.rays_tail_not_cast;
+  a.camera_rays += b.camera_rays; a.rays_closest += b.rays_closest; a.rays_shadow += b.rays_shadow; a.rays_mis += b.rays_mis; a.rays_mis_not_cast += b.rays_mis_not_cast; a.rays_tail_not_cast += b.rays_tail_not_cast; a.rays_shadow_not_cast += b.rays_shadow_not_cast;
   a.nodes_closest += b.nodes_closest; a.nodes_shadow += b.nodes_shadow; a.nodes_mis += b.nodes_mis;
   a.tris_closest += b.tris_closest; a.tris_shadow += b.tris_shadow; a.tris_mis += b.tris_mis; a.paths_scrubbed += b.paths_scrubbed;
   a.ms_total += b.ms_total; a.ms_sampler += b.ms_sampler; a.ms_raygen += b.ms_raygen; a.ms_trace_closest += b.ms_trace_closest; a.ms_trace_any += b.ms_trace_any;

@@ -1254,6 +1254,12 @@ int rtxh_scene_link_tables(rtxh_scene* s, int32_t mid, uint32_t* link_kept, uint
   rt_scene_desc d = make_desc(s);
   return rt_link_tables(&d, mid, link_kept, link_full, capacity_words, stats);
 }
+int rtxh_scene_shadow_sets(rtxh_scene* s, uint32_t* words, uint64_t capacity_words, int32_t n_voxels[3], uint64_t* stats) {
+  if (!s || !s->committed) return fail(RT_ERR_INVALID, "scene not committed");
+  g_err.clear();
+  rt_scene_desc d = make_desc(s);
+  return rt_shadow_sets(&d, words, capacity_words, n_voxels, stats);
+}
 int rtxh_sizeof(const char* name) {
   if (!name) return -1;
 #define RTXH_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);

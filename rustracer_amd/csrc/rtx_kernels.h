@@ -128,6 +128,7 @@ struct PassState {
                                 // 0 / 1 / 2 / 3: S2 1509 / 1533 / 1523 / 1556, S3 1816 / 1825 / 1828 / 1842, S4 447.0 / 445.3 / 448.2 / 446.6
 #define RT_FRESH_BETA(ps) (((ps).fresh & 1) != 0)
 #define RT_FRESH_ST(ps) (((ps).fresh & 2) != 0)
+  int shadow_sets;    // k_shade: a shadow segment whose voxel / light pair is EMPTY (ld_rows8 r0.w / r1.w, rtx_shadow_sets.h) is answered without a walk (off on frames that count node visits)
   int mis_any;        // BSDF-sampled MIS rays toward an infinite light go to q_misany (off on frames that count node visits: reference walk)
   // Sphere::pdf_wi answers with the cone's uniform density for ANY direction (sphere.rs:310-334 never tests wi against the cone), so estimate_direct casts the
   // BSDF-sampled ray of every vertex whose picked light is a sphere - 150x the MIS rays of the tessellated S3 - and drops all that do not end on the sphere. A ray
@@ -143,6 +144,10 @@ struct PassState {
   unsigned long long* stats;  // device-side u64 counters, see ST_* below
 };
 #define RT_NQ 4  // queues a bounce fills
+// the kind of a voxel / light pair's shadow sets (rtx_shadow_sets.h) in the spare words of its ld_rows8 record
+#define RT_SHADOW_WALK 0u
+#define RT_SHADOW_EMPTY 1u
+#define RT_SHADOW_KIND(w) ((w) & 3u)
 enum { ST_CAMERA = 0, ST_RAYS_CLOSEST, ST_RAYS_SHADOW, ST_RAYS_MIS, ST_NODES_CLOSEST, ST_NODES_SHADOW, ST_NODES_MIS,
        ST_TRIS_CLOSEST, ST_TRIS_SHADOW, ST_TRIS_MIS, ST_SCRUBBED, ST_UNBUILT_VOXEL,
        ST_RAYS_MISANY, ST_NODES_MISANY, ST_TRIS_MISANY,  // the occlusion-only MIS rays (also counted in the _MIS entries)
@@ -150,7 +155,8 @@ enum { ST_CAMERA = 0, ST_RAYS_CLOSEST, ST_RAYS_SHADOW, ST_RAYS_MIS, ST_NODES_CLO
        ST_TAIL_UNCAST,    // path rays at the depth limit after a non-specular bounce: not cast (PassState::skip_dead_tail)
        ST_SHADED,  // + {0: k_shade<1>, 1: k_shade<3>, 2: k_shade<5>, 3: k_shade<0>}: path vertices shaded by each front-end (misses included)
        ST_STAMP = ST_SHADED + 4,  // + 8 * front-end + section: wave cycles of the sections of k_shade (measurement builds only, make ABLATE=1)
-       ST_COUNT = ST_STAMP + 32 };
+       ST_SHADOW_SETS = ST_STAMP + 32,  // shadow segments of EMPTY voxel / light pairs: unoccluded for certain, not cast (PassState::shadow_sets)
+       ST_COUNT };
 #ifdef RT_ABLATE
 #define RT_STAMP(k) do { const unsigned long long t_ = clock64(); stamp_acc[k] += t_ - stamp_last; stamp_last = t_; } while (0)
 #else
@@ -2426,6 +2432,16 @@ static __global__ void __launch_bounds__(256) k_lightdist_dense8(const float4* _
   const int slot = slot_of[v];
   out[2 * v] = slot >= 0 ? rows8[2 * (size_t)slot] : make_float4(-1.0f, 0.0f, 0.0f, 0.0f);
   out[2 * v + 1] = slot >= 0 ? rows8[2 * (size_t)slot + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+// the shadow-set words of the built voxels (rtx_shadow_sets.h) into their records' spare words: r0.w = light 0's, r1.w = light 1's (both 0 from k_lightdist_rows8 when n_lights <= 2)
+static __global__ void __launch_bounds__(256) k_lightdist_shadow_words(const unsigned* __restrict__ word, const int* __restrict__ slot_of, unsigned long long n_voxels, float4* __restrict__ rows8, float4* __restrict__ dense8) {
+  const unsigned long long v = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_voxels) return;
+  const int slot = slot_of[v];
+  if (slot < 0) return;
+  float* r = (float*)(rows8 + 2 * (size_t)slot);
+  r[3] = __uint_as_float(word[2 * v]); r[7] = __uint_as_float(word[2 * v + 1]);
+  if (dense8) { float* q = (float*)(dense8 + 2 * v); q[3] = r[3]; q[7] = r[7]; }
 }
 static __global__ void __launch_bounds__(256) k_light_consts(DScene sc, DLight* __restrict__ lights, int n_all /* sampled lights + unlisted emitters */) {
   const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);

@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
   unsigned first = 0, count = ps.cnt_in ? qv.total() : ps.cap;  // no counts: bounce 0 of a pass whose samples are all traced (entry i = slot i = path i)
   if (MODE != 1 && ps.range) { first = ps.range[0]; count = ps.range[1]; }
   const unsigned stride = gridDim.x * blockDim.x;
-  unsigned n_shaded = 0, n_unreached = 0, n_tail = 0;
+  unsigned n_shaded = 0, n_unreached = 0, n_tail = 0, n_no_walk = 0;
   const DScene& gsc = *sc.self;  // what out-of-line functions get: the scene record in device memory, not a private copy of the kernel argument
 #ifdef RT_ABLATE
   unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = clock64();
@@ -362,7 +362,7 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
   // end are workgroup-wide).
   auto shade_vertex = [&](const bool lane_live, const unsigned i, const unsigned rslot) {
     RT_STAMP(7);  // loop overhead / previous iteration's tail
-    bool cont = false, want_shadow = false, want_mis = false, mis_occlusion_only = false, tail = false;
+    bool cont = false, want_shadow = false, want_mis = false, mis_occlusion_only = false, tail = false, no_walk = false;
     // what a continuing path takes to its slot in the next bounce's queue (stored after the append below has named the slot)
     f3 nr_o = mk3(0, 0, 0), nr_d = mk3(0, 0, 0); rgb3 beta = mkc(0, 0, 0); float eta_scale = 1.0f; unsigned st_out = 0u, pid = 0u; unsigned long long rng_out = 0ull;
     if (lane_live) {
@@ -459,6 +459,10 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
           else if (rows8) d1_sample_discrete_row8(ld_r0, ld_r1, sc.n_lights, su, light_num, light_pdf);
           else if (MODE != 1 && sc.ld_glog >= 0) d1_sample_discrete_guided(ld_func, ld_cdf, ld_int, sc.n_lights, su, sc.ld_guide + ld_row * ((1 << sc.ld_glog) + 1), sc.ld_glog, light_num, light_pdf);
           else d1_sample_discrete(ld_func, ld_cdf, ld_int, sc.n_lights, su, light_num, light_pdf);
+          // Shadow sets (rtx_shadow_sets.h): the spare word of the voxel's record for the picked light (two lights) says EMPTY when no segment from
+          // this voxel to the light can be occluded - the segment is then not cast and its answer, "unoccluded", is applied below as the any-hit kernel would apply it
+          // (the constant-Kd Lambert front-end only, the one the scenes of two area lights in LDS reach most: the other forms keep their register budgets)
+          const bool ld_empty = MODE == 1 && ps.shadow_sets && RT_SHADOW_KIND(__float_as_uint(light_num == 0 ? ld_r0.w : ld_r1.w)) == RT_SHADOW_EMPTY;
           RT_STAMP(3);  // light pick: voxel row + discrete search
           if (light_pdf != 0.0f) {
             f2 u_light = smp.get_2d();
@@ -481,7 +485,7 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
               float scattering_pdf = ((MODE != 1 && !LEAN) && light_is_delta(light)) ? 0.0f : bsdf.pdf(si.hit.wo, ls.wi, nonspec);  // read by the power heuristic only: a delta light has none
               if (!is_black(f)) {
                 Ray sr = spawn_ray_to_interaction(si.hit, ls.p1);  // VisibilityTester, light/mod.rs:52-55
-                sh_o[i] = make_float4(sr.o.x, sr.o.y, sr.o.z, sr.t_max);  // (shadow and MIS records sit at the vertex's position in THIS launch's queue, see PassState::sh)
+                if (!ld_empty) sh_o[i] = make_float4(sr.o.x, sr.o.y, sr.o.z, sr.t_max);  // (shadow and MIS records sit at the vertex's position in THIS launch's queue, see PassState::sh)
                 sh_dir = sr.d;
                 want_shadow = true;
                 if (light_is_delta(light)) ld1 = vdiv(f * ls.li, ls.pdf);
@@ -519,17 +523,20 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
                 }
               }
             }
+            no_walk = want_shadow && ld_empty;
             if (want_mis) {  // both halves are combined by k_resolve once both rays are back
               mi_a[i] = make_float4(ld1.r, ld1.g, ld1.b, light_pdf);
               mi_b[i] = make_float4(f2v.r, f2v.g, f2v.b, w2);
               mi_c[i] = make_float4(beta.r, beta.g, beta.b, spdf2);
               mi_flags[i] = (want_shadow ? RT_PEND_SHADOW : 0u) | 2u | ((unsigned)light_num << 2) | (mis_occlusion_only ? RT_PEND_MIS_ANY : 0u);
-              if (!want_shadow) ps.occ_sh[i] = (unsigned char)1;  // no light-sampling term: as good as blocked (the any-hit kernel writes the byte of every other vertex)
-            } else if (want_shadow) {  // L += beta * ((0 + Ld1) / pick_pdf) if unoccluded, applied by the any-hit kernel
+              if (!want_shadow || no_walk) ps.occ_sh[i] = no_walk ? (unsigned char)0 : (unsigned char)1;  // no light-sampling term: as good as blocked (the any-hit kernel writes the byte of every other vertex)
+            } else if (want_shadow) {  // L += beta * ((0 + Ld1) / pick_pdf) if unoccluded, applied by the any-hit kernel (trace_write_any) - or here, with the same sum
               rgb3 add = beta * vdiv(mkc(0, 0, 0) + ld1, light_pdf);
-              sh_add[i] = make_float4(add.r, add.g, add.b, 0.0f);
+              if (no_walk) { const float4 l4 = ps.lacc[pid]; ps.lacc[pid] = make_float4(l4.x + add.r, l4.y + add.g, l4.z + add.b, l4.w); }
+              else sh_add[i] = make_float4(add.r, add.g, add.b, 0.0f);
             }
-            if (want_shadow) sh_d[i] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, __uint_as_float((want_mis ? 0u : 0x80000000u) | pid));  // bit 31: complete here (no MIS ray), bits 0-30: the path
+            if (want_shadow && !no_walk) sh_d[i] = make_float4(sh_dir.x, sh_dir.y, sh_dir.z, __uint_as_float((want_mis ? 0u : 0x80000000u) | pid));  // bit 31: complete here (no MIS ray), bits 0-30: the path
+            want_shadow = want_shadow && !no_walk;  // (from here on: a record in the shadow queue)
           }
         }
         RT_STAMP(5);  // BSDF-sampling half + records
@@ -562,6 +569,7 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
     // (a wave-uniform count, kept in a scalar register: a per-lane counter is one more live vector register in every form, and an atomic where the paths end
     // is ~7 M atomics on one word in the launch at the depth limit - k_shade<1> 271 -> 329 ms per S1 frame, measured)
     n_tail += (unsigned)__popcll(__ballot(tail));
+    n_no_walk += (unsigned)__popcll(__ballot(no_walk));
     constexpr int NQ = (MODE == 1 || LEAN) ? 3 : 4;  // area lights only: every MIS ray needs its closest hit
     const int ci[4] = {0, 1, 2, 3}; const bool pr[4] = {cont, want_shadow, want_mis && !mis_occlusion_only, want_mis && mis_occlusion_only}; unsigned slot[4];
     block_push<NQ>(ps.cnt_out, ps.shard_cap, ci, pr, slot);
@@ -625,6 +633,7 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
     if ((threadIdx.x & 63u) == 0u && n_unreached) atomicAdd(&ps.stats[ST_MIS_UNREACHED], (unsigned long long)n_unreached);
   }
   if ((threadIdx.x & 63u) == 0u && n_tail) atomicAdd(&ps.stats[ST_TAIL_UNCAST], (unsigned long long)n_tail);  // (the wave's count, the same in every lane)
+  if ((threadIdx.x & 63u) == 0u && n_no_walk) atomicAdd(&ps.stats[ST_SHADOW_SETS], (unsigned long long)n_no_walk);
   for (int off = 32; off > 0; off >>= 1) n_shaded += __shfl_down(n_shaded, off);
   if ((threadIdx.x & 63u) == 0u && n_shaded) atomicAdd(&ps.stats[ST_SHADED + (MODE == 1 ? 0 : (MODE == 3 ? 1 : (MODE == 5 || MODE == 6 ? 2 : 3)))], (unsigned long long)n_shaded);
 #ifdef RT_ABLATE

@@ -80,7 +80,7 @@ class Stats(C.Structure):
         [(n, C.c_double) for n in ("ms_shade_lambert_const", "ms_shade_lambert", "ms_shade_two_lobe", "ms_shade_generic", "ms_shade_bin", "ms_shade_miss")] +
         [("shade_section_cycles", C.c_uint64 * 32)] +
         [(n, C.c_uint64) for n in ("rays_mis_any", "nodes_mis_any", "tris_mis_any")] + [("ms_trace_mis_any", C.c_double), ("ms_gather", C.c_double), ("rays_mis_not_cast", C.c_uint64), ("rays_tail_not_cast", C.c_uint64)] +
-        [(n, C.c_uint64) for n in ("launches_trace_path", "launches_trace_shadow", "launches_trace_mis", "launches_trace_mis_any", "launches_shade")])
+        [(n, C.c_uint64) for n in ("launches_trace_path", "launches_trace_shadow", "launches_trace_mis", "launches_trace_mis_any", "launches_shade", "rays_shadow_not_cast")])
 
     def as_dict(self):
         return {n: (list(getattr(self, n)) if n == "shade_section_cycles" else getattr(self, n)) for n, _ in self._fields_}
@@ -274,6 +274,19 @@ class HostScene:
             return rows, np.concatenate([t[8 * nn:8 * nn + 8], t[9 * nn + 8:9 * nn + 9]])
         (rk, sk), (rf, sf) = split(kept), split(full)
         return dict(kept=rk, full=rf, start_kept=sk, start_full=sf, rays=stats[:9], tests_all=stats[9:18], tests_kept=stats[18:27])
+
+    def shadow_sets(self):
+        """The shadow sets rt_scene_create gives an LDS-resident plain-triangle scene of two triangle lights (rt_shadow_sets: host only, no device), as
+        dict(nvox=(nx, ny, nz), kind=[nz, ny, nx, 2] (1 = EMPTY: no shadow segment from the voxel to the light can be occluded, 0 = walk), pairs=, empty=)."""
+        nv, st = np.zeros(3, np.int32), np.zeros(2, np.uint64)
+        _check(lib().rtxh_scene_shadow_sets(self.h, None, C.c_uint64(0), _p(nv, C.c_int32), _p(st, C.c_uint64)), "rtxh_scene_shadow_sets")
+        words = np.zeros(2 * int(np.prod(nv)), np.uint32)
+        _check(lib().rtxh_scene_shadow_sets(self.h, _p(words, C.c_uint32), C.c_uint64(words.size), _p(nv, C.c_int32), _p(st, C.c_uint64)), "rtxh_scene_shadow_sets")
+        return dict(nvox=tuple(int(x) for x in nv), kind=(words & 3).reshape(int(nv[2]), int(nv[1]), int(nv[0]), 2), pairs=int(st[0]), empty=int(st[1]))
+
+    def scene_query(self, what):
+        """rt_scene_query of the uploaded scene (RT_QUERY_* of rtx_hip.h)."""
+        return _check(lib().rtxh_scene_query(self.h, C.c_int32(what)), "scene_query")
 
     def lds_resident(self):
         """Does the traversal kernel keep this scene's nodes and primitives in LDS? Asked of the uploaded scene (rt_scene_query: what rt_scene_create decided,
