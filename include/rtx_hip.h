@@ -92,7 +92,13 @@ typedef struct rt_texture {
   float mapping[4];           /* UVMapping2D su sv du dv (rc/texture/mod.rs:38-61)      */
 } rt_texture;
 
-/* -- MIP pyramid built by the host: replaces MIPMap<Spectrum> (rc/mipmap.rs:46-53) --------- */
+/* -- MIP pyramid built by the host: replaces MIPMap<Spectrum> (rc/mipmap.rs:46-53) ---------
+ * An image with n_levels == 0 is a Fourier BSDF table instead (FourierBSDFTable, rc/bsdf/fourier.rs:281-371) that an RT_MAT_FOURIER material names:
+ * `texels` points to 3 * n_texels packed 32-bit words (zero-padded to a whole texel) - the header {nMu, mMax, nChannels, nCoeffs as u32, eta as f32},
+ * then mu[nMu] (f32, strictly ascending), cdf[nMu * nMu] (f32), offset_and_length[2 * nMu * nMu] (u32) and a[nCoeffs] (f32), as a .bsdf file lists them.
+ * rt_scene_create / rt_multi_create refuse with RT_ERR_INVALID (before any device is touched) a table whose sizes do not add up, with nMu outside [2, 8192],
+ * nChannels not 1 or 3, mu not ascending, a cell longer than mMax or whose coefficients run past nCoeffs, more than 2^28 table words in the scene, a Fourier
+ * material whose slot M1 names a MIP pyramid, and an image texture or infinite light that names a table. width / height / offset / trilinear / wrap are unused. */
 enum { RT_WRAP_REPEAT = 0, RT_WRAP_BLACK = 1, RT_WRAP_CLAMP = 2 };
 #define RT_MAX_MIP_LEVELS 16
 typedef struct rt_image {
@@ -110,7 +116,9 @@ typedef struct rt_image {
 enum { RT_MAT_MATTE = 0, RT_MAT_PLASTIC, RT_MAT_METAL, RT_MAT_MIRROR, RT_MAT_GLASS, RT_MAT_UBER, RT_MAT_SUBSTRATE, RT_MAT_MIX, RT_MAT_TRANSLUCENT,
        RT_MAT_DISNEY /* rc/material/disney.rs; slots: KD color, KS metallic, ETA eta, ROUGHNESS roughness, KR speculartint, UROUGH anisotropic,
                         KT sheen, SIGMA sheentint, VROUGH clearcoat, K clearcoatgloss, OPACITY spectrans, REFLECT scatterdistance,
-                        TRANSMIT flatness, AMOUNT difftrans, M1 = thin (0 / 1, not an id) */ };
+                        TRANSMIT flatness, AMOUNT difftrans, M1 = thin (0 / 1, not an id) */,
+       RT_MAT_FOURIER /* rc/material/fourier.rs; M1 = index into images[] of its Fourier BSDF table (n_levels == 0, see rt_image; not a texture id);
+                         bump as for the other kinds; the other slots are -1 */ };
 enum { RT_SLOT_KD = 0, RT_SLOT_KS, RT_SLOT_KR, RT_SLOT_KT, RT_SLOT_SIGMA, RT_SLOT_ROUGHNESS, RT_SLOT_UROUGH, RT_SLOT_VROUGH,
        RT_SLOT_ETA, RT_SLOT_K, RT_SLOT_OPACITY, RT_SLOT_REFLECT, RT_SLOT_TRANSMIT, RT_SLOT_AMOUNT, RT_SLOT_M1, RT_SLOT_M2, RT_N_SLOTS };
 typedef struct rt_material {
@@ -336,6 +344,11 @@ int rt_sampler_tables_plain(int32_t spp, int32_t dimensions, uint64_t pixel0, ui
  * direction w as n x 3 floats each, out n x 3. The device function every spawned ray goes through (Interaction::spawn_ray / spawn_ray_to, rc/interaction.rs:
  * 56-74), exposed for the parity tests (zeros of both signs, infinities, denormals, NaN). Host pointers. */
 int rt_offset_ray_origin(const float* p, const float* p_error, const float* n, const float* w, uint64_t count, float* out);
+
+/* FourierBSDF::f, ::pdf and ::sample_f (rc/bsdf/fourier.rs:45-278) of RT_MAT_FOURIER material `material` of the scene, run by the device lobe functions of
+ * the shade kernel on n queries in the shading frame (TransportMode::RADIANCE, no bump map, no mix): wo, wi n x 3 floats, u n x 2 (sample_f's u[0], u[1]).
+ * out: n x 11 floats - f(wo, wi) rgb, pdf(wo, wi), then sample_f(wo, u): f rgb, wi xyz, pdf. Host pointers. For the parity tests. */
+int rt_fourier_eval(rt_scene* scene, int32_t material, uint64_t n, const float* wo, const float* wi, const float* u, float* out);
 
 /* Dense voxel light distribution of SpatialLightDistribution (rc/lightdistrib.rs:101-179):
  * n_voxels[3]; func: nvox*n_lights, cdf: nvox*(n_lights+1), func_int: nvox (host pointers, may be NULL

@@ -91,6 +91,10 @@ int rtxh_scene_set_alpha(rtxh_scene*, const int32_t* tri_alpha2);
  * different threads do not affect each other) and applies to the scenes that thread builds afterwards, rtxh_pbrt_load included. */
 void rtxh_set_device_ingest(int32_t on);
 int rtxh_scene_add_mipmap(rtxh_scene*, int32_t width, int32_t height, const float* rgb, int32_t trilinear, float max_aniso, int32_t wrap);
+/* Material "fourier" (rc/material/fourier.rs): reads the .bsdf table at `path` (FourierBSDFTable::read, rc/bsdf/fourier.rs:294-371; little-endian) and returns
+ * its image id - an rt_image with n_levels == 0 (rtx_hip.h) for slot M1 of an RT_MAT_FOURIER material - or -1 with rtxh_last_error() naming the file. A path
+ * read before returns the same id. */
+int rtxh_scene_add_fourier_table(rtxh_scene*, const char* path);
 int rtxh_scene_add_texture(rtxh_scene*, int32_t kind, const float* value3, int32_t tex1, int32_t tex2, int32_t amount, int32_t mip, const float* mapping4);
 int rtxh_scene_add_material(rtxh_scene*, int32_t kind, const int32_t* slots16, int32_t remap_roughness, int32_t bump_texture /* or -1 */);
 int rtxh_scene_add_light(rtxh_scene*, int32_t kind, int32_t tri, const float* rgb3, int32_t two_sided, const float* vec3, int32_t mip,
@@ -142,6 +146,8 @@ int rtxh_trace_device(rtxh_scene*, const void* d_rays, uint64_t n, void* d_hits,
 int rtxh_light_distribution(rtxh_scene*, int32_t n_voxels[3], float* func, float* cdf, float* func_int);
 /* rt_scene_query on the uploaded scene (uploads it first if need be; rtx_hip.h: RT_QUERY_*). */
 int rtxh_scene_query(rtxh_scene*, int32_t what);
+/* The rt_scene of the uploaded scene (uploads it first if need be), for the kernel-level entry points of rtx_hip.h (rt_fourier_eval). Owned by the rtxh_scene. */
+int rtxh_scene_device(rtxh_scene*, rt_scene** out);
 /* rt_link_tables on the scene's description (host only: nothing is uploaded). */
 int rtxh_scene_link_tables(rtxh_scene*, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats);
 /* rt_shadow_sets of the committed scene (host only, no device). */

@@ -103,7 +103,8 @@ RT_DEVN rgb3 fr_conductor(float cos_theta_i, rgb3 eta_i, rgb3 eta_t, rgb3 k) {  
 
 // ---------------------------------------------------------------- lobes
 enum { LB_LAMBERT_R = 0, LB_LAMBERT_T, LB_OREN_NAYAR, LB_SPEC_R, LB_SPEC_T, LB_FRESNEL_SPEC, LB_FRESNEL_BLEND, LB_MICRO_R, LB_MICRO_T,
-       LB_DISNEY_DIFFUSE, LB_DISNEY_FAKESS, LB_DISNEY_RETRO, LB_DISNEY_SHEEN, LB_DISNEY_CLEARCOAT };  // rc/material/disney.rs:215-418
+       LB_DISNEY_DIFFUSE, LB_DISNEY_FAKESS, LB_DISNEY_RETRO, LB_DISNEY_SHEEN, LB_DISNEY_CLEARCOAT,  // rc/material/disney.rs:215-418
+       LB_FOURIER };  // rc/bsdf/fourier.rs; the table's address sits in ax / ay (lobe_set_table)
 // fr_kind: bits 0-1 = Fresnel kind; bit 2 = the microfacet distribution is Disney's (separable masking-shadowing, disney.rs:444-476)
 enum { FR_NOOP = 0, FR_DIELECTRIC = 1, FR_CONDUCTOR = 2, FR_DISNEY = 3, FR_SEPARABLE_G = 4 };
 struct Lobe {
@@ -111,7 +112,7 @@ struct Lobe {
   rgb3 r;        // R / T / FresnelSpecular R / FresnelBlend Rd
   rgb3 t;        // FresnelSpecular T / FresnelBlend Rs / conductor eta_t / DisneyFresnel R0
   rgb3 k;        // conductor k
-  float ax, ay;  // Trowbridge-Reitz alphas, or Oren-Nayar A, B; Disney FakeSS / Retro: ax = roughness; ClearCoat: ax = weight, ay = gloss
+  float ax, ay;  // Trowbridge-Reitz alphas, or Oren-Nayar A, B; Disney FakeSS / Retro: ax = roughness; ClearCoat: ax = weight, ay = gloss; Fourier: the table's address
   float eta_a, eta_b;  // transmission lobes / FresnelSpecular; dielectric Fresnel uses (fr_ei, fr_et)
   float fr_ei, fr_et;  // DisneyFresnel: metallic, eta
   int n_scales; rgb3 scale0, scale1;  // ScaledBxDF nesting (bxdf.rs:48-71), innermost first
@@ -128,6 +129,7 @@ RT_DEV unsigned lobe_type(int kind) {
     case LB_MICRO_R: return BSDF_REFLECTION | BSDF_GLOSSY;
     case LB_DISNEY_DIFFUSE: case LB_DISNEY_FAKESS: case LB_DISNEY_RETRO: case LB_DISNEY_SHEEN: return BSDF_REFLECTION | BSDF_DIFFUSE;
     case LB_DISNEY_CLEARCOAT: return BSDF_REFLECTION | BSDF_GLOSSY;
+    case LB_FOURIER: return BSDF_REFLECTION | BSDF_TRANSMISSION | BSDF_GLOSSY;  // fourier.rs:275-277
     default: return BSDF_TRANSMISSION | BSDF_GLOSSY;
   }
 }
@@ -235,8 +237,226 @@ RT_DEV bool sharp_lobe(const Lobe& l) {
 #endif
 }
 
+struct LobeSample { rgb3 f; f3 wi; float pdf; unsigned type; };
+RT_DEV LobeSample mk_ls(rgb3 f, f3 wi, float pdf, unsigned type) { LobeSample s; s.f = f; s.wi = wi; s.pdf = pdf; s.type = type; return s; }
+
+// ---------------------------------------------------------------- FourierBSDF (rc/bsdf/fourier.rs, rc/interpolation.rs), in f32 as the reference has it
+// The table is an rt_image with n_levels == 0 (rtx_hip.h): words {nMu, mMax, nChannels, nCoeffs, eta}, mu[nMu], cdf[nMu^2], {offset, length}[nMu^2], a[nCoeffs],
+// validated by rt_scene_create. The reference's per-call ak[mMax * nChannels] is never built: a per-lane array of runtime length lives in scratch. Each
+// ak[c mMax + k] is recomputed where it is read, as the same sum over the <= 16 cells of the (muI, muO) stencil in the reference's order (b outer, a inner,
+// zero weights skipped) - with contraction off that is the reference's accumulated value bit for bit.
+RT_DEV void lobe_set_table(Lobe& l, const unsigned* tab) {
+  const unsigned long long p = (unsigned long long)tab;
+  l.ax = __uint_as_float((unsigned)p); l.ay = __uint_as_float((unsigned)(p >> 32));
+}
+RT_DEV const unsigned* lobe_table(const Lobe& l) {
+  return (const unsigned*)(((unsigned long long)__float_as_uint(l.ay) << 32) | (unsigned long long)__float_as_uint(l.ax));
+}
+struct FourierTab {
+  const float* mu; const float* cdf; const unsigned* ol; const float* a; int n_mu, n_ch; float eta;
+};
+RT_DEV FourierTab fourier_tab(const unsigned* w) {
+  FourierTab t; t.n_mu = (int)w[0]; t.n_ch = (int)w[2]; t.eta = __uint_as_float(w[4]);
+  const size_t n = (size_t)t.n_mu;
+  t.mu = (const float*)(w + 5); t.cdf = t.mu + n; t.ol = w + 5 + n + n * n; t.a = (const float*)(w + 5 + n + 3 * n * n);
+  return t;
+}
+RT_DEV int fourier_find_interval(const float* nodes, int size, float x) {  // find_interval(size, |i| nodes[i] <= x), rc/lib.rs:171-189
+  int first = 0, len = size;
+  while (len > 0) {
+    const int half = len >> 1, middle = first + half;
+    if (nodes[middle] <= x) { first = middle + 1; len -= half + 1; } else len = half;
+  }
+  return clampi(first - 1, 0, size - 2);
+}
+RT_DEV bool catmull_rom_weights(const float* nodes, int size, float x, int& offset, float w[4]) {  // interpolation.rs:97-145
+  if (!(x >= nodes[0] && x <= nodes[size - 1])) return false;
+  const int idx = fourier_find_interval(nodes, size, x);
+  offset = idx - 1;
+  const float x0 = nodes[idx], x1 = nodes[idx + 1];
+  const float t = (x - x0) / (x1 - x0), t2 = t * t, t3 = t2 * t;
+  w[1] = 2.0f * t3 - 3.0f * t2 + 1.0f;
+  w[2] = -2.0f * t3 + 3.0f * t2;
+  if (idx > 0) { const float w0 = (t3 - 2.0f * t2 + t) * (x1 - x0) / (x1 - nodes[idx - 1]); w[0] = -w0; w[2] += w0; }
+  else { const float w0 = t3 - 2.0f * t2 + t; w[0] = 0.0f; w[1] -= w0; w[2] += w0; }
+  if (idx + 2 < size) { const float w3 = (t3 - t2) * (x1 - x0) / (nodes[idx + 2] - x0); w[1] -= w3; w[3] = w3; }
+  else { const float w3 = t3 - t2; w[1] -= w3; w[2] += w3; w[3] = 0.0f; }
+  return true;
+}
+// The cells of one (muI, muO) pair: weight, first coefficient and order of cell j = 4 b + a (b: the muO node, a: the muI node). A cell of zero weight has
+// order 0 and is never read. Every loop over j is unrolled, so the arrays are registers.
+struct FourierCells {
+  float w[16]; unsigned off[16]; int m[16]; int m_max;
+  float wo[4]; int off_o;
+  RT_DEV float ak(const float* a, int c, int k) const {  // ak[c mMax + k] of fourier.rs:71-87 / 232-246
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) if (k < m[j]) s += w[j] * a[off[j] + (unsigned)(c * m[j] + k)];
+    return s;
+  }
+};
+RT_DEV bool fourier_cells(const FourierTab& t, float mu_i, float mu_o, FourierCells& cl) {
+  float wi[4]; int off_i;
+  const bool ok_i = catmull_rom_weights(t.mu, t.n_mu, mu_i, off_i, wi);
+  const bool ok_o = catmull_rom_weights(t.mu, t.n_mu, mu_o, cl.off_o, cl.wo);
+  if (!ok_i || !ok_o) return false;
+  cl.m_max = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int j = 4 * b + a;
+      const float weight = wi[a] * cl.wo[b];
+      cl.w[j] = weight; cl.off[j] = 0u; cl.m[j] = 0;
+      if (weight != 0.0f) {
+        const size_t cell = (size_t)(cl.off_o + b) * (size_t)t.n_mu + (size_t)(off_i + a);
+        cl.off[j] = t.ol[2 * cell]; cl.m[j] = (int)t.ol[2 * cell + 1];
+        cl.m_max = max(cl.m_max, cl.m[j]);
+      }
+    }
+  return true;
+}
+RT_DEV float fourier_series(const FourierCells& cl, const float* a, int c, float cos_phi) {  // interpolation.rs:264-277 over ak channel c
+  float value = 0.0f, cos_km1 = cos_phi, cos_k = 1.0f;
+  for (int k = 0; k < cl.m_max; ++k) {
+    value += cl.ak(a, c, k) * cos_k;
+    const float cos_kp1 = 2.0f * cos_phi * cos_k - cos_km1;
+    cos_km1 = cos_k; cos_k = cos_kp1;
+  }
+  return value;
+}
+RT_DEV float fourier_cos_d_phi(f3 wa, f3 wb) {  // fourier.rs:389-397
+  return clampf((wa.x * wb.x + wa.y * wb.y) / sqrtf((wa.x * wa.x + wa.y * wa.y) * (wb.x * wb.x + wb.y * wb.y)), -1.0f, 1.0f);
+}
+RT_DEV float fourier_scale(const FourierTab& t, float mu_i, float mu_o) {  // fourier.rs:91-101 (TransportMode::RADIANCE: the path integrator's mode)
+  float scale = mu_i != 0.0f ? 1.0f / fabsf(mu_i) : 0.0f;
+  if (mu_i * mu_o > 0.0f) { const float eta = mu_i > 0.0f ? 1.0f / t.eta : t.eta; scale *= eta * eta; }
+  return scale;
+}
+RT_DEV rgb3 fourier_rgb(const FourierTab& t, const FourierCells& cl, float y, float scale, float cos_phi) {  // fourier.rs:102-110
+  if (t.n_ch == 1) return grey(y * scale);
+  const float r = fourier_series(cl, t.a, 1, cos_phi), b = fourier_series(cl, t.a, 2, cos_phi);
+  const float g = 1.39829f * y - 0.100913f * b - 0.297375f * r;
+  return mkc(clampf(r * scale, 0.0f, kInf), clampf(g * scale, 0.0f, kInf), clampf(b * scale, 0.0f, kInf));  // Spectrum::clamp
+}
+RT_DEVN rgb3 fourier_f(const unsigned* tab, f3 wo, f3 wi) {  // FourierBSDF::f, fourier.rs:47-111
+  const FourierTab t = fourier_tab(tab);
+  const float mu_i = -wi.z, mu_o = wo.z, cos_phi = fourier_cos_d_phi(-wi, wo);
+  FourierCells cl;
+  if (!fourier_cells(t, mu_i, mu_o, cl)) return mkc(0, 0, 0);
+  const float y = fmaxf(0.0f, fourier_series(cl, t.a, 0, cos_phi));
+  return fourier_rgb(t, cl, y, fourier_scale(t, mu_i, mu_o), cos_phi);
+}
+RT_DEVN float fourier_pdf(const unsigned* tab, f3 wo, f3 wi) {  // FourierBSDF::pdf, fourier.rs:218-272
+  const FourierTab t = fourier_tab(tab);
+  const float mu_i = -wi.z, mu_o = wo.z, cos_phi = fourier_cos_d_phi(-wi, wo);
+  FourierCells cl;
+  if (!fourier_cells(t, mu_i, mu_o, cl)) return 0.0f;
+  float rho = 0.0f;
+#pragma unroll
+  for (int o = 0; o < 4; ++o)
+    if (cl.wo[o] != 0.0f) rho += cl.wo[o] * t.cdf[(size_t)(cl.off_o + o) * (size_t)t.n_mu + (size_t)(t.n_mu - 1)] * (2.0f * kPi);
+  const float y = fourier_series(cl, t.a, 0, cos_phi);
+  return (rho > 0.0f && y > 0.0f) ? y / rho : 0.0f;
+}
+// a0 of the table (fourier.rs:364-370): the first coefficient of a cell, 0 for an empty one
+RT_DEV float fourier_a0(const FourierTab& t, size_t cell) { return t.ol[2 * cell + 1] > 0u ? t.a[t.ol[2 * cell]] : 0.0f; }
+// Newton-bisection loops: the reference iterates until convergence; here at most this many steps, far more than a convergent f32 search takes (a bisection
+// alone halves [0, 1] below 1e-6 in 20), so that no table can keep a lane in the loop
+#define RT_FOURIER_MAX_ITER 64
+RT_DEV float sample_catmull_rom_2d(const FourierTab& t, float alpha, float u, float& pdf) {  // interpolation.rs:6-95 with nodes1 = nodes2 = mu, values = a0
+  const int n = t.n_mu;
+  float w[4]; int off;
+  if (!catmull_rom_weights(t.mu, n, alpha, off, w)) { pdf = 0.0f; return 0.0f; }
+  auto cdf_at = [&](int idx) {
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (w[i] != 0.0f) v += t.cdf[(size_t)(off + i) * (size_t)n + (size_t)idx] * w[i];
+    return v;
+  };
+  auto a0_at = [&](int idx) {
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (w[i] != 0.0f) v += fourier_a0(t, (size_t)(off + i) * (size_t)n + (size_t)idx) * w[i];
+    return v;
+  };
+  const float maximum = cdf_at(n - 1);
+  u *= maximum;
+  int first = 0, len = n;  // find_interval(size2, |i| interpolate(cdf, i) <= u)
+  while (len > 0) {
+    const int half = len >> 1, middle = first + half;
+    if (cdf_at(middle) <= u) { first = middle + 1; len -= half + 1; } else len = half;
+  }
+  const int idx = clampi(first - 1, 0, n - 2);
+  const float f0 = a0_at(idx), f1 = a0_at(idx + 1);
+  const float x0 = t.mu[idx], x1 = t.mu[idx + 1], width = x1 - x0;
+  u = (u - cdf_at(idx)) / width;
+  const float d0 = idx > 0 ? width * (f1 - a0_at(idx - 1)) / (x1 - t.mu[idx - 1]) : f1 - f0;
+  const float d1 = idx + 2 < n ? width * (a0_at(idx + 2) - f0) / (t.mu[idx + 2] - x0) : f1 - f0;
+  float tt = f0 != f1 ? (f0 - sqrtf(fmaxf(0.0f, f0 * f0 + 2.0f * u * (f1 - f0)))) / (f0 - f1) : u / f0;
+  float a = 0.0f, b = 1.0f, fhat_big, fhat;
+  for (int it = 0;; ++it) {
+    if (!(tt >= a && tt <= b)) tt = 0.5f * (a + b);
+    fhat_big = tt * (f0 + tt * (0.5f * d0 + tt * ((1.0f / 3.0f) * (-2.0f * d0 - d1) + f1 - f0 + tt * (0.25f * (d0 + d1) + 0.5f * (f0 - f1)))));
+    fhat = f0 + tt * (d0 + tt * (-2.0f * d0 - d1 + 3.0f * (f1 - f0) + tt * (d0 + d1 + 2.0f * (f0 - f1))));
+    if (fabsf(fhat_big - u) < 1e-6f || b - a < 1e-6f || it + 1 >= RT_FOURIER_MAX_ITER) break;
+    if (fhat_big - u < 0.0f) a = tt; else b = tt;
+    tt -= (fhat_big - u) / fhat;
+  }
+  pdf = fhat / maximum;
+  return x0 + width * tt;
+}
+RT_DEV float sample_fourier(const FourierCells& cl, const float* ak_src, float u, float& pdf, float& phi_out) {  // interpolation.rs:279-352 over ak channel 0
+  const bool flip = u >= 0.5f;
+  u = flip ? 1.0f - 2.0f * (u - 0.5f) : u * 2.0f;
+  const float ak0 = cl.ak(ak_src, 0, 0);
+  float a = 0.0f, b = kPi, phi = 0.5f * kPi, F, f;
+  for (int it = 0;; ++it) {
+    const float cos_phi = cosf(phi);
+    const float sin_phi = sqrtf(fmaxf(0.0f, 1.0f - cos_phi * cos_phi));
+    float cos_prev = cos_phi, cos_cur = 1.0f, sin_prev = -sin_phi, sin_cur = 0.0f;
+    F = ak0 * phi; f = ak0;
+    for (int k = 1; k < cl.m_max; ++k) {
+      const float sin_next = 2.0f * cos_phi * sin_cur - sin_prev;
+      const float cos_next = 2.0f * cos_phi * cos_cur - cos_prev;
+      sin_prev = sin_cur; sin_cur = sin_next; cos_prev = cos_cur; cos_cur = cos_next;
+      const float akk = cl.ak(ak_src, 0, k);
+      F += akk * (1.0f / (float)k) * sin_next;  // recip[k]
+      f += akk * cos_next;
+    }
+    F -= u * ak0 * kPi;
+    if (F > 0.0f) b = phi; else a = phi;
+    if (fabsf(F) < 1e-6f || b - a < 1e-6f || it + 1 >= RT_FOURIER_MAX_ITER) break;
+    phi -= F / f;
+    if (!(phi > a && phi < b)) phi = 0.5f * (a + b);
+  }
+  if (flip) phi = 2.0f * kPi - phi;
+  pdf = 0.15915494309189533577f * f / ak0;  // INV_2_PI
+  phi_out = phi;
+  return f;
+}
+RT_DEVN LobeSample fourier_sample_f(const unsigned* tab, f3 wo, f2 u, bool want_f) {  // FourierBSDF::sample_f, fourier.rs:113-216
+  const FourierTab t = fourier_tab(tab);
+  const unsigned ty = BSDF_REFLECTION | BSDF_TRANSMISSION | BSDF_GLOSSY;
+  const float mu_o = wo.z;
+  float pdf_mu;
+  const float mu_i = sample_catmull_rom_2d(t, mu_o, u.y, pdf_mu);
+  FourierCells cl;
+  if (!fourier_cells(t, mu_i, mu_o, cl)) return mk_ls(mkc(0, 0, 0), mk3(0, 0, 0), 0.0f, ty);
+  float pdf_phi, phi;
+  const float y = sample_fourier(cl, t.a, u.x, pdf_phi, phi);
+  const float pdf = fmaxf(0.0f, pdf_phi * pdf_mu);
+  const float sin2_theta_i = fmaxf(0.0f, 1.0f - mu_i * mu_i);
+  float norm = sqrtf(sin2_theta_i / sin2_theta(wo));
+  if (isinf(norm)) norm = 0.0f;
+  const float sin_phi = sinf(phi), cos_phi = cosf(phi);
+  const f3 wi = normalize(-mk3(norm * (cos_phi * wo.x - sin_phi * wo.y), norm * (sin_phi * wo.x + cos_phi * wo.y), mu_i));
+  return mk_ls(want_f ? fourier_rgb(t, cl, y, fourier_scale(t, mu_i, mu_o), cos_phi) : mkc(0, 0, 0), wi, pdf, ty);
+}
+
 RT_DEV rgb3 lobe_f_inner(const Lobe& l, f3 wo, f3 wi) {
   switch (l.kind) {
+    case LB_FOURIER: return fourier_f(lobe_table(l), wo, wi);
     case LB_LAMBERT_R: case LB_LAMBERT_T: return l.r * kInvPi;
     case LB_OREN_NAYAR: {  // oren_nayar.rs:31-53
       float sin_theta_i = sin_theta(wi), sin_theta_o = sin_theta(wo);
@@ -314,6 +534,7 @@ RT_DEV rgb3 lobe_f_inner(const Lobe& l, f3 wo, f3 wi) {
 }
 RT_DEV float lobe_pdf_inner(const Lobe& l, f3 wo, f3 wi) {
   switch (l.kind) {
+    case LB_FOURIER: return fourier_pdf(lobe_table(l), wo, wi);
     case LB_SPEC_R: case LB_SPEC_T: case LB_FRESNEL_SPEC: return 0.0f;
     case LB_FRESNEL_BLEND: {  // fresnel.rs:376-384
       if (!same_hemisphere(wo, wi)) return 0.0f;
@@ -345,14 +566,13 @@ RT_DEV float lobe_pdf_inner(const Lobe& l, f3 wo, f3 wi) {
     default: return default_pdf(wo, wi);  // Lambertian R and T (quirk 6), Oren-Nayar, Disney diffuse lobes
   }
 }
-struct LobeSample { rgb3 f; f3 wi; float pdf; unsigned type; };
-RT_DEV LobeSample mk_ls(rgb3 f, f3 wi, float pdf, unsigned type) { LobeSample s; s.f = f; s.wi = wi; s.pdf = pdf; s.type = type; return s; }
 // WANT_F = false: the value of a NON-specular lobe is left out (zero). Bsdf::sample_f discards it - for a non-specular sample f is recomputed as the sum over
 // every matching lobe (bsdf/mod.rs:228-247) - and with it goes one full microfacet evaluation (D, G, Fresnel) per sample. Specular lobes always return theirs.
 template <bool WANT_F = true>
 RT_DEV LobeSample lobe_sample_inner(const Lobe& l, f3 wo, f2 u) {
   const unsigned ty = lobe_type(l.kind);
   switch (l.kind) {
+    case LB_FOURIER: return fourier_sample_f(lobe_table(l), wo, u, WANT_F);
     case LB_SPEC_R: {  // fresnel.rs:158-163
       f3 wi = mk3(-wo.x, -wo.y, wo.z);
       return mk_ls(fresnel_eval(l, cos_theta(wi)) * l.r / abs_cos_theta(wi), wi, 1.0f, ty);

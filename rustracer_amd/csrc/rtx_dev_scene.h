@@ -75,6 +75,7 @@ struct DScene {
   // lane by lane at each use (k_shade<3> on S4 moved 4 KB per vertex between L2 and memory, most of it scratch).
   int route_quadric_hits;  // k_bin_count: vertices on analytic quadrics go to a bin of their own in the generic range (scenes shaded by the QLIGHTS forms of k_shade)
   const DScene* self;
+  const unsigned* fourier;  // the words of every Fourier BSDF table (an rt_image with n_levels 0); such an image's DImage::off[0] is its first word here
 #ifdef RT_ABLATE
   int dbg;  // measurement builds only (make ABLATE=1): bits switch parts of the shade kernel off to see what they cost; images are wrong
 #endif

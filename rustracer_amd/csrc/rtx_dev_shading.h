@@ -452,6 +452,11 @@ RT_DEVN float material_lobes(const DScene& sc, const DMaterial& m, const Surface
       eta = 1.0f;  // Bsdf::new(si, 1.0, ..), :212
       break;
     }
+    case 10: {  // fourier.rs:30-42 - one FourierBSDF over the table images[slot 14] (an rt_image of n_levels 0: rt_scene_create placed its words in sc.fourier)
+      Lobe l = lobe_zero(LB_FOURIER); lobe_set_table(l, sc.fourier + sc.images[s[14]].off[0]); bsdf_add(b, l);
+      eta = 1.0f;  // Bsdf::new(si, 1.0, ..)
+      break;
+    }
     default: break;
   }
   return eta;

@@ -82,6 +82,9 @@ struct rt_scene {
   DevBuf quads; bool use_quads = false; int quad_stack_depth = 0;  // four-wide records of the any-hit kernel (k_trace_quad)
   DevBuf tri_rec;  // per-triangle shade records (k_tri_records)
   DevBuf nodes, tri_p, tri_n, tri_uv, tri_s, tri_alpha, spheres, textures, images, materials, lights, texels, dist, guides, prim_class;
+  DevBuf fourier;  // the words of the scene's Fourier BSDF tables (images with n_levels == 0), one after the other
+  std::vector<int> mat_kind, mat_table;  // per material: its kind and, for RT_MAT_FOURIER, its table's image (rt_fourier_eval)
+  std::vector<uint64_t> fourier_at;      // per image: the first word of its Fourier table in `fourier`, or ~0 (a MIP pyramid)
   bool has_spheres = false;
   bool has_instances = false;  // object instances: two-level traversal in k_trace_big<.., GENERAL>, every vertex shaded by k_shade<0, true>
   DevBuf instances;
@@ -210,8 +213,60 @@ static bool shadow_sets_apply(const rt_scene_desc* desc, bool plain) {
   return true;
 }
 
+// Fourier BSDF tables (an rt_image with n_levels == 0, rtx_hip.h): what is wrong with one, or "" - then `words` is its length. Everything the device lobe
+// (fourier_f / fourier_pdf / fourier_sample_f in rtx_dev_bsdf.h) indexes is checked here, so that no table can make it read outside its words.
+#define RT_FOURIER_MAX_WORDS (1ull << 28)
+static std::string fourier_table_error(const rt_image& im, uint64_t& words) {
+  if (!im.texels) return "Fourier BSDF table without words";
+  if (im.n_texels > RT_FOURIER_MAX_WORDS) return "Fourier BSDF table larger than 2^28 words";
+  const uint64_t cap = 3 * im.n_texels;
+  if (cap < 5) return "Fourier BSDF table shorter than its header";
+  const uint32_t* w = (const uint32_t*)im.texels;
+  const uint64_t n_mu = w[0], m_max = w[1], n_ch = w[2], n_coeffs = w[3];
+  float eta; memcpy(&eta, &w[4], 4);
+  if (n_mu < 2 || n_mu > 8192) return "Fourier BSDF table: nMu must lie in [2, 8192]";
+  if (n_ch != 1 && n_ch != 3) return "Fourier BSDF table: nChannels must be 1 or 3";
+  if (n_coeffs > RT_FOURIER_MAX_WORDS) return "Fourier BSDF table: nCoeffs larger than 2^28";
+  if (!std::isfinite(eta)) return "Fourier BSDF table: eta is not finite";
+  words = 5 + n_mu + 3 * n_mu * n_mu + n_coeffs;
+  if ((words + 2) / 3 != im.n_texels) return "Fourier BSDF table: sizes do not add up (" + std::to_string(words) + " words for " + std::to_string(im.n_texels) + " texels)";
+  const float* mu = (const float*)(w + 5);
+  for (uint64_t i = 0; i < n_mu; ++i) if (!std::isfinite(mu[i]) || (i > 0 && !(mu[i - 1] < mu[i]))) return "Fourier BSDF table: mu is not strictly ascending";
+  const uint32_t* ol = w + 5 + n_mu + n_mu * n_mu;
+  for (uint64_t c = 0; c < n_mu * n_mu; ++c) {
+    const uint64_t off = ol[2 * c], len = ol[2 * c + 1];
+    if (len > m_max) return "Fourier BSDF table: a cell's length exceeds mMax";
+    if (off + len * n_ch > n_coeffs) return "Fourier BSDF table: a cell's coefficients run past nCoeffs";
+  }
+  return "";
+}
+// The Fourier half of a scene description's checks, made before any device is touched: the tables, and every reference to an image that is one
+static std::string fourier_desc_error(const rt_scene_desc* desc) {
+  auto is_table = [&](int id) { return id >= 0 && (uint32_t)id < desc->n_images && desc->images && desc->images[id].n_levels == 0; };
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < desc->n_images; ++i) {
+    if (!desc->images || desc->images[i].n_levels != 0) continue;
+    uint64_t words = 0;
+    const std::string why = fourier_table_error(desc->images[i], words);
+    if (!why.empty()) return "image " + std::to_string(i) + ": " + why;
+    total += words;
+    if (total > RT_FOURIER_MAX_WORDS) return "Fourier BSDF tables larger than 2^28 words in all";
+  }
+  for (uint32_t i = 0; i < desc->n_materials && desc->materials; ++i) {
+    const rt_material& m = desc->materials[i];
+    if (m.kind == RT_MAT_FOURIER && !is_table(m.slot[RT_SLOT_M1]))
+      return "material " + std::to_string(i) + ": a Fourier material must name a Fourier BSDF table (n_levels == 0) in slot M1, not a MIP pyramid";
+  }
+  for (uint32_t i = 0; i < desc->n_textures && desc->textures; ++i)
+    if (desc->textures[i].kind == RT_TEX_IMAGE && is_table(desc->textures[i].image)) return "texture " + std::to_string(i) + ": an image texture names a Fourier BSDF table, not a MIP pyramid";
+  for (uint32_t i = 0; i < desc->n_lights && desc->lights; ++i)
+    if (desc->lights[i].kind == RT_LIGHT_INFINITE && is_table(desc->lights[i].image)) return "light " + std::to_string(i) + ": an infinite light names a Fourier BSDF table, not a MIP pyramid";
+  return "";
+}
+
 extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
   if (!desc || !out) return fail(RT_ERR_INVALID, "null argument");
+  { const std::string why = fourier_desc_error(desc); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   if (!rt_device_available()) return fail(RT_ERR_NO_DEVICE, "no HIP device visible; this backend has no CPU fallback");
   if (desc->n_nodes == 0 || desc->n_tris == 0 || !desc->nodes || !desc->tri_p || !desc->tri_meta) return fail(RT_ERR_INVALID, "empty scene");
   if (device >= 0) HIP_TRY(hipSetDevice(device));
@@ -294,12 +349,19 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
   // images: one blob of float4 texels, every level cut into tiles of 4 x 2 texels = one 128-byte line (mip_texel in rtx_dev_shading.h): a bilinear
   // or EWA footprint then touches fewer lines than with 12-byte row-major texels, and a texel is one aligned 16-byte load. The layout changes no value.
   std::vector<DImage> himg(desc->n_images);
+  std::vector<uint64_t> fourier_at(desc->n_images, ~0ull);  // first word of an image's Fourier table in s->fourier, or ~0: a MIP pyramid
   {
     auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
     size_t total = 0;  // in float4 texels, levels padded to whole tiles
+    uint64_t fourier_words = 0;
     for (uint32_t i = 0; i < desc->n_images; ++i) {
       const rt_image& im = desc->images[i];
-      if (im.n_levels <= 0 || im.n_levels > RT_MAX_MIP_LEVELS) { delete s; return fail(RT_ERR_INVALID, "bad mip level count"); }
+      if (im.n_levels == 0) {  // a Fourier BSDF table (rtx_hip.h)
+        uint64_t words = 0; (void)fourier_table_error(im, words);  // (checked by fourier_desc_error)
+        fourier_at[i] = fourier_words; fourier_words += words;
+        continue;
+      }
+      if (im.n_levels < 0 || im.n_levels > RT_MAX_MIP_LEVELS) { delete s; return fail(RT_ERR_INVALID, "bad mip level count"); }
       for (int l = 0; l < im.n_levels; ++l) {
         // MIPMap::new resamples to powers of two and halves from there (rc/mipmap.rs:75-139), which is what lets Repeat wrap by a mask
         if (!is_pow2(im.width[l]) || !is_pow2(im.height[l])) { delete s; return fail(RT_ERR_INVALID, "MIP level sizes must be powers of two (rc/mipmap.rs:75-139)"); }
@@ -308,12 +370,20 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
       }
     }
     std::vector<float> blob((total + 1) * 4, 0.0f);
+    std::vector<uint32_t> fblob((size_t)fourier_words + 1, 0u);
     size_t base = 0;
     for (uint32_t i = 0; i < desc->n_images; ++i) {
       const rt_image& im = desc->images[i];
       DImage& d = himg[i];
       d.n_levels = im.n_levels; d.trilinear = im.trilinear; d.max_aniso = im.max_anisotropy; d.wrap = im.wrap;
       for (int l = 0; l < 16; ++l) { d.w[l] = 0; d.h[l] = 0; d.off[l] = 0; d.tshift[l] = 0; }
+      if (im.n_levels == 0) {  // table words as they are; material_lobes finds them at fourier + off[0]
+        const uint32_t* w = (const uint32_t*)im.texels;
+        uint64_t words = 0; (void)fourier_table_error(im, words);
+        memcpy(&fblob[(size_t)fourier_at[i]], w, (size_t)words * 4);
+        d.off[0] = fourier_at[i];
+        continue;
+      }
       for (int l = 0; l < im.n_levels; ++l) {
         const int w = im.width[l], h = im.height[l], pw = std::max(w, 4), ph = std::max(h, 2);
         int ts = 0; while ((4 << ts) < pw) ++ts;  // tiles per row = 2^ts
@@ -329,6 +399,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
       }
     }
     TRY_RC(upload(s->texels, blob.data(), blob.size() * 4));
+    TRY_RC(upload(s->fourier, fblob.data(), fblob.size() * 4));
+    s->fourier_at = fourier_at;
     for (auto& d : himg) d.texels = s->texels.as<float4>();
     TRY_RC(upload(s->images, himg.data(), himg.size() * sizeof(DImage)));
   }
@@ -361,8 +433,11 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
   }
   TRY_RC(upload(s->textures, htex.data(), htex.size() * sizeof(DTexture)));
   std::vector<DMaterial> hmat(desc->n_materials);
+  s->mat_kind.assign(desc->n_materials, 0); s->mat_table.assign(desc->n_materials, -1);
   for (uint32_t i = 0; i < desc->n_materials; ++i) {
     const rt_material& m = desc->materials[i];
+    s->mat_kind[i] = m.kind;
+    if (m.kind == RT_MAT_FOURIER) s->mat_table[i] = m.slot[RT_SLOT_M1];  // the table's image (fourier_desc_error checked it); no texture slot is read
     hmat[i].kind = m.kind; hmat[i].remap = m.remap_roughness;
     hmat[i].bump = (m.kind != RT_MAT_MIX && m.bump >= 0) ? m.bump : -1;
     if (hmat[i].bump >= 0 && (uint32_t)hmat[i].bump >= desc->n_textures) { delete s; return fail(RT_ERR_INVALID, "bump texture out of range"); }
@@ -543,6 +618,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
   d.spheres = s->has_spheres ? s->spheres.as<DSphere>() : nullptr;
   d.instances = s->has_instances ? s->instances.as<DInstance>() : nullptr; d.n_instances = s->has_instances ? desc->n_instances : 0u; d.n_top_prims = n_top_prims;
   d.textures = s->textures.as<DTexture>(); d.images = s->images.as<DImage>(); d.materials = s->materials.as<DMaterial>(); d.lights = s->lights.as<DLight>();
+  d.fourier = s->fourier.as<unsigned>();
   d.n_materials = (int)desc->n_materials; d.n_textures = (int)desc->n_textures; d.n_images = (int)desc->n_images;
   d.n_lights = (int)desc->n_lights;
   d.wb_min = f3{desc->nodes[0].bmin[0], desc->nodes[0].bmin[1], desc->nodes[0].bmin[2]};
@@ -834,6 +910,36 @@ extern "C" int rt_offset_ray_origin(const float* p, const float* p_error, const 
   hipLaunchKernelGGL(k_offset_ray_origin, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(), b[3].as<float>(), (unsigned long long)count, b[4].as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, b[4].p, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+// rt_fourier_eval: the FourierBSDF lobe functions of the shade kernel (lobe_f_inner / lobe_pdf_inner / lobe_sample_inner of rtx_dev_bsdf.h) on query directions
+__global__ void k_fourier_eval(const unsigned* __restrict__ tab, const float* __restrict__ wo, const float* __restrict__ wi, const float* __restrict__ u, unsigned long long n,
+                               float* __restrict__ out) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Lobe l = lobe_zero(LB_FOURIER); lobe_set_table(l, tab);
+  const f3 o = mk3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), w = mk3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+  const rgb3 f = lobe_f_inner(l, o, w);
+  const float pdf = lobe_pdf_inner(l, o, w);
+  const LobeSample s = lobe_sample_inner<true>(l, o, mk2(u[2 * i], u[2 * i + 1]));
+  float* r = out + 11 * i;
+  r[0] = f.r; r[1] = f.g; r[2] = f.b; r[3] = pdf;
+  r[4] = s.f.r; r[5] = s.f.g; r[6] = s.f.b; r[7] = s.wi.x; r[8] = s.wi.y; r[9] = s.wi.z; r[10] = s.pdf;
+}
+extern "C" int rt_fourier_eval(rt_scene* scene, int32_t material, uint64_t n, const float* wo, const float* wi, const float* u, float* out) {
+  if (!scene || !wo || !wi || !u || !out || n == 0) return fail(RT_ERR_INVALID, "bad rt_fourier_eval arguments");
+  if (material < 0 || (size_t)material >= scene->mat_kind.size() || scene->mat_kind[material] != RT_MAT_FOURIER) return fail(RT_ERR_INVALID, "rt_fourier_eval: not a Fourier material");
+  HIP_TRY(hipSetDevice(scene->device));
+  const unsigned* tab = scene->fourier.as<unsigned>() + scene->fourier_at[scene->mat_table[material]];
+  DevBuf b[4];
+  const size_t n3 = (size_t)n * 12, n2 = (size_t)n * 8, n11 = (size_t)n * 44;
+  HIP_TRY(b[0].ensure(n3)); HIP_TRY(b[1].ensure(n3)); HIP_TRY(b[2].ensure(n2)); HIP_TRY(b[3].ensure(n11));
+  HIP_TRY(hipMemcpy(b[0].p, wo, n3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b[1].p, wi, n3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b[2].p, u, n2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_fourier_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, tab, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(), (unsigned long long)n, b[3].as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, b[3].p, n11, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 extern "C" int rt_link_tables(const rt_scene_desc* desc, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats) {
@@ -1827,6 +1933,7 @@ struct rt_multi {
 };
 extern "C" int rt_multi_create(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices, rt_multi** out) {
   if (!desc || !devices || n_devices < 1 || !out) return fail(RT_ERR_INVALID, "bad rt_multi_create arguments");
+  { const std::string why = fourier_desc_error(desc); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   int n_visible = 0;
   if (hipGetDeviceCount(&n_visible) != hipSuccess || n_visible <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible; this backend has no CPU fallback");
   rt_multi* m = new rt_multi();

@@ -145,6 +145,7 @@ float filter_eval(int kind, const float prm[4], float x, float y) {
 struct MipLevels {
   int trilinear, wrap; float max_aniso;
   std::vector<int> w, h; std::vector<uint64_t> off; std::vector<float> texels;  // RGB
+  bool fourier = false;  // a Fourier BSDF table (rtxh_scene_add_fourier_table): no levels; `texels` holds its packed words (rtx_hip.h, rt_image)
 };
 long modl(long a, long b) { long r = a % b; return r < 0 ? r + b : r; }
 // MIPMap::texel (mipmap.rs:208-225) on a finished level
@@ -224,6 +225,7 @@ struct rtxh_scene {
   size_t n_listed_lights = 0;        // f_lights: the scene's lights first, then `emitters`
   size_t n_prims() const { return n_tris() + spheres.size() + instances.size(); }
   std::vector<rt_texture> textures; std::vector<rt_material> materials; std::vector<MipLevels> mips; std::vector<HostLight> lights;
+  std::map<std::string, int> fourier_files;  // .bsdf path -> its image in `mips`: a table several materials use is read once
   // BVH products
   std::vector<rt_bvh_node> nodes; std::vector<int32_t> ordered;
   // flattened arrays (leaf order)
@@ -627,6 +629,7 @@ int finish_commit(rtxh_scene* s) {
   s->f_images.clear();
   for (const MipLevels& m : s->mips) {
     rt_image im{};
+    if (m.fourier) { im.texels = m.texels.data(); im.n_texels = m.texels.size() / 3; s->f_images.push_back(im); continue; }  // n_levels 0: a table
     im.n_levels = (int32_t)m.w.size();
     for (int l = 0; l < im.n_levels; ++l) { im.width[l] = m.w[l]; im.height[l] = m.h[l]; im.offset[l] = m.off[l]; }
     im.texels = m.texels.data(); im.n_texels = m.texels.size() / 3; im.trilinear = m.trilinear; im.max_anisotropy = m.max_aniso; im.wrap = m.wrap;
@@ -980,6 +983,51 @@ int rtxh_scene_add_mipmap(rtxh_scene* s, int32_t w, int32_t h, const float* rgb_
   return (int)s->mips.size() - 1;
 }
 
+// FourierBSDFTable::read (rc/bsdf/fourier.rs:294-371), little-endian: the 8-byte magic "SCATFUN\x01", nine u32 (flags nMu nCoeffs mMax nChannels nBases
+// nMetadataBytes nParameters nParameterValues) and five f32 (eta alpha[2] unused[2]), then mu[nMu], cdf[nMu^2], offset_and_length[2 nMu^2], a[nCoeffs]; metadata
+// and parameter blocks are not read. The reference's refusals (magic; flags != 1, nChannels not 1 or 3, nBases != 1) plus a truncated file, nMu < 2, mu not
+// ascending, a cell longer than mMax or past nCoeffs, and tables beyond the budget (nMu <= 8192, 2^28 words) - every message names the file.
+int rtxh_scene_add_fourier_table(rtxh_scene* s, const char* path) {
+  if (!s || !path) return fail(RT_ERR_INVALID, "bad rtxh_scene_add_fourier_table arguments");
+  const std::string name = path;
+  if (name.empty()) return fail(RT_ERR_INVALID, "Material \"fourier\": \"bsdffile\" is empty");
+  auto hit = s->fourier_files.find(name);
+  if (hit != s->fourier_files.end()) return hit->second;
+  const std::string q = "BSDF file \"" + name + "\"";
+  FILE* f = fopen(path, "rb");
+  if (!f) return fail(RT_ERR_INVALID, q + " cannot be opened");
+  std::vector<unsigned char> bytes;
+  { unsigned char buf[65536]; size_t n; while ((n = fread(buf, 1, sizeof buf, f)) > 0) { bytes.insert(bytes.end(), buf, buf + n); if (bytes.size() > (5ull << 30)) break; } }
+  fclose(f);
+  if (bytes.size() < 8) return fail(RT_ERR_INVALID, q + " is truncated (no header)");
+  if (memcmp(bytes.data(), "SCATFUN\x01", 8) != 0) return fail(RT_ERR_INVALID, q + " has an invalid header");
+  if (bytes.size() < 64) return fail(RT_ERR_INVALID, q + " is truncated (header)");
+  uint32_t hd[9]; float eta; memcpy(hd, &bytes[8], 36); memcpy(&eta, &bytes[44], 4);
+  const uint32_t flags = hd[0], n_mu = hd[1], n_coeffs = hd[2], m_max = hd[3], n_ch = hd[4], n_bases = hd[5];
+  if (flags != 1 || (n_ch != 1 && n_ch != 3) || n_bases != 1) return fail(RT_ERR_INVALID, "Unsupported " + q + " (flags " + std::to_string(flags) + ", nChannels " + std::to_string(n_ch) + ", nBases " + std::to_string(n_bases) + ")");
+  if (n_mu < 2 || n_mu > 8192) return fail(RT_ERR_INVALID, q + ": nMu = " + std::to_string(n_mu) + " is outside [2, 8192]");
+  const uint64_t nn = (uint64_t)n_mu * n_mu, payload = (uint64_t)n_mu + 3 * nn + n_coeffs;  // words after the header
+  if (5 + payload > (1ull << 28)) return fail(RT_ERR_INVALID, q + " is larger than the 2^28-word budget of a table");
+  if ((uint64_t)bytes.size() < 64 + 4 * payload) return fail(RT_ERR_INVALID, q + " is truncated (" + std::to_string(bytes.size()) + " bytes, the header promises " + std::to_string(64 + 4 * payload) + ")");
+  std::vector<uint32_t> w((size_t)(5 + payload + 2) / 3 * 3, 0u);
+  w[0] = n_mu; w[1] = m_max; w[2] = n_ch; w[3] = n_coeffs; memcpy(&w[4], &eta, 4);
+  memcpy(&w[5], &bytes[64], (size_t)payload * 4);
+  const float* mu = (const float*)&w[5];
+  for (uint32_t i = 0; i < n_mu; ++i) if (!std::isfinite(mu[i]) || (i > 0 && !(mu[i - 1] < mu[i]))) return fail(RT_ERR_INVALID, q + ": mu is not strictly ascending");
+  const uint32_t* ol = &w[5 + n_mu + nn];
+  for (uint64_t c = 0; c < nn; ++c) {
+    if (ol[2 * c + 1] > m_max) return fail(RT_ERR_INVALID, q + ": a cell holds more than mMax coefficients");
+    if ((uint64_t)ol[2 * c] + (uint64_t)ol[2 * c + 1] * n_ch > n_coeffs) return fail(RT_ERR_INVALID, q + ": a cell's offset and length run past nCoeffs");
+  }
+  MipLevels m; m.trilinear = 0; m.wrap = 0; m.max_aniso = 0.0f; m.fourier = true;
+  m.texels.resize(w.size()); memcpy(m.texels.data(), w.data(), w.size() * 4);
+  s->mips.push_back(std::move(m));
+  s->committed = false;
+  const int id = (int)s->mips.size() - 1;
+  s->fourier_files[name] = id;
+  return id;
+}
+
 int rtxh_scene_add_texture(rtxh_scene* s, int32_t kind, const float* v, int32_t tex1, int32_t tex2, int32_t amount, int32_t mip, const float* mapping) {
   if (!s || !v) return fail(RT_ERR_INVALID, "bad texture arguments");
   rt_texture t{}; t.kind = kind; t.value[0] = v[0]; t.value[1] = v[1]; t.value[2] = v[2]; t.tex1 = tex1; t.tex2 = tex2; t.amount = amount; t.image = mip;
@@ -1006,7 +1054,7 @@ int rtxh_scene_add_light(rtxh_scene* s, int32_t kind, int32_t tri, const float* 
   }
   for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { l.l2w[4 * r + c] = l2w ? l2w[4 * r + c] : (r == c ? 1.0f : 0.0f); l.w2l[4 * r + c] = w2l ? w2l[4 * r + c] : (r == c ? 1.0f : 0.0f); }
   if (kind == RT_LIGHT_INFINITE) {
-    if (mip < 0 || (size_t)mip >= s->mips.size()) return fail(RT_ERR_INVALID, "infinite light needs an environment map");
+    if (mip < 0 || (size_t)mip >= s->mips.size() || s->mips[mip].fourier) return fail(RT_ERR_INVALID, "infinite light needs an environment map");
     // InfiniteAreaLight::new (infinite.rs:78-101): luminance * sin(theta) at twice the map resolution
     const MipLevels& m = s->mips[mip];
     const int width = 2 * m.w[0], height = 2 * m.h[0];
@@ -1247,6 +1295,13 @@ int rtxh_scene_query(rtxh_scene* s, int32_t what) {
   g_err.clear();
   if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_scene_query(s->dev, what);
+}
+int rtxh_scene_device(rtxh_scene* s, rt_scene** out) {
+  if (!s || !out) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  *out = s->dev;
+  return RT_OK;
 }
 int rtxh_scene_link_tables(rtxh_scene* s, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats) {
   if (!s || !s->committed) return fail(RT_ERR_INVALID, "scene not committed");

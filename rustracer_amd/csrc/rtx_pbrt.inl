@@ -314,8 +314,14 @@ struct PbrtLoader {
         if (it != gs.named_materials.end()) slots[RT_SLOT_M1 + k] = it->second;
         else { warn("named material undefined, using matte"); slots[RT_SLOT_M1 + k] = make_material("matte", gp, mp); }
       }
+    } else if (name == "fourier") {  // FourierMaterial::create (rc/material/fourier.rs:18-28); a missing or unreadable table is an error (the reference panics)
+      kind = RT_MAT_FOURIER;
+      const std::string file = tp_string(gp, mp, "bsdffile", "");
+      if (file.empty()) { fail_("Material \"fourier\": \"bsdffile\" is missing or empty"); return -1; }
+      const int table = rtxh_scene_add_fourier_table(scene, resolve(file).c_str());
+      if (table < 0) { fail_(rtxh_last_error()); return -1; }
+      slots[RT_SLOT_M1] = table;
     } else {
-      if (name == "fourier") { fail_("material \"fourier\" is not supported"); return -1; }
       if (name != "matte") warn("unknown material, using matte");
       kind = RT_MAT_MATTE; S(RT_SLOT_KD, "Kd", .5f, .5f, .5f); F(RT_SLOT_SIGMA, "sigma", 0.0f);
     }

@@ -200,6 +200,9 @@ class HostScene:
             self._keep += (alpha,)
             _check(L.rtxh_scene_set_alpha(self.h, _p(alpha, C.c_int32)), "set_alpha")
         for m in desc.mipmaps:
+            if getattr(m, "path", None) is not None:  # scene_desc.FourierTable: the C++ reader loads the .bsdf file
+                _check(L.rtxh_scene_add_fourier_table(self.h, os.fsencode(m.path)), "add_fourier_table")
+                continue
             h, w = m.data.shape[:2]
             _check(L.rtxh_scene_add_mipmap(self.h, w, h, _p(m.data), int(m.trilinear), C.c_float(m.max_aniso), m.wrap), "add_mipmap")
         for t in desc.textures:
@@ -370,6 +373,22 @@ class HostScene:
         film = np.zeros((h, w, 4), np.float32)
         _check(lib().rtxh_render_multi(self.h, C.byref(p), _p(dev, C.c_int32), len(dev), int(chunks_per_device), _p(film), C.byref(total), per), "render_multi")
         return film, total.as_dict(), [s.as_dict() for s in per]
+
+    def fourier_eval(self, material, wo, wi, u):
+        """FourierBSDF f / pdf / sample_f of Material "fourier" `material` through the shade kernel's device lobe functions (rt_fourier_eval; shading frame,
+        radiance mode). wo, wi: (n, 3), u: (n, 2). Returns dict(f=(n, 3), pdf=(n,), sf=(n, 3), swi=(n, 3), spdf=(n,)). Uploads the scene first if need be."""
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = wo.shape[0]
+        assert wi.shape[0] == n and u.shape[0] == n
+        dev = C.c_void_p()
+        _check(lib().rtxh_scene_device(self.h, C.byref(dev)), "scene_device")
+        out = np.zeros((n, 11), np.float32)
+        rc = hip_lib().rt_fourier_eval(dev, C.c_int32(material), C.c_uint64(n), _p(wo), _p(wi), _p(u), _p(out))
+        if rc != 0:
+            raise BackendError(f"rt_fourier_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+        return dict(f=out[:, 0:3], pdf=out[:, 3], sf=out[:, 4:7], swi=out[:, 7:10], spdf=out[:, 10])
 
     def trace(self, rays, any_hit=False, count=True):
         """count=True: the visit-counting kernels (one node per step, the reference's sequence); count=False: the

@@ -19,7 +19,7 @@ from .ingest import write_pfm
 _FILTER_NAMES = {sd.FILTER_BOX: "box", sd.FILTER_TRIANGLE: "triangle", sd.FILTER_GAUSSIAN: "gaussian", sd.FILTER_MITCHELL: "mitchell"}
 _WRAP_NAMES = {sd.WRAP_REPEAT: "repeat", sd.WRAP_BLACK: "black", sd.WRAP_CLAMP: "clamp"}
 _MAT_NAMES = {sd.MAT_MATTE: "matte", sd.MAT_PLASTIC: "plastic", sd.MAT_METAL: "metal", sd.MAT_MIRROR: "mirror", sd.MAT_GLASS: "glass", sd.MAT_UBER: "uber",
-              sd.MAT_SUBSTRATE: "substrate", sd.MAT_MIX: "mix", sd.MAT_TRANSLUCENT: "translucent", sd.MAT_DISNEY: "disney"}
+              sd.MAT_SUBSTRATE: "substrate", sd.MAT_MIX: "mix", sd.MAT_TRANSLUCENT: "translucent", sd.MAT_DISNEY: "disney", sd.MAT_FOURIER: "fourier"}
 # material kind -> {slot: (pbrt parameter, "spectrum" | "float")}   (the create() of each rc/material/*.rs)
 _S, _F = "spectrum", "float"
 _SLOTS = {
@@ -36,6 +36,7 @@ _SLOTS = {
                     "urough": ("anisotropic", _F), "kt": ("sheen", _F), "sigma": ("sheentint", _F), "vrough": ("clearcoat", _F), "k": ("clearcoatgloss", _F),
                     "opacity": ("spectrans", _F), "reflect": ("scatterdistance", _S), "transmit": ("flatness", _F), "amount": ("difftrans", _F)},
     sd.MAT_MIX: {"amount": ("amount", _S)},
+    sd.MAT_FOURIER: {},
 }
 
 
@@ -127,6 +128,9 @@ class _Writer:
         else:
             if m.kind == sd.MAT_DISNEY:
                 parts.append(f'"bool thin" "{"true" if m.params.get("m1", 0) else "false"}"')
+            elif m.kind == sd.MAT_FOURIER:  # the table's file, by absolute path (FourierMaterial::create's find_filename leaves those as they are)
+                parts.append(f'"string bsdffile" "{self.d.mipmaps[m.params["m1"]].path}"')
+                parts.append(f'"bool remaproughness" "{"true" if m.remap_roughness else "false"}"')
             else:
                 parts.append(f'"bool remaproughness" "{"true" if m.remap_roughness else "false"}"')
             if m.bump >= 0:

@@ -18,7 +18,7 @@ import numpy as np
 # --- enums shared (by value) with include/rtx_hip.h and oracle/ -------------------------------
 TEX_CONST, TEX_SCALE, TEX_MIX, TEX_IMAGE, TEX_CHECKER, TEX_UV, TEX_FBM = 0, 1, 2, 3, 4, 5, 6
 (MAT_MATTE, MAT_PLASTIC, MAT_METAL, MAT_MIRROR, MAT_GLASS, MAT_UBER, MAT_SUBSTRATE, MAT_MIX,
- MAT_TRANSLUCENT, MAT_DISNEY) = range(10)
+ MAT_TRANSLUCENT, MAT_DISNEY, MAT_FOURIER) = range(11)
 LIGHT_DIFFUSE_AREA, LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2, 3
 FILTER_BOX, FILTER_TRIANGLE, FILTER_GAUSSIAN, FILTER_MITCHELL = 0, 1, 2, 3
 WRAP_REPEAT, WRAP_BLACK, WRAP_CLAMP = 0, 1, 2
@@ -53,6 +53,13 @@ class MipImage:
     trilinear: bool = False
     max_aniso: float = 8.0
     wrap: int = WRAP_REPEAT
+
+
+@dataclass
+class FourierTable:
+    """A tabulated Fourier BSDF (.bsdf file, rc/bsdf/fourier.rs): an entry of SceneDesc.mipmaps that is no MIP pyramid. The backend's host layer reads the
+    file (rtxh_scene_add_fourier_table); a Material "fourier" names the entry in its "m1" slot."""
+    path: str
 
 
 @dataclass
@@ -289,6 +296,20 @@ class SceneDesc:
         assert self.materials[material].kind != MAT_MIX
         self.materials[material].bump = self._t(_f(tex))
         return material
+
+    def fourier(self, bsdffile) -> int:  # FourierMaterial::create (rc/material/fourier.rs:18-28); bump maps: set_bump
+        """Material "fourier" over the .bsdf table at `bsdffile`; a file several materials use is one table."""
+        import os
+        path = os.path.abspath(str(bsdffile))
+        table = next((i for i, m in enumerate(self.mipmaps) if isinstance(m, FourierTable) and m.path == path), None)
+        if table is None:
+            self.mipmaps.append(FourierTable(path))
+            table = len(self.mipmaps) - 1
+        self.materials.append(Material(MAT_FOURIER, {"m1": table}))
+        return len(self.materials) - 1
+
+    def has_fourier(self) -> bool:
+        return any(m.kind == MAT_FOURIER for m in self.materials)
 
     def mix(self, m1: int, m2: int, amount=0.5) -> int:  # mixmat.rs:22-30
         self.materials.append(Material(MAT_MIX, {"m1": int(m1), "m2": int(m2), "amount": self._t(_f(amount))}))

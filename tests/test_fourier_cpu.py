@@ -1,0 +1,266 @@
+"""Material "fourier" without a GPU: the .bsdf reader of the C++ host, the checks rt_scene_create makes on a table before it touches a device, the .pbrt
+loader (bsdffile, NamedMaterial, mix, bumpmap) and the exporter's round trip."""
+import ctypes as C
+import os
+import struct
+
+import numpy as np
+import pytest
+
+from rustracer_amd import host
+from rustracer_amd import scene_desc as sd
+from rustracer_amd.pbrt_export import write_pbrt
+from rustracer_amd.scenes import cornell_box
+
+import fourier_ref as fr
+
+RT_ERR_INVALID, RT_ERR_NO_DEVICE = -1, -2
+
+
+def _table(tmp_path, name="t.bsdf", **kw):
+    return fr.write_table(str(tmp_path / name), fr.glossy_table(**kw))
+
+
+def _add(path):
+    L = host.lib()
+    h = C.c_void_p(L.rtxh_scene_new())
+    try:
+        rc = L.rtxh_scene_add_fourier_table(h, os.fsencode(str(path)))
+        return rc, (L.rtxh_last_error() or b"").decode()
+    finally:
+        L.rtxh_scene_free(h)
+
+
+# ---------------------------------------------------------------- the reader
+@pytest.mark.parametrize("kw", [dict(n_channels=1), dict(n_channels=3, eta=1.33), dict(n_channels=1, empty_cells=True, varying=True)])
+def test_reader_accepts_what_the_writer_writes(tmp_path, kw):
+    path = _table(tmp_path, **kw)
+    rc, err = _add(path)
+    assert rc == 0, err
+    t = fr.read_bsdf(path)
+    assert t.n_channels == kw["n_channels"] and np.all(np.diff(t.mu) > 0)
+
+
+def test_a_table_two_materials_use_is_read_once(tmp_path):
+    path = _table(tmp_path)
+    d = cornell_box(16, 16, 1)
+    a, b = d.fourier(path), d.fourier(path)
+    assert d.materials[a].params["m1"] == d.materials[b].params["m1"] == len(d.mipmaps) - 1
+    L = host.lib()
+    h = C.c_void_p(L.rtxh_scene_new())
+    try:
+        assert L.rtxh_scene_add_fourier_table(h, os.fsencode(path)) == L.rtxh_scene_add_fourier_table(h, os.fsencode(path)) == 0
+    finally:
+        L.rtxh_scene_free(h)
+
+
+def _corrupt(tmp_path, name, fn):
+    raw = bytearray(open(_table(tmp_path, n_channels=3), "rb").read())
+    p = tmp_path / name
+    p.write_bytes(bytes(fn(raw)))
+    return p
+
+
+def _set_u32(raw, word, v):
+    struct.pack_into("<I", raw, 8 + 4 * word, v)
+    return raw
+
+
+@pytest.mark.parametrize("name, fn, what", [
+    ("magic.bsdf", lambda r: b"SCATFUN\x02" + r[8:], "invalid header"),
+    ("flags.bsdf", lambda r: _set_u32(r, 0, 3), "Unsupported"),
+    ("channels.bsdf", lambda r: _set_u32(r, 4, 2), "Unsupported"),
+    ("bases.bsdf", lambda r: _set_u32(r, 5, 2), "Unsupported"),
+    ("cut4.bsdf", lambda r: r[:4], "truncated"),
+    ("cut40.bsdf", lambda r: r[:40], "truncated"),
+    ("cut100.bsdf", lambda r: r[:100], "truncated"),
+    ("cut_end.bsdf", lambda r: r[:-1], "truncated"),
+])
+def test_reader_refuses_bad_files_and_names_them(tmp_path, name, fn, what):
+    p = _corrupt(tmp_path, name, fn)
+    rc, err = _add(p)
+    assert rc < 0 and what in err and name in err, (rc, err)
+
+
+def test_reader_refuses_an_offset_past_ncoeffs(tmp_path):
+    t = fr.glossy_table()
+    t.offset = t.offset.copy()
+    t.offset[-1] = t.a.size  # a non-empty cell whose coefficients start at the end
+    assert t.length[-1] > 0
+    p = fr.write_table(str(tmp_path / "offset.bsdf"), t)
+    rc, err = _add(p)
+    assert rc < 0 and "nCoeffs" in err and "offset.bsdf" in err, (rc, err)
+
+
+def test_reader_refuses_a_missing_or_empty_name(tmp_path):
+    rc, err = _add(tmp_path / "nope.bsdf")
+    assert rc < 0 and "nope.bsdf" in err
+    rc, err = _add("")
+    assert rc < 0 and "bsdffile" in err
+
+
+# ---------------------------------------------------------------- rt_scene_create's checks (made before any device is touched)
+class RtImage(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("width", C.c_int32 * 16), ("height", C.c_int32 * 16), ("offset", C.c_uint64 * 16), ("texels", C.c_void_p),
+                ("n_texels", C.c_uint64), ("trilinear", C.c_int32), ("max_anisotropy", C.c_float), ("wrap", C.c_int32)]
+
+
+class RtMaterial(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("slot", C.c_int32 * 16), ("remap_roughness", C.c_int32), ("bump", C.c_int32)]
+
+
+class RtTexture(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("value", C.c_float * 3), ("tex1", C.c_int32), ("tex2", C.c_int32), ("amount", C.c_int32), ("image", C.c_int32),
+                ("mapping", C.c_float * 4)]
+
+
+class RtSceneDesc(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_tris", C.c_uint32), ("tri_p", C.c_void_p), ("tri_n", C.c_void_p), ("tri_uv", C.c_void_p),
+                ("tri_s", C.c_void_p), ("tri_meta", C.c_void_p), ("tri_alpha", C.c_void_p), ("n_spheres", C.c_uint32), ("spheres", C.c_void_p),
+                ("n_textures", C.c_uint32), ("textures", C.c_void_p), ("n_images", C.c_uint32), ("images", C.c_void_p), ("n_materials", C.c_uint32),
+                ("materials", C.c_void_p), ("n_lights", C.c_uint32), ("lights", C.c_void_p), ("n_instances", C.c_uint32), ("instances", C.c_void_p),
+                ("n_top_nodes", C.c_uint32), ("n_top_prims", C.c_uint32), ("n_unlisted_lights", C.c_uint32)]
+
+
+def test_mirrors_have_the_header_sizes():
+    for cls, name in ((RtImage, b"rt_image"), (RtMaterial, b"rt_material"), (RtTexture, b"rt_texture"), (RtSceneDesc, b"rt_scene_desc")):
+        assert host.hip_lib().rt_sizeof(name) == C.sizeof(cls), name
+
+
+def _words(t):
+    n = t.n_mu
+    ol = np.stack([t.offset, t.length], 1).astype(np.uint32).ravel()
+    w = np.concatenate([np.uint32([n, t.m_max, t.n_channels, t.a.size]), np.float32([t.eta]).view(np.uint32), t.mu.view(np.uint32),
+                        t.cdf.view(np.uint32), ol, t.a.view(np.uint32)])
+    return np.concatenate([w, np.zeros((-w.size) % 3, np.uint32)])
+
+
+def _create(words, mat_kind=sd.MAT_FOURIER, mat_slot=0, tex_image=None, extra_pyramid=False):
+    """rt_scene_create over one table image (and a 1x1 pyramid), one material and maybe an image texture; the rest of the description is empty."""
+    keep = [words]
+    imgs = (RtImage * 2)()
+    imgs[0].n_levels = 0; imgs[0].texels = words.ctypes.data; imgs[0].n_texels = words.size // 3
+    px = np.zeros(3, np.float32); keep.append(px)
+    imgs[1].n_levels = 1; imgs[1].width[0] = imgs[1].height[0] = 1; imgs[1].texels = px.ctypes.data; imgs[1].n_texels = 1
+    mats = (RtMaterial * 1)()
+    mats[0].kind = mat_kind; mats[0].bump = -1
+    for k in range(16):
+        mats[0].slot[k] = -1
+    mats[0].slot[14] = mat_slot
+    texs = (RtTexture * 1)()
+    texs[0].kind = sd.TEX_IMAGE; texs[0].image = 0 if tex_image is None else tex_image
+    d = RtSceneDesc()
+    d.n_images, d.images = 2, C.cast(imgs, C.c_void_p)
+    d.n_materials, d.materials = 1, C.cast(mats, C.c_void_p)
+    if tex_image is not None:
+        d.n_textures, d.textures = 1, C.cast(texs, C.c_void_p)
+    out = C.c_void_p()
+    L = host.hip_lib()
+    rc = L.rt_scene_create(C.byref(d), -1, C.byref(out))
+    msg = L.rt_last_error().decode()
+    if rc == 0:
+        L.rt_scene_destroy(out)
+    return rc, msg
+
+
+def test_scene_create_passes_a_good_table_on_to_the_device_checks():
+    rc, msg = _create(_words(fr.glossy_table(n_channels=3)))
+    assert rc != RT_ERR_INVALID or "Fourier" not in msg, msg   # RT_ERR_NO_DEVICE here, "empty scene" (INVALID) on a GPU box
+
+
+@pytest.mark.parametrize("what, edit, needle", [
+    ("short", lambda w: w[:-3], "do not add up"),
+    ("long", lambda w: np.concatenate([w, np.zeros(3, np.uint32)]), "do not add up"),
+    ("channels", lambda w: np.concatenate([w[:2], np.uint32([2]), w[3:]]), "nChannels"),
+])
+def test_scene_create_refuses_malformed_tables(what, edit, needle):
+    rc, msg = _create(edit(_words(fr.glossy_table())).astype(np.uint32))
+    assert rc == RT_ERR_INVALID and needle in msg, (rc, msg)
+
+
+def test_scene_create_refuses_an_offset_past_ncoeffs_and_mu_out_of_order():
+    t = fr.glossy_table()
+    w = _words(t)
+    n = t.n_mu
+    ol0 = 5 + n + n * n
+    bad = w.copy(); bad[ol0 + 2 * (n * n - 1)] = t.a.size
+    rc, msg = _create(bad)
+    assert rc == RT_ERR_INVALID and "nCoeffs" in msg, msg
+    bad = w.copy(); bad[5 + 1], bad[5 + 2] = w[5 + 2], w[5 + 1]
+    rc, msg = _create(bad)
+    assert rc == RT_ERR_INVALID and "ascending" in msg, msg
+
+
+def test_scene_create_refuses_crossed_references():
+    w = _words(fr.glossy_table())
+    rc, msg = _create(w, mat_slot=1)   # a Fourier material naming the pyramid
+    assert rc == RT_ERR_INVALID and "slot M1" in msg, msg
+    rc, msg = _create(w, mat_kind=sd.MAT_MATTE, tex_image=0)   # an image texture naming the table
+    assert rc == RT_ERR_INVALID and "image texture" in msg, msg
+
+
+# ---------------------------------------------------------------- the .pbrt loader and the exporter
+_SCENE = """LookAt 0 0 5  0 0 0  0 1 0
+Camera "perspective" "float fov" [30]
+Film "image" "integer xresolution" [16] "integer yresolution" [16]
+Sampler "02sequence" "integer pixelsamples" [4]
+WorldBegin
+LightSource "point" "point from" [0 0 3] "rgb I" [5 5 5]
+{material}
+Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [-1 -1 0  1 -1 0  1 1 0  -1 1 0]
+WorldEnd
+"""
+
+
+def _load(tmp_path, material, sub="scn"):
+    d = tmp_path / sub
+    d.mkdir(exist_ok=True)
+    (d / "tables").mkdir(exist_ok=True)
+    fr.write_table(str(d / "tables" / "g.bsdf"), fr.glossy_table(n_channels=3))
+    p = d / "s.pbrt"
+    p.write_text(_SCENE.format(material=material))
+    return host.PbrtScene(str(p))
+
+
+def test_loader_accepts_fourier_with_bsdffile_relative_to_the_scene(tmp_path):
+    s = _load(tmp_path, 'Material "fourier" "string bsdffile" "tables/g.bsdf"')
+    m = s.table("materials")
+    fm = [x for x in m if x["kind"] == sd.MAT_FOURIER]
+    assert len(fm) == 1 and fm[0]["slot"][14] >= 0 and fm[0]["bump"] == -1
+
+
+def test_loader_accepts_named_mix_and_bump(tmp_path):
+    s = _load(tmp_path, 'MakeNamedMaterial "f" "string type" "fourier" "string bsdffile" "tables/g.bsdf" "float bumpmap" [0.1]\n'
+                        'MakeNamedMaterial "m" "string type" "matte"\n'
+                        'MakeNamedMaterial "x" "string type" "mix" "string namedmaterial1" "f" "string namedmaterial2" "m"\n'
+                        'NamedMaterial "x"')
+    m = s.table("materials")
+    fm = [x for x in m if x["kind"] == sd.MAT_FOURIER]
+    assert len(fm) == 1 and fm[0]["bump"] >= 0
+    mix = [x for x in m if x["kind"] == sd.MAT_MIX]
+    assert len(mix) == 1 and m[mix[0]["slot"][14]]["kind"] == sd.MAT_FOURIER
+
+
+@pytest.mark.parametrize("material, needle", [('Material "fourier"', "bsdffile"), ('Material "fourier" "string bsdffile" ""', "bsdffile"),
+                                              ('Material "fourier" "string bsdffile" "tables/missing.bsdf"', "missing.bsdf")])
+def test_loader_refuses_an_empty_or_missing_file(tmp_path, material, needle):
+    with pytest.raises(host.BackendError, match=needle):
+        _load(tmp_path, material)
+
+
+def test_export_round_trips_a_fourier_scene(tmp_path):
+    t = fr.write_table(str(tmp_path / "g.bsdf"), fr.glossy_table(n_channels=3))
+    d = cornell_box(16, 16, 1)
+    f1 = d.fourier(t)
+    d.set_bump(f1, 0.05)
+    mix = d.mix(d.fourier(t), 0, 0.3)
+    for k, mid in ((0, f1), (2, mix)):  # floor -> bumped Fourier, back wall -> mix(Fourier, white)
+        d._mat[k][:] = mid
+    path = str(tmp_path / "c.pbrt")
+    write_pbrt(d, path)
+    assert '"fourier"' in open(path).read()
+    p, h = host.PbrtScene(path), host.HostScene(d)
+    mp, mh = p.table("materials"), h.table("materials")
+    kinds = lambda m: sorted(int(x["kind"]) for x in m)
+    assert kinds(mp) == kinds(mh) and sd.MAT_FOURIER in kinds(mp)
+    assert np.array_equal(p.table("tri_material").size, h.table("tri_material").size)
