@@ -82,8 +82,22 @@ typedef struct rt_instance {
 
 /* -- textures: replaces dyn Texture<T> (rc/texture/{constant,scale,mix,imagemap,checkerboard,uv,fbm}.rs) --
  * checkerboard (2D): tex1, tex2, mapping, amount = AAMethod (0 none, 1 closedform); uv: mapping;
- * fbm: value[0] = omega, amount = octaves (texture space = world space). */
-enum { RT_TEX_CONST = 0, RT_TEX_SCALE = 1, RT_TEX_MIX = 2, RT_TEX_IMAGE = 3, RT_TEX_CHECKER = 4, RT_TEX_UV = 5, RT_TEX_FBM = 6 };
+ * fbm: value[0] = omega, amount = octaves (texture space = world space).
+ * RT_TEX_CHECKER_PLANAR: a checkerboard under PlanarMapping2D (rc/texture/mod.rs:63-85): tex1, tex2, amount as for RT_TEX_CHECKER; `image` names a word block
+ *   (an rt_image with n_levels == 0) whose first 8 words are v1.xyz, v2.xyz, udelta, vdelta (f32); mapping[] is unused.
+ * RT_TEX_FBM_MAPPED: fbm under IdentityMapping3D (rc/texture/mod.rs:92-115): value[0] = omega, amount = octaves as for RT_TEX_FBM; `image` names a word
+ *   block whose first 16 words are the row-major 4 x 4 matrix applied to the hit point and its differentials - the CTM at the Texture directive itself, which
+ *   the reference stores as its world_to_texture.
+ * Scale, mix and checkerboards nest to any depth, and a mix amount may be any float texture. The graph must be acyclic. A graph's value slots (the combinator
+ * values alive at once while it is evaluated, heavier operands first) are held in registers and bounded by RT_TEX_SLOTS: every tree of at most 120
+ * combinators fits (the smallest tree that needs 9 values at once has 121, with three-operand mixes), a graph that shares a sub-graph keeps its value until
+ * its last reader, and rt_scene_create refuses a graph that needs more than RT_TEX_SLOTS - or, as an alpha mask, more than RT_TEX_MASK_SLOTS (every tree of
+ * at most 12 combinators fits) - naming the texture and its requirement. This falls short of "every graph of 64 combinators": a graph that shares many
+ * sub-graphs can need more than 8 values with fewer combinators. */
+enum { RT_TEX_CONST = 0, RT_TEX_SCALE = 1, RT_TEX_MIX = 2, RT_TEX_IMAGE = 3, RT_TEX_CHECKER = 4, RT_TEX_UV = 5, RT_TEX_FBM = 6, RT_TEX_CHECKER_PLANAR = 7,
+       RT_TEX_FBM_MAPPED = 8 };
+#define RT_TEX_SLOTS 8
+#define RT_TEX_MASK_SLOTS 4 /* ... of the graph of an alpha / shadow-alpha mask (evaluated inside the traversal kernels) */
 typedef struct rt_texture {
   int32_t kind;
   float value[3];             /* constant; float textures use value[0]                 */
@@ -93,12 +107,15 @@ typedef struct rt_texture {
 } rt_texture;
 
 /* -- MIP pyramid built by the host: replaces MIPMap<Spectrum> (rc/mipmap.rs:46-53) ---------
- * An image with n_levels == 0 is a Fourier BSDF table instead (FourierBSDFTable, rc/bsdf/fourier.rs:281-371) that an RT_MAT_FOURIER material names:
+ * An image with n_levels == 0 is a block of packed 32-bit words instead: the word block of an RT_TEX_CHECKER_PLANAR / RT_TEX_FBM_MAPPED texture that names it,
+ * or else a Fourier BSDF table (FourierBSDFTable, rc/bsdf/fourier.rs:281-371) that an RT_MAT_FOURIER material names:
  * `texels` points to 3 * n_texels packed 32-bit words (zero-padded to a whole texel) - the header {nMu, mMax, nChannels, nCoeffs as u32, eta as f32},
  * then mu[nMu] (f32, strictly ascending), cdf[nMu * nMu] (f32), offset_and_length[2 * nMu * nMu] (u32) and a[nCoeffs] (f32), as a .bsdf file lists them.
  * rt_scene_create / rt_multi_create refuse with RT_ERR_INVALID (before any device is touched) a table whose sizes do not add up, with nMu outside [2, 8192],
  * nChannels not 1 or 3, mu not ascending, a cell longer than mMax or whose coefficients run past nCoeffs, more than 2^28 table words in the scene, a Fourier
- * material whose slot M1 names a MIP pyramid, and an image texture or infinite light that names a table. width / height / offset / trilinear / wrap are unused. */
+ * material whose slot M1 names a MIP pyramid, and an image texture or infinite light that names a table. width / height / offset / trilinear / wrap are unused.
+ * They refuse as well (RT_ERR_INVALID, before any device is touched) a word block shorter than its texture's words, a mapped texture that names a MIP
+ * pyramid, a Fourier material, image texture or infinite light that names a word block, a texture graph with a cycle and an operand out of range. */
 enum { RT_WRAP_REPEAT = 0, RT_WRAP_BLACK = 1, RT_WRAP_CLAMP = 2 };
 #define RT_MAX_MIP_LEVELS 16
 typedef struct rt_image {
@@ -349,6 +366,11 @@ int rt_offset_ray_origin(const float* p, const float* p_error, const float* n, c
  * the shade kernel on n queries in the shading frame (TransportMode::RADIANCE, no bump map, no mix): wo, wi n x 3 floats, u n x 2 (sample_f's u[0], u[1]).
  * out: n x 11 floats - f(wo, wi) rgb, pdf(wo, wi), then sample_f(wo, u): f rgb, wi xyz, pdf. Host pointers. For the parity tests. */
 int rt_fourier_eval(rt_scene* scene, int32_t material, uint64_t n, const float* wo, const float* wi, const float* u, float* out);
+
+/* Texture::evaluate (rc/texture/*.rs) of texture `texture` of the scene on n records, run by the device evaluator the shade kernels call. records: n x 15
+ * floats in the order u v dudx dvdx dudy dvdy p.xyz dpdx.xyz dpdy.xyz; rgb_out: n x 3 (a float texture: its value three times). Host pointers. For the
+ * parity tests. */
+int rt_texture_eval(rt_scene* scene, int32_t texture, uint64_t n, const float* records, float* rgb_out);
 
 /* Dense voxel light distribution of SpatialLightDistribution (rc/lightdistrib.rs:101-179):
  * n_voxels[3]; func: nvox*n_lights, cdf: nvox*(n_lights+1), func_int: nvox (host pointers, may be NULL

@@ -96,6 +96,11 @@ int rtxh_scene_add_mipmap(rtxh_scene*, int32_t width, int32_t height, const floa
  * read before returns the same id. */
 int rtxh_scene_add_fourier_table(rtxh_scene*, const char* path);
 int rtxh_scene_add_texture(rtxh_scene*, int32_t kind, const float* value3, int32_t tex1, int32_t tex2, int32_t amount, int32_t mip, const float* mapping4);
+/* A texture with a word block (rtx_hip.h: RT_TEX_CHECKER_PLANAR - v1.xyz v2.xyz udelta vdelta; RT_TEX_FBM_MAPPED - a row-major 4 x 4 matrix): the n_words
+ * words become an image with n_levels == 0 that the texture names. Returns the texture id. */
+int rtxh_scene_add_texture_mapped(rtxh_scene*, int32_t kind, const float* value3, int32_t tex1, int32_t tex2, int32_t amount, const float* words, int32_t n_words);
+/* The words of texture `texture`'s word block, `capacity` at most into `out` (may be NULL). Returns their number; 0 for a texture that names none. */
+int rtxh_texture_words(rtxh_scene*, int32_t texture, float* out, int32_t capacity);
 int rtxh_scene_add_material(rtxh_scene*, int32_t kind, const int32_t* slots16, int32_t remap_roughness, int32_t bump_texture /* or -1 */);
 int rtxh_scene_add_light(rtxh_scene*, int32_t kind, int32_t tri, const float* rgb3, int32_t two_sided, const float* vec3, int32_t mip,
                          const float* l2w16, const float* w2l16);

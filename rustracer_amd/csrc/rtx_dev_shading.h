@@ -124,7 +124,7 @@ RT_DEV float noise_grad(int x, int y, int z, float dx, float dy, float dz) {  //
   return ((h & 1) ? -u : u) + ((h & 2) ? -v : v);
 }
 RT_DEV float noise_weight(float t) { float t3 = t * t * t, t4 = t3 * t; return 6.0f * t4 * t - 15.0f * t4 + 10.0f * t3; }  // :78-83
-RT_DEVN float noise_perlin(float x, float y, float z) {  // noise.rs:8-43
+RT_DEV float noise_perlin_body(float x, float y, float z) {  // noise.rs:8-43
   int ix = f2i_sat(floorf(x)), iy = f2i_sat(floorf(y)), iz = f2i_sat(floorf(z));
   float dx = x - (float)ix, dy = y - (float)iy, dz = z - (float)iz;
   ix &= 255; iy &= 255; iz &= 255;
@@ -137,21 +137,36 @@ RT_DEVN float noise_perlin(float x, float y, float z) {  // noise.rs:8-43
   float y0 = lerpf(wy, x00, x10), y1 = lerpf(wy, x01, x11);
   return lerpf(wz, y0, y1);
 }
-RT_DEV float noise_fbm(f3 p, f3 dpdx, f3 dpdy, float omega, unsigned max_octaves) {  // noise.rs:46-66
+RT_DEVN float noise_perlin(float x, float y, float z) { return noise_perlin_body(x, y, z); }
+// INLINE: the Perlin lattice inline as well (the alpha-mask program evaluator: no call in its loop, so no register of it has to survive one)
+template <bool INLINE = false>
+RT_DEV float noise_fbm_t(f3 p, f3 dpdx, f3 dpdy, float omega, unsigned max_octaves) {  // noise.rs:46-66
   float l2 = fmaxf(len2(dpdx), len2(dpdy));
   float n = clampf(-1.0f - 0.5f * log2f(l2), 0.0f, (float)max_octaves);
   unsigned n_int = f2u_sat(floorf(n));
   float sum = 0.0f, lambda = 1.0f, o = 1.0f;
+  if (INLINE) {  // one lattice evaluation site: the octaves, then the partial one with weight o * smooth_step (the same products, in the same order)
+    const float n_partial = n - (float)n_int;
+    const float v = clampf((n_partial - 0.3f) / (0.7f - 0.3f), 0.0f, 1.0f);
+    for (unsigned i = 0; i <= n_int; ++i) {
+      const float w = i < n_int ? o : o * (v * v * (-2.0f * v + 3.0f));
+      sum += w * noise_perlin_body(lambda * p.x, lambda * p.y, lambda * p.z);
+      lambda *= 1.99f;
+      o *= omega;
+    }
+    return sum;
+  }
   for (unsigned i = 0; i < n_int; ++i) {
-    sum += o * noise_perlin(lambda * p.x, lambda * p.y, lambda * p.z);
+    sum += o * (INLINE ? noise_perlin_body(lambda * p.x, lambda * p.y, lambda * p.z) : noise_perlin(lambda * p.x, lambda * p.y, lambda * p.z));
     lambda *= 1.99f;
     o *= omega;
   }
   float n_partial = n - (float)n_int;
   float v = clampf((n_partial - 0.3f) / (0.7f - 0.3f), 0.0f, 1.0f);  // smooth_step, :85-89
-  sum += o * (v * v * (-2.0f * v + 3.0f)) * noise_perlin(lambda * p.x, lambda * p.y, lambda * p.z);
+  sum += o * (v * v * (-2.0f * v + 3.0f)) * (INLINE ? noise_perlin_body(lambda * p.x, lambda * p.y, lambda * p.z) : noise_perlin(lambda * p.x, lambda * p.y, lambda * p.z));
   return sum;
 }
+RT_DEV float noise_fbm(f3 p, f3 dpdx, f3 dpdy, float omega, unsigned max_octaves) { return noise_fbm_t<false>(p, dpdx, dpdy, omega, max_octaves); }
 
 // What a texture reads of the SurfaceInteraction (texture/mod.rs:52-60 UVMapping2D, noise.rs): 15 dwords, handed to the out-of-line evaluator by value in
 // registers - a reference would pin the caller's whole SurfaceInteraction in scratch.
@@ -170,14 +185,13 @@ RT_DEV rgb3 tex_leaf(const DImage* images, const DTexture& t, const TexIn& si) {
   f2 dstdx = mk2(t.su * si.dudx, t.sv * si.dvdx), dstdy = mk2(t.su * si.dudy, t.sv * si.dvdy);
   return mip_lookup_diff(images[t.image], st, dstdx, dstdy);
 }
-// checkerboard.rs:102-143: which of the two operands, or the box-filtered blend. Returns 0 = tex1, 1 = tex2, 2 = blend with area2.
-RT_DEV int checker_select(const DTexture& t, const TexIn& si, float& area2) {
-  f2 st = mk2(t.su * si.uv.x + t.du, t.sv * si.uv.y + t.dv);
-  if (t.amount == 0) {  // AAMethod::None: `floor() as u32` saturates negatives to 0, the u32 sum wraps
+// checkerboard.rs:102-143 on the mapped (st, dstdx, dstdy): which of the two operands, or the box-filtered blend. Returns 0 = tex1, 1 = tex2, 2 = blend
+// with area2. `aa` = AAMethod (0 none, 1 closed form).
+RT_DEV int checker_pick(int aa, f2 st, f2 dstdx, f2 dstdy, float& area2) {
+  if (aa == 0) {  // AAMethod::None: `floor() as u32` saturates negatives to 0, the u32 sum wraps
     unsigned a = f2u_sat(floorf(st.x)), b = f2u_sat(floorf(st.y));
     return ((a + b) % 2u == 0u) ? 0 : 1;
   }
-  f2 dstdx = mk2(t.su * si.dudx, t.sv * si.dvdx), dstdy = mk2(t.su * si.dudy, t.sv * si.dvdy);
   float ds = fmaxf(fabsf(dstdx.x), fabsf(dstdy.x)), dt = fmaxf(fabsf(dstdx.y), fabsf(dstdy.y));
   float s0 = st.x - ds, s1 = st.x + ds, t0 = st.y - dt, t1 = st.y + dt;
   if (floorf(s0) == floorf(s1) && floorf(t0) == floorf(t1)) {
@@ -193,6 +207,10 @@ RT_DEV int checker_select(const DTexture& t, const TexIn& si, float& area2) {
   if (ds > 1.0f || dt > 1.0f) area2 = 0.5f;
   return 2;
 }
+// ... under UVMapping2D (texture/mod.rs:52-60)
+RT_DEV int checker_select(const DTexture& t, const TexIn& si, float& area2) {
+  return checker_pick(t.amount, mk2(t.su * si.uv.x + t.du, t.sv * si.uv.y + t.dv), mk2(t.su * si.dudx, t.sv * si.dvdx), mk2(t.su * si.dudy, t.sv * si.dvdy), area2);
+}
 RT_DEV rgb3 tex_combine(const DTexture* textures, const DImage* images, const DTexture& t, rgb3 a, rgb3 b, const TexIn& si) {
   if (t.kind == 1) return a * b;  // scale.rs:23-25
   if (t.kind == 2) { float amt = tex_leaf(images, textures[t.amount], si).r; return a * (1.0f - amt) + b * amt; }  // mix.rs:24
@@ -205,14 +223,152 @@ RT_DEV rgb3 tex_depth1(const DTexture* textures, const DImage* images, const DTe
   if (tex_is_leaf(t.kind)) return tex_leaf(images, t, si);
   return tex_combine(textures, images, t, tex_leaf(images, textures[t.tex1], si), tex_leaf(images, textures[t.tex2], si), si);
 }
-// combinators nest two deep at most (a combinator of combinators of leaves); the host rejects deeper scenes
+// ---- the shapes the two-level evaluator below does not take (rt_scene_create): RT_TEX_CHECKER_PLANAR, RT_TEX_FBM_MAPPED and combinators nested deeper than
+// two or with a combinator as mix amount. Their words sit in side records behind the scene's textures (DTexture::image = the first one; the 48-byte record
+// itself is unchanged): a planar checkerboard's are {v1.xyz, v2.xyz, udelta, vdelta}, a mapped fbm's its row-major 4 x 4 matrix. A combinator that roots
+// such a graph has a program there, from word 8 on (a planar checkerboard's words 0-7 are its mapping): n, then n instructions {node, dst, r0, r1, r2} in
+// post-order - combinator `node` of its operands (tex1, tex2, mix amount) into value slot `dst`; r >= 0 is a leaf texture evaluated in place, r < 0 the
+// combinator value in slot -1 - r.
+// PlanarMapping2D::map (texture/mod.rs:63-85): dot products in x, y, z order on the world-space point and its differentials
+RT_DEV f2 planar_map(const float* w, f3 v) { return mk2(v.x * w[0] + v.y * w[1] + v.z * w[2], v.x * w[3] + v.y * w[4] + v.z * w[5]); }
+RT_DEV int checker_select_planar(const DTexture* textures, const DTexture& t, const TexIn& si, float& area2) {
+  const float* w = (const float*)&textures[t.image];
+  const f2 d = planar_map(w, si.p);
+  return checker_pick(t.amount, mk2(w[6] + d.x, w[7] + d.y), planar_map(w, si.dpdx), planar_map(w, si.dpdy), area2);
+}
+// fbm under IdentityMapping3D (texture/mod.rs:92-115): the CTM at the Texture directive applied as `Transform * Point3f` / `* Vector3f` (transform.rs:264-303).
+// The reference asserts w != 0 and aborts there; this texture is 0 instead.
+template <bool INLINE = false>
+RT_DEV float fbm_mapped(const DTexture* textures, const DTexture& t, const TexIn& si) {
+  const float* m = (const float*)&textures[t.image];
+  const f3 p = si.p;
+  float x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3], y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7], z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
+  const float w = m[12] * p.x + m[13] * p.y + m[14] * p.z + m[15];
+  if (w == 0.0f) return 0.0f;
+  if (w != 1.0f) { x = x / w; y = y / w; z = z / w; }
+  const f3 a = si.dpdx, b = si.dpdy;
+  const f3 dx = mk3(m[0] * a.x + m[1] * a.y + m[2] * a.z, m[4] * a.x + m[5] * a.y + m[6] * a.z, m[8] * a.x + m[9] * a.y + m[10] * a.z);
+  const f3 dy = mk3(m[0] * b.x + m[1] * b.y + m[2] * b.z, m[4] * b.x + m[5] * b.y + m[6] * b.z, m[8] * b.x + m[9] * b.y + m[10] * b.z);
+  return noise_fbm_t<INLINE>(mk3(x, y, z), dx, dy, t.v[0], (unsigned)(t.amount < 0 ? 0 : t.amount));
+}
+// A leaf of a program
+RT_DEV rgb3 tex_leaf_any(const DTexture* textures, const DImage* images, int id, f2 uv, float dudx, float dvdx, float dudy, float dvdy, float px, float py, float pz,
+                          float dpdx_x, float dpdx_y, float dpdx_z, float dpdy_x, float dpdy_y, float dpdy_z) {
+  TexIn si; si.uv = uv; si.dudx = dudx; si.dvdx = dvdx; si.dudy = dudy; si.dvdy = dvdy; si.p = mk3(px, py, pz); si.dpdx = mk3(dpdx_x, dpdx_y, dpdx_z); si.dpdy = mk3(dpdy_x, dpdy_y, dpdy_z);
+  const DTexture& t = textures[id];
+  if (t.kind == 8) { const float f = fbm_mapped(textures, t, si); return mkc(f, f, f); }
+  return tex_leaf(images, t, si);
+}
+// The program of a graph root (see above), each combinator evaluated once, operands eagerly. Its RT_TEX_SLOTS value slots (rtx_hip.h) are registers: every
+// access below is unrolled over the slots with constant indices, so no array reaches private memory - the kernels that can reach this code (the generic
+// front-end, the mask-aware traversal and shade kernels) keep their scratch budgets.
+template <int SLOTS = RT_TEX_SLOTS>
+RT_DEV rgb3 tex_slot_get(const rgb3* s, int k) {
+  rgb3 r = s[0];
+#pragma unroll
+  for (int i = 1; i < SLOTS; ++i) if (k == i) r = s[i];
+  return r;
+}
+RT_DEVN rgb3 tex_eval_prog(const DTexture* textures, const DImage* images, int id, f2 uv, float dudx, float dvdx, float dudy, float dvdy, float px, float py, float pz,
+                           float dpdx_x, float dpdx_y, float dpdx_z, float dpdy_x, float dpdy_y, float dpdy_z) {
+  TexIn si; si.uv = uv; si.dudx = dudx; si.dvdx = dvdx; si.dudy = dudy; si.dvdy = dvdy; si.p = mk3(px, py, pz); si.dpdx = mk3(dpdx_x, dpdx_y, dpdx_z); si.dpdy = mk3(dpdy_x, dpdy_y, dpdy_z);
+  const DTexture& root = textures[id];
+  if (root.kind == 8) return tex_leaf_any(textures, images, id, uv, dudx, dvdx, dudy, dvdy, px, py, pz, dpdx_x, dpdx_y, dpdx_z, dpdy_x, dpdy_y, dpdy_z);
+  const int* prog = (const int*)&textures[root.image] + 8;
+  const int n = prog[0];
+  rgb3 slot[RT_TEX_SLOTS];
+#pragma unroll
+  for (int i = 0; i < RT_TEX_SLOTS; ++i) slot[i] = mkc(0, 0, 0);
+  rgb3 v = mkc(0, 0, 0);
+  for (int i = 0; i < n; ++i) {
+    const int* in = prog + 1 + 5 * i;
+    const DTexture& t = textures[in[0]];
+    rgb3 op[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int r = in[2 + k];
+      if (k == 2 && t.kind != 2) { op[k] = mkc(0, 0, 0); continue; }
+      op[k] = r < 0 ? tex_slot_get(slot, -1 - r) : tex_leaf_any(textures, images, r, uv, dudx, dvdx, dudy, dvdy, px, py, pz, dpdx_x, dpdx_y, dpdx_z, dpdy_x, dpdy_y, dpdy_z);
+    }
+    if (t.kind == 1) v = op[0] * op[1];  // scale.rs:23-25
+    else if (t.kind == 2) { const float amt = op[2].r; v = op[0] * (1.0f - amt) + op[1] * amt; }  // mix.rs:24
+    else {
+      float area2 = 0.0f;
+      const int sel = t.kind == 7 ? checker_select_planar(textures, t, si, area2) : checker_select(t, si, area2);
+      v = sel == 0 ? op[0] : (sel == 1 ? op[1] : op[0] * (1.0f - area2) + op[1] * area2);
+    }
+    const int dst = in[1];
+#pragma unroll
+    for (int k = 0; k < RT_TEX_SLOTS; ++k) if (dst == k) slot[k] = v;
+  }
+  return v;  // (the root is the last instruction)
+}
+// The same program at an alpha-mask lookup, which has no differentials (mesh.rs:353-370, 534-582; tri_alpha_rejects): a leaf is then what tex_leaf gives
+// for zero footprints - an image map its level-0 bilinear lookup (mip_lookup_diff, see tex_eval_leaf_bounced), fbm every octave, a checkerboard a point
+// sample - and everything is inline. Its RT_TEX_MASK_SLOTS value slots (rt_scene_create refuses a mask whose program needs more) keep the frame the
+// mask-aware traversal kernels give it within their scratch budget.
+RT_DEV rgb3 tex_leaf_mask(const DTexture* textures, const DImage* images, const DTexture& t, const TexIn& si) {
+  if (t.kind == 0) return mkc(t.v[0], t.v[1], t.v[2]);
+  if (t.kind == 6 || t.kind == 8) {
+    const float f = t.kind == 8 ? fbm_mapped<true>(textures, t, si) : noise_fbm_t<true>(si.p, si.dpdx, si.dpdy, t.v[0], (unsigned)(t.amount < 0 ? 0 : t.amount));
+    return mkc(f, f, f);
+  }
+  const f2 st = mk2(t.su * si.uv.x + t.du, t.sv * si.uv.y + t.dv);
+  if (t.kind == 5) return mkc(st.x - floorf(st.x), st.y - floorf(st.y), 0.0f);
+  return mip_triangle(images[t.image], 0, st);
+}
+RT_DEVN rgb3 tex_eval_prog_mask(const DTexture* textures, const DImage* images, int id, f2 uv, float px, float py, float pz) {
+  TexIn si; si.uv = uv; si.dudx = si.dvdx = si.dudy = si.dvdy = 0.0f; si.p = mk3(px, py, pz); si.dpdx = si.dpdy = mk3(0.0f, 0.0f, 0.0f);
+  const DTexture& root = textures[id];
+  if (root.kind == 8) return tex_leaf_mask(textures, images, root, si);
+  const int* prog = (const int*)&textures[root.image] + 8;
+  const int n = prog[0];
+  rgb3 slot[RT_TEX_MASK_SLOTS];
+#pragma unroll
+  for (int i = 0; i < RT_TEX_MASK_SLOTS; ++i) slot[i] = mkc(0, 0, 0);
+  rgb3 v = mkc(0, 0, 0);
+  for (int i = 0; i < n; ++i) {
+    const int* in = prog + 1 + 5 * i;
+    const DTexture& t = textures[in[0]];
+    rgb3 op[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int r = in[2 + k];
+      if (k == 2 && t.kind != 2) { op[k] = mkc(0, 0, 0); continue; }
+      op[k] = r < 0 ? tex_slot_get<RT_TEX_MASK_SLOTS>(slot, -1 - r) : tex_leaf_mask(textures, images, textures[r], si);
+    }
+    if (t.kind == 1) v = op[0] * op[1];
+    else if (t.kind == 2) { const float amt = op[2].r; v = op[0] * (1.0f - amt) + op[1] * amt; }
+    else {
+      float area2 = 0.0f;
+      const int sel = t.kind == 7 ? checker_select_planar(textures, t, si, area2) : checker_select(t, si, area2);
+      v = sel == 0 ? op[0] : (sel == 1 ? op[1] : op[0] * (1.0f - area2) + op[1] * area2);
+    }
+    const int dst = in[1];
+#pragma unroll
+    for (int k = 0; k < RT_TEX_MASK_SLOTS; ++k) if (dst == k) slot[k] = v;
+  }
+  return v;
+}
+// combinators nest two deep at most (a combinator of combinators of leaves); rt_scene_create gives every other graph root a program (tex_eval_prog)
+RT_DEV rgb3 tex_two_level(const DTexture* textures, const DImage* images, const DTexture& t, const TexIn& si) {
+  if (tex_is_leaf(t.kind)) return tex_leaf(images, t, si);
+  return tex_combine(textures, images, t, tex_depth1(textures, images, textures[t.tex1], si), tex_depth1(textures, images, textures[t.tex2], si), si);
+}
 // The register budget of a call's aggregate arguments is 16 dwords, pointers included; scalars always travel in registers - hence the nine floats.
 RT_DEVN rgb3 tex_eval_q(const DTexture* textures, const DImage* images, int id, f2 uv, float dudx, float dvdx, float dudy, float dvdy, float px, float py, float pz,
                         float dpdx_x, float dpdx_y, float dpdx_z, float dpdy_x, float dpdy_y, float dpdy_z) {
-  TexIn si; si.uv = uv; si.dudx = dudx; si.dvdx = dvdx; si.dudy = dudy; si.dvdy = dvdy; si.p = mk3(px, py, pz); si.dpdx = mk3(dpdx_x, dpdx_y, dpdx_z); si.dpdy = mk3(dpdy_x, dpdy_y, dpdy_z);
   const DTexture& t = textures[id];
-  if (tex_is_leaf(t.kind)) return tex_leaf(images, t, si);
-  return tex_combine(textures, images, t, tex_depth1(textures, images, textures[t.tex1], si), tex_depth1(textures, images, textures[t.tex2], si), si);
+  if (t.kind > 6 || (t.image >= 0 && !tex_is_leaf(t.kind)))
+    return tex_eval_prog(textures, images, id, uv, dudx, dvdx, dudy, dvdy, px, py, pz, dpdx_x, dpdx_y, dpdx_z, dpdy_x, dpdy_y, dpdy_z);
+  TexIn si; si.uv = uv; si.dudx = dudx; si.dvdx = dvdx; si.dudy = dudy; si.dvdy = dvdy; si.p = mk3(px, py, pz); si.dpdx = mk3(dpdx_x, dpdx_y, dpdx_z); si.dpdy = mk3(dpdy_x, dpdy_y, dpdy_z);
+  return tex_two_level(textures, images, t, si);
+}
+// ... of an alpha mask whose graph the two-level code takes (tri_alpha_rejects; tex_eval_prog_mask runs the others)
+RT_DEVN rgb3 tex_eval_mask_q(const DTexture* textures, const DImage* images, int id, f2 uv, float dudx, float dvdx, float dudy, float dvdy, float px, float py, float pz,
+                             float dpdx_x, float dpdx_y, float dpdx_z, float dpdy_x, float dpdy_y, float dpdy_z) {
+  TexIn si; si.uv = uv; si.dudx = dudx; si.dvdx = dvdx; si.dudy = dudy; si.dvdy = dvdy; si.p = mk3(px, py, pz); si.dpdx = mk3(dpdx_x, dpdx_y, dpdx_z); si.dpdy = mk3(dpdy_x, dpdy_y, dpdy_z);
+  return tex_two_level(textures, images, textures[id], si);
 }
 RT_DEV rgb3 tex_eval(const DScene& sc, int id, const SurfaceInteraction& si) {
   return tex_eval_q(sc.textures, sc.images, id, si.uv, si.dudx, si.dvdx, si.dudy, si.dvdy, si.hit.p.x, si.hit.p.y, si.hit.p.z, si.dpdx.x, si.dpdx.y, si.dpdx.z, si.dpdy.x, si.dpdy.y, si.dpdy.z);
@@ -260,8 +416,13 @@ RT_DEVN bool tri_alpha_rejects(const DScene& sc, int prim, const TriHit& h, bool
   si.dudx = si.dvdx = si.dudy = si.dvdy = 0.0f; si.dpdx = si.dpdy = mk3(0, 0, 0);
   si.hit.p_error = si.hit.wo = si.hit.n = si.dpdu = si.dpdv = si.sh_n = si.sh_dpdu = si.sh_dpdv = mk3(0, 0, 0); si.prim = prim;
   const int2 ids = sc.tri_alpha[prim];
-  if ((flags & 16u) && tex_eval(sc, ids.x, si).r == 0.0f) return true;
-  if (shadow_ray && (flags & 32u) && tex_eval(sc, ids.y, si).r == 0.0f) return true;
+  auto mask = [&](int id) {
+    const DTexture& t = sc.textures[id];
+    if (t.kind > 6 || (t.image >= 0 && !tex_is_leaf(t.kind))) return tex_eval_prog_mask(sc.textures, sc.images, id, si.uv, si.hit.p.x, si.hit.p.y, si.hit.p.z).r;
+    return tex_eval_mask_q(sc.textures, sc.images, id, si.uv, 0.0f, 0.0f, 0.0f, 0.0f, si.hit.p.x, si.hit.p.y, si.hit.p.z, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f).r;
+  };
+  if ((flags & 16u) && mask(ids.x) == 0.0f) return true;
+  if (shadow_ray && (flags & 32u) && mask(ids.y) == 0.0f) return true;
   return false;
 }
 

@@ -241,11 +241,23 @@ static std::string fourier_table_error(const rt_image& im, uint64_t& words) {
   return "";
 }
 // The Fourier half of a scene description's checks, made before any device is touched: the tables, and every reference to an image that is one
+static bool tex_mapped(int kind) { return kind == RT_TEX_CHECKER_PLANAR || kind == RT_TEX_FBM_MAPPED; }
+// per image: whether a mapped texture (RT_TEX_CHECKER_PLANAR / RT_TEX_FBM_MAPPED) names it as its word block
+static std::vector<char> word_blocks(const rt_scene_desc* desc) {
+  std::vector<char> b(desc->images ? desc->n_images : 0, 0);
+  for (uint32_t i = 0; i < desc->n_textures && desc->textures; ++i) {
+    const rt_texture& t = desc->textures[i];
+    if (tex_mapped(t.kind) && t.image >= 0 && (size_t)t.image < b.size()) b[t.image] = 1;
+  }
+  return b;
+}
 static std::string fourier_desc_error(const rt_scene_desc* desc) {
-  auto is_table = [&](int id) { return id >= 0 && (uint32_t)id < desc->n_images && desc->images && desc->images[id].n_levels == 0; };
+  const std::vector<char> block = word_blocks(desc);
+  auto is_block = [&](int id) { return id >= 0 && (size_t)id < block.size() && block[id]; };
+  auto is_table = [&](int id) { return id >= 0 && (uint32_t)id < desc->n_images && desc->images && desc->images[id].n_levels == 0 && !is_block(id); };
   uint64_t total = 0;
   for (uint32_t i = 0; i < desc->n_images; ++i) {
-    if (!desc->images || desc->images[i].n_levels != 0) continue;
+    if (!desc->images || desc->images[i].n_levels != 0 || is_block((int)i)) continue;
     uint64_t words = 0;
     const std::string why = fourier_table_error(desc->images[i], words);
     if (!why.empty()) return "image " + std::to_string(i) + ": " + why;
@@ -254,18 +266,165 @@ static std::string fourier_desc_error(const rt_scene_desc* desc) {
   }
   for (uint32_t i = 0; i < desc->n_materials && desc->materials; ++i) {
     const rt_material& m = desc->materials[i];
+    if (m.kind == RT_MAT_FOURIER && is_block(m.slot[RT_SLOT_M1]))
+      return "material " + std::to_string(i) + ": a Fourier material names the word block of a mapped texture, not a Fourier BSDF table";
     if (m.kind == RT_MAT_FOURIER && !is_table(m.slot[RT_SLOT_M1]))
       return "material " + std::to_string(i) + ": a Fourier material must name a Fourier BSDF table (n_levels == 0) in slot M1, not a MIP pyramid";
   }
   for (uint32_t i = 0; i < desc->n_textures && desc->textures; ++i)
     if (desc->textures[i].kind == RT_TEX_IMAGE && is_table(desc->textures[i].image)) return "texture " + std::to_string(i) + ": an image texture names a Fourier BSDF table, not a MIP pyramid";
-  for (uint32_t i = 0; i < desc->n_lights && desc->lights; ++i)
+  for (uint32_t i = 0; i < desc->n_textures && desc->textures; ++i)
+    if (desc->textures[i].kind == RT_TEX_IMAGE && is_block(desc->textures[i].image)) return "texture " + std::to_string(i) + ": an image texture names the word block of a mapped texture, not a MIP pyramid";
+  for (uint32_t i = 0; i < desc->n_lights && desc->lights; ++i) {
     if (desc->lights[i].kind == RT_LIGHT_INFINITE && is_table(desc->lights[i].image)) return "light " + std::to_string(i) + ": an infinite light names a Fourier BSDF table, not a MIP pyramid";
+    if (desc->lights[i].kind == RT_LIGHT_INFINITE && is_block(desc->lights[i].image)) return "light " + std::to_string(i) + ": an infinite light names the word block of a mapped texture, not a MIP pyramid";
+  }
+  return "";
+}
+
+// ---- texture graphs (rtx_dev_shading.h, tex_eval_q / tex_eval_prog). Roots of the shapes the two-level evaluator takes - combinators of combinators of
+// leaves, kinds 0-6, mix amounts leaves - keep it; every other texture that is no leaf gets a post-order program in side records behind the textures.
+static bool tex_comb(int kind) { return kind == RT_TEX_SCALE || kind == RT_TEX_MIX || kind == RT_TEX_CHECKER || kind == RT_TEX_CHECKER_PLANAR; }
+static int tex_n_ops(int kind) { return kind == RT_TEX_MIX ? 3 : (tex_comb(kind) ? 2 : 0); }
+static int tex_op(const rt_texture& t, int k) { return k == 0 ? t.tex1 : (k == 1 ? t.tex2 : t.amount); }
+static bool tex_two_level(const rt_scene_desc* desc, int id) {
+  auto leaf = [&](int i) { const int k = desc->textures[i].kind; return k == RT_TEX_CONST || k == RT_TEX_IMAGE || k == RT_TEX_UV || k == RT_TEX_FBM; };
+  auto depth1 = [&](int i) {  // a leaf, or a combinator of kinds 1, 2, 4 over leaves
+    const rt_texture& t = desc->textures[i];
+    if (leaf(i)) return true;
+    if (t.kind != RT_TEX_SCALE && t.kind != RT_TEX_MIX && t.kind != RT_TEX_CHECKER) return false;
+    for (int k = 0; k < tex_n_ops(t.kind); ++k) if (!leaf(tex_op(t, k))) return false;
+    return true;
+  };
+  const rt_texture& t = desc->textures[id];
+  if (t.kind != RT_TEX_SCALE && t.kind != RT_TEX_MIX && t.kind != RT_TEX_CHECKER) return t.kind <= RT_TEX_FBM;
+  return depth1(t.tex1) && depth1(t.tex2) && (t.kind != RT_TEX_MIX || leaf(t.amount));
+}
+#define RT_TEX_PROGRAM_WORDS (1ull << 24)  // 64 MB of programs per scene at most
+// Every check of the texture table, and the programs: side words to append behind the n_textures records (DTexture::image of texture i = side_at[i] / 12 +
+// n_textures, or -1). Returns what is wrong, or "". Runs before any device is touched.
+static std::string texture_programs(const rt_scene_desc* desc, std::vector<int32_t>* side, std::vector<int64_t>* side_at, std::vector<int>* slots_of = nullptr) {
+  const uint32_t nt = desc->n_textures;
+  if (nt && !desc->textures) return "texture table missing";
+  auto ok = [&](int id) { return id >= 0 && (uint32_t)id < nt; };
+  for (uint32_t i = 0; i < nt; ++i) {
+    const rt_texture& t = desc->textures[i];
+    const std::string who = "texture " + std::to_string(i) + ": ";
+    if (t.kind < RT_TEX_CONST || t.kind > RT_TEX_FBM_MAPPED) return who + "unknown texture kind";
+    for (int k = 0; k < tex_n_ops(t.kind); ++k) if (!ok(tex_op(t, k))) return who + (k == 2 ? "mix amount out of range" : "texture operand out of range");
+    if (tex_mapped(t.kind)) {
+      const uint64_t need = t.kind == RT_TEX_CHECKER_PLANAR ? 8 : 16;
+      if (t.image < 0 || (uint32_t)t.image >= desc->n_images || !desc->images) return who + "word block image index out of range";
+      const rt_image& im = desc->images[t.image];
+      if (im.n_levels != 0) return who + "a mapped texture names a MIP pyramid, not a word block (n_levels == 0)";
+      if (!im.texels || 3 * im.n_texels < need) return who + "word block shorter than " + std::to_string(need) + " words";
+    }
+  }
+  // cycles (a C caller can build one; the reference cannot): depth-first over the operand edges, iteratively
+  std::vector<char> color(nt, 0);  // 0 new, 1 on the path, 2 done
+  std::vector<std::pair<int, int>> st;
+  for (uint32_t r = 0; r < nt; ++r) {
+    if (color[r]) continue;
+    st.push_back({(int)r, 0}); color[r] = 1;
+    while (!st.empty()) {
+      const int v = st.back().first; const int k = st.back().second;
+      const rt_texture& t = desc->textures[v];
+      if (k < tex_n_ops(t.kind)) {
+        ++st.back().second;
+        const int u = tex_op(t, k);
+        if (color[u] == 1) return "texture " + std::to_string(u) + ": the texture graph has a cycle";
+        if (color[u] == 0) { color[u] = 1; st.push_back({u, 0}); }
+      } else { color[v] = 2; st.pop_back(); }
+    }
+  }
+  // Sethi-Ullman numbers over the combinators (leaves are evaluated in place and hold no slot): operands are visited heavier first
+  std::vector<int> su(nt, 0);
+  for (uint32_t r = 0; r < nt; ++r) {  // post-order again (acyclic now)
+    if (su[r]) continue;
+    st.push_back({(int)r, 0});
+    while (!st.empty()) {
+      const int v = st.back().first; const int k = st.back().second;
+      const rt_texture& t = desc->textures[v];
+      if (k < tex_n_ops(t.kind)) { ++st.back().second; const int u = tex_op(t, k); if (tex_comb(desc->textures[u].kind) && !su[u]) st.push_back({u, 0}); continue; }
+      st.pop_back();
+      if (!tex_comb(t.kind)) { su[v] = -1; continue; }  // (-1: a leaf, done)
+      int c[3] = {-8, -8, -8};  // (a leaf operand holds no slot)
+      for (int q = 0; q < tex_n_ops(t.kind); ++q) c[q] = su[tex_op(t, q)] > 0 ? su[tex_op(t, q)] : -8;
+      std::sort(c, c + 3, std::greater<int>());
+      su[v] = std::max(std::max(1, c[0]), std::max(c[1] + 1, c[2] + 2));
+    }
+  }
+  auto ordered_ops = [&](const rt_texture& t, int* o) {  // operand indices 0 .. n-1, heavier first (stable)
+    const int n = tex_n_ops(t.kind);
+    for (int q = 0; q < n; ++q) o[q] = q;
+    std::stable_sort(o, o + n, [&](int a, int b) { return std::max(su[tex_op(t, a)], 0) > std::max(su[tex_op(t, b)], 0); });
+    return n;
+  };
+  std::vector<int> seen(nt, -1), last(nt, -1), slot_of(nt, -1), order;
+  uint64_t total_words = 0;
+  for (uint32_t r = 0; r < nt; ++r) {
+    const rt_texture& root = desc->textures[r];
+    std::vector<int32_t> words;
+    int peak_slots = 0;
+    if (root.kind == RT_TEX_CHECKER_PLANAR) { const float* w = desc->images[root.image].texels; for (int k = 0; k < 8; ++k) { int32_t b; memcpy(&b, &w[k], 4); words.push_back(b); } }
+    if (root.kind == RT_TEX_FBM_MAPPED) { const float* w = desc->images[root.image].texels; for (int k = 0; k < 16; ++k) { int32_t b; memcpy(&b, &w[k], 4); words.push_back(b); } }
+    if (tex_comb(root.kind) && !tex_two_level(desc, (int)r)) {
+      words.resize(8, 0);
+      // the combinators of the graph in post-order, each once
+      order.clear();
+      st.push_back({(int)r, 0}); seen[r] = (int)r;
+      while (!st.empty()) {
+        const int v = st.back().first; const int k = st.back().second;
+        const rt_texture& t = desc->textures[v];
+        int o[3]; const int n = ordered_ops(t, o);
+        if (k < n) {
+          ++st.back().second;
+          const int u = tex_op(t, o[k]);
+          if (tex_comb(desc->textures[u].kind) && seen[u] != (int)r) { seen[u] = (int)r; st.push_back({u, 0}); }
+        } else { order.push_back(v); st.pop_back(); }
+      }
+      for (size_t j = 0; j < order.size(); ++j) {
+        const rt_texture& t = desc->textures[order[j]];
+        for (int q = 0; q < tex_n_ops(t.kind); ++q) last[tex_op(t, q)] = (int)j;
+      }
+      // value slots by linear scan: an operand's slot is free again once its last reader has read it
+      std::vector<char> busy(RT_TEX_SLOTS + 1, 0); int peak = 0;
+      words.push_back((int32_t)order.size());
+      for (size_t j = 0; j < order.size(); ++j) {
+        const rt_texture& t = desc->textures[order[j]];
+        int32_t ref[3] = {0, 0, 0};
+        for (int q = 0; q < tex_n_ops(t.kind); ++q) { const int u = tex_op(t, q); ref[q] = tex_comb(desc->textures[u].kind) ? -1 - slot_of[u] : u; }
+        for (int q = 0; q < tex_n_ops(t.kind); ++q) { const int u = tex_op(t, q); if (tex_comb(desc->textures[u].kind) && last[u] == (int)j) busy[slot_of[u]] = 0; }
+        int d = 0; while (d < RT_TEX_SLOTS && busy[d]) ++d;
+        if (d == RT_TEX_SLOTS) {  // count what it would need, for the message
+          int live = 0; for (size_t q = 0; q < j; ++q) if (last[order[q]] > (int)j) ++live;
+          peak = std::max(peak, live + 1);
+          return "texture " + std::to_string(r) + ": its graph needs at least " + std::to_string(peak) + " value slots, more than the " + std::to_string(RT_TEX_SLOTS) +
+                 " (RT_TEX_SLOTS) of the device evaluator";
+        }
+        busy[d] = 1; slot_of[order[j]] = d; peak = std::max(peak, d + 1); peak_slots = peak;
+        words.push_back(order[j]); words.push_back(d); words.push_back(ref[0]); words.push_back(ref[1]); words.push_back(ref[2]);
+      }
+    }
+    if (slots_of) slots_of->push_back(tex_comb(root.kind) && !tex_two_level(desc, (int)r) ? (int)peak_slots : 0);
+    if (words.empty()) { if (side_at) side_at->push_back(-1); continue; }
+    // every such root has a program over its whole sub-graph, so a chain of n nested combinators costs ~n^2 / 2 instructions: bounded here, by name
+    total_words += (words.size() + 11) / 12 * 12;
+    if (total_words > RT_TEX_PROGRAM_WORDS)
+      return "texture " + std::to_string(r) + ": the scene's texture programs would exceed " + std::to_string(RT_TEX_PROGRAM_WORDS) + " words (graphs nested that deep are not supported)";
+    if (side && side_at) {
+      side_at->push_back((int64_t)side->size());
+      side->insert(side->end(), words.begin(), words.end());
+      side->resize((side->size() + 11) / 12 * 12, 0);  // whole 48-byte records
+    }
+  }
   return "";
 }
 
 extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
   if (!desc || !out) return fail(RT_ERR_INVALID, "null argument");
+  std::vector<int32_t> tex_side; std::vector<int64_t> tex_side_at; std::vector<int> tex_slots;
+  { const std::string why = texture_programs(desc, &tex_side, &tex_side_at, &tex_slots); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   { const std::string why = fourier_desc_error(desc); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   if (!rt_device_available()) return fail(RT_ERR_NO_DEVICE, "no HIP device visible; this backend has no CPU fallback");
   if (desc->n_nodes == 0 || desc->n_tris == 0 || !desc->nodes || !desc->tri_p || !desc->tri_meta) return fail(RT_ERR_INVALID, "empty scene");
@@ -303,6 +462,13 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
         if ((m.flags & (k == 0 ? RT_TRI_HAS_ALPHA : RT_TRI_HAS_SHADOW_ALPHA)) && (desc->tri_alpha[2 * i + k] < 0 || (uint32_t)desc->tri_alpha[2 * i + k] >= desc->n_textures)) {
           delete s; return fail(RT_ERR_INVALID, "alpha texture out of range");
         }
+      for (int k = 0; k < 2; ++k) {
+        const int a = desc->tri_alpha[2 * i + k];
+        if ((m.flags & (k == 0 ? RT_TRI_HAS_ALPHA : RT_TRI_HAS_SHADOW_ALPHA)) && tex_slots[a] > RT_TEX_MASK_SLOTS) {
+          delete s; return fail(RT_ERR_UNSUPPORTED, "alpha texture " + std::to_string(a) + ": its graph needs " + std::to_string(tex_slots[a]) + " value slots, more than the " +
+                                                    std::to_string(RT_TEX_MASK_SLOTS) + " (RT_TEX_MASK_SLOTS) a mask has");
+        }
+      }
       s->general_prims = true; s->has_masks = true;
     }
   }
@@ -354,8 +520,10 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
     auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
     size_t total = 0;  // in float4 texels, levels padded to whole tiles
     uint64_t fourier_words = 0;
+    const std::vector<char> block = word_blocks(desc);
     for (uint32_t i = 0; i < desc->n_images; ++i) {
       const rt_image& im = desc->images[i];
+      if (im.n_levels == 0 && block[i]) continue;  // a mapped texture's word block: its words go to the texture side records (texture_programs)
       if (im.n_levels == 0) {  // a Fourier BSDF table (rtx_hip.h)
         uint64_t words = 0; (void)fourier_table_error(im, words);  // (checked by fourier_desc_error)
         fourier_at[i] = fourier_words; fourier_words += words;
@@ -377,6 +545,7 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
       DImage& d = himg[i];
       d.n_levels = im.n_levels; d.trilinear = im.trilinear; d.max_aniso = im.max_anisotropy; d.wrap = im.wrap;
       for (int l = 0; l < 16; ++l) { d.w[l] = 0; d.h[l] = 0; d.off[l] = 0; d.tshift[l] = 0; }
+      if (im.n_levels == 0 && block[i]) continue;
       if (im.n_levels == 0) {  // table words as they are; material_lobes finds them at fourier + off[0]
         const uint32_t* w = (const uint32_t*)im.texels;
         uint64_t words = 0; (void)fourier_table_error(im, words);
@@ -404,33 +573,17 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
     for (auto& d : himg) d.texels = s->texels.as<float4>();
     TRY_RC(upload(s->images, himg.data(), himg.size() * sizeof(DImage)));
   }
-  std::vector<DTexture> htex(desc->n_textures);
+  // the n_textures records, then the side records of the mapped textures and graph programs (texture_programs checked the table)
+  std::vector<DTexture> htex(desc->n_textures + tex_side.size() / 12);
   for (uint32_t i = 0; i < desc->n_textures; ++i) {
     const rt_texture& t = desc->textures[i]; DTexture& d = htex[i];
     d.kind = t.kind; d.v[0] = t.value[0]; d.v[1] = t.value[1]; d.v[2] = t.value[2];
     d.tex1 = t.tex1; d.tex2 = t.tex2; d.amount = t.amount; d.image = t.image;
     d.su = t.mapping[0]; d.sv = t.mapping[1]; d.du = t.mapping[2]; d.dv = t.mapping[3];
-    auto ok = [&](int id) { return id >= 0 && (uint32_t)id < desc->n_textures; };
-    const bool comb = t.kind == RT_TEX_SCALE || t.kind == RT_TEX_MIX || t.kind == RT_TEX_CHECKER;
-    if (t.kind < RT_TEX_CONST || t.kind > RT_TEX_FBM) { delete s; return fail(RT_ERR_INVALID, "unknown texture kind"); }
-    if (comb && (!ok(t.tex1) || !ok(t.tex2))) { delete s; return fail(RT_ERR_INVALID, "texture operand out of range"); }
-    if (t.kind == RT_TEX_MIX && !ok(t.amount)) { delete s; return fail(RT_ERR_INVALID, "mix amount out of range"); }
     if (t.kind == RT_TEX_IMAGE && (t.image < 0 || (uint32_t)t.image >= desc->n_images)) { delete s; return fail(RT_ERR_INVALID, "image index out of range"); }
+    if (tex_comb(t.kind) || tex_mapped(t.kind)) d.image = tex_side_at[i] < 0 ? -1 : (int)(desc->n_textures + tex_side_at[i] / 12);  // (tex_eval_q reads it)
   }
-  // combinators (scale / mix / checkerboard) nested deeper than two levels are not expanded on the device
-  auto is_comb = [&](int id) { int k = desc->textures[id].kind; return k == RT_TEX_SCALE || k == RT_TEX_MIX || k == RT_TEX_CHECKER; };
-  for (uint32_t i = 0; i < desc->n_textures; ++i) {
-    const rt_texture& t = desc->textures[i];
-    if (!is_comb((int)i)) continue;
-    if (t.kind == RT_TEX_MIX && is_comb(t.amount)) { delete s; return fail(RT_ERR_INVALID, "mix amount must be a leaf texture"); }
-    const int ops[2] = {t.tex1, t.tex2};
-    for (int k = 0; k < 2; ++k) {
-      const rt_texture& c = desc->textures[ops[k]];
-      if (!is_comb(ops[k])) continue;
-      if (c.kind == RT_TEX_MIX && is_comb(c.amount)) { delete s; return fail(RT_ERR_INVALID, "mix amount must be a leaf texture"); }
-      if (is_comb(c.tex1) || is_comb(c.tex2)) { delete s; return fail(RT_ERR_INVALID, "texture nesting deeper than 2"); }
-    }
-  }
+  if (!tex_side.empty()) memcpy(&htex[desc->n_textures], tex_side.data(), tex_side.size() * 4);
   TRY_RC(upload(s->textures, htex.data(), htex.size() * sizeof(DTexture)));
   std::vector<DMaterial> hmat(desc->n_materials);
   s->mat_kind.assign(desc->n_materials, 0); s->mat_table.assign(desc->n_materials, -1);
@@ -459,11 +612,12 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
       sig.push_back(t.kind);
       if (t.kind == RT_TEX_CONST) sig.push_back(t.value[0] == 0.0f ? 0 : 1);  // sigma == 0 (Lambert, not Oren-Nayar), roughness == 0 (specular lobes), ...
       if (t.kind == RT_TEX_IMAGE) { const rt_image& im = desc->images[t.image]; sig.push_back(im.trilinear ? 1 : 0); }
-      if (t.kind == RT_TEX_CHECKER) sig.push_back(t.amount);
-      if ((t.kind == RT_TEX_SCALE || t.kind == RT_TEX_MIX || t.kind == RT_TEX_CHECKER) && depth < 3) {
+      if (t.kind == RT_TEX_CHECKER || t.kind == RT_TEX_CHECKER_PLANAR) sig.push_back(t.amount);
+      if (tex_comb(t.kind) && depth < 3) {
         tex_sig(t.tex1, depth + 1, sig); tex_sig(t.tex2, depth + 1, sig);
         if (t.kind == RT_TEX_MIX) tex_sig(t.amount, depth + 1, sig);
-      }
+      } else if (tex_comb(t.kind)) sig.push_back(id);  // a graph deeper than that (only programs reach here): the sub-graph itself, not its shape
+
     };
     // an uber material whose opacity, Kr and Kt are constants with 1 - opacity, Kr and Kt black builds Lambert + microfacet reflection only (uber.rs:76-121)
     auto uber_two_lobes = [&](const rt_material& m) {
@@ -630,7 +784,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
 #endif
   for (uint32_t i = 0; i < desc->n_textures; ++i) {
     const rt_texture& t = desc->textures[i];
-    if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_FBM || (t.kind == RT_TEX_CHECKER && t.amount != 0)) d.needs_differentials = 1;
+    if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_FBM || t.kind == RT_TEX_FBM_MAPPED || ((t.kind == RT_TEX_CHECKER || t.kind == RT_TEX_CHECKER_PLANAR) && t.amount != 0))
+      d.needs_differentials = 1;
   }
   for (uint32_t i = 0; i < desc->n_materials; ++i) if (desc->materials[i].kind != RT_MAT_MIX && desc->materials[i].bump >= 0) d.needs_differentials = 1;  // bump() reads dudx..
   s->lambert_only = true;
@@ -940,6 +1095,28 @@ extern "C" int rt_fourier_eval(rt_scene* scene, int32_t material, uint64_t n, co
   hipLaunchKernelGGL(k_fourier_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, tab, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(), (unsigned long long)n, b[3].as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, b[3].p, n11, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+// rt_texture_eval: tex_eval_q, the texture evaluator of the shade kernels, bump maps and alpha masks, on hand-made records (15 floats, TexIn order)
+__global__ void k_texture_eval(const DTexture* __restrict__ textures, const DImage* __restrict__ images, int texture, const float* __restrict__ rec, unsigned long long n,
+                               float* __restrict__ out) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rec + 15 * i;
+  const rgb3 c = tex_eval_q(textures, images, texture, mk2(r[0], r[1]), r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11], r[12], r[13], r[14]);
+  out[3 * i] = c.r; out[3 * i + 1] = c.g; out[3 * i + 2] = c.b;
+}
+extern "C" int rt_texture_eval(rt_scene* scene, int32_t texture, uint64_t n, const float* records, float* rgb_out) {
+  if (!scene || !records || !rgb_out || n == 0) return fail(RT_ERR_INVALID, "bad rt_texture_eval arguments");
+  if (texture < 0 || texture >= scene->d.n_textures) return fail(RT_ERR_INVALID, "rt_texture_eval: texture out of range");
+  HIP_TRY(hipSetDevice(scene->device));
+  DevBuf b[2];
+  HIP_TRY(b[0].ensure((size_t)n * 60)); HIP_TRY(b[1].ensure((size_t)n * 12));
+  HIP_TRY(hipMemcpy(b[0].p, records, (size_t)n * 60, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_texture_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, scene->d.textures, scene->d.images, (int)texture, b[0].as<float>(),
+                     (unsigned long long)n, b[1].as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(rgb_out, b[1].p, (size_t)n * 12, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 extern "C" int rt_link_tables(const rt_scene_desc* desc, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats) {
@@ -1933,6 +2110,7 @@ struct rt_multi {
 };
 extern "C" int rt_multi_create(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices, rt_multi** out) {
   if (!desc || !devices || n_devices < 1 || !out) return fail(RT_ERR_INVALID, "bad rt_multi_create arguments");
+  { const std::string why = texture_programs(desc, nullptr, nullptr); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   { const std::string why = fourier_desc_error(desc); if (!why.empty()) return fail(RT_ERR_INVALID, why); }
   int n_visible = 0;
   if (hipGetDeviceCount(&n_visible) != hipSuccess || n_visible <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible; this backend has no CPU fallback");

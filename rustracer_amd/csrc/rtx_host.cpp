@@ -145,7 +145,8 @@ float filter_eval(int kind, const float prm[4], float x, float y) {
 struct MipLevels {
   int trilinear, wrap; float max_aniso;
   std::vector<int> w, h; std::vector<uint64_t> off; std::vector<float> texels;  // RGB
-  bool fourier = false;  // a Fourier BSDF table (rtxh_scene_add_fourier_table): no levels; `texels` holds its packed words (rtx_hip.h, rt_image)
+  bool fourier = false;  // a word block, no levels: `texels` holds packed words (rtx_hip.h, rt_image) - a Fourier BSDF table (rtxh_scene_add_fourier_table)
+  int words = 0;         // ... or, when > 0, the mapping of a texture (rtxh_scene_add_texture_mapped): its number of words
 };
 long modl(long a, long b) { long r = a % b; return r < 0 ? r + b : r; }
 // MIPMap::texel (mipmap.rs:208-225) on a finished level
@@ -1034,6 +1035,24 @@ int rtxh_scene_add_texture(rtxh_scene* s, int32_t kind, const float* v, int32_t 
   t.mapping[0] = mapping ? mapping[0] : 1.0f; t.mapping[1] = mapping ? mapping[1] : 1.0f; t.mapping[2] = mapping ? mapping[2] : 0.0f; t.mapping[3] = mapping ? mapping[3] : 0.0f;
   s->textures.push_back(t);
   return (int)s->textures.size() - 1;
+}
+int rtxh_scene_add_texture_mapped(rtxh_scene* s, int32_t kind, const float* v, int32_t tex1, int32_t tex2, int32_t amount, const float* words, int32_t n_words) {
+  if (!s || !v || !words || n_words < 1 || (kind != RT_TEX_CHECKER_PLANAR && kind != RT_TEX_FBM_MAPPED)) return fail(RT_ERR_INVALID, "bad mapped texture arguments");
+  MipLevels m; m.trilinear = 0; m.wrap = 0; m.max_aniso = 0.0f; m.fourier = true; m.words = n_words;
+  m.texels.assign((size_t)(n_words + 2) / 3 * 3, 0.0f);  // whole texels, zero-padded
+  memcpy(m.texels.data(), words, (size_t)n_words * 4);
+  s->mips.push_back(std::move(m));
+  s->committed = false;
+  return rtxh_scene_add_texture(s, kind, v, tex1, tex2, amount, (int)s->mips.size() - 1, nullptr);
+}
+int rtxh_texture_words(rtxh_scene* s, int32_t texture, float* out, int32_t capacity) {
+  if (!s || texture < 0 || (size_t)texture >= s->textures.size()) return fail(RT_ERR_INVALID, "bad texture index");
+  const rt_texture& t = s->textures[texture];
+  if (t.kind != RT_TEX_CHECKER_PLANAR && t.kind != RT_TEX_FBM_MAPPED) return 0;
+  if (t.image < 0 || (size_t)t.image >= s->mips.size() || !s->mips[t.image].words) return 0;
+  const MipLevels& m = s->mips[t.image];
+  if (out) memcpy(out, m.texels.data(), (size_t)std::min(capacity, m.words) * 4);
+  return m.words;
 }
 int rtxh_scene_add_material(rtxh_scene* s, int32_t kind, const int32_t* slots, int32_t remap, int32_t bump) {
   if (!s || !slots) return fail(RT_ERR_INVALID, "bad material arguments");

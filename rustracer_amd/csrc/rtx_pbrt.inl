@@ -32,6 +32,11 @@ struct PbrtParams {
     if (p && p->nums.size() >= 3) { out[0] = p->nums[0]; out[1] = p->nums[1]; out[2] = p->nums[2]; return true; }
     return false;
   }
+  bool one_vector(const std::string& n, float out[3]) const {  // find_one_vector3f (paramset.rs)
+    const PbrtParam* p = find(n, {"vector3", "vector"});
+    if (p && p->nums.size() >= 3) { out[0] = p->nums[0]; out[1] = p->nums[1]; out[2] = p->nums[2]; return true; }
+    return false;
+  }
   bool one_point(const std::string& n, float out[3]) const {
     const PbrtParam* p = find(n, {"point3", "point", "vector3", "vector"});
     if (p && p->nums.size() >= 3) { out[0] = p->nums[0]; out[1] = p->nums[1]; out[2] = p->nums[2]; return true; }
@@ -240,7 +245,15 @@ struct PbrtLoader {
     const bool is_float = type == "float";
     if (!is_float && type != "color" && type != "spectrum") { warn("texture type unknown"); return true; }
     const PbrtParams none;
-    const float map[4] = {p.one_float("uscale", 1.0f), p.one_float("vscale", 1.0f), p.one_float("udelta", 0.0f), p.one_float("vdelta", 0.0f)};
+    float map[4] = {p.one_float("uscale", 1.0f), p.one_float("vscale", 1.0f), p.one_float("udelta", 0.0f), p.one_float("vdelta", 0.0f)};
+    // a 2D mapping name the reference does not know: it logs an error and uses UVMapping2D(1, 1, 0, 0) (checkerboard.rs:73-76, uv.rs:35-38)
+    auto unknown_mapping = [&]() {
+      const std::string m = p.one_string("mapping", "uv");
+      if (m == "uv" || m == "spherical" || m == "cylindrical" || m == "planar") return false;
+      warn("2D texture mapping \"" + m + "\" unknown; using uv (1, 1, 0, 0)");
+      map[0] = map[1] = 1.0f; map[2] = map[3] = 0.0f;
+      return true;
+    };
     const float zero3[3] = {0, 0, 0};
     auto tex = [&](const std::string& n, float d) { return is_float ? float_texture(p, none, n, d) : spectrum_texture(p, none, n, d, d, d); };
     auto uv_mapping_only = [&]() { return p.one_string("mapping", "uv") == "uv"; };
@@ -263,16 +276,28 @@ struct PbrtLoader {
       if (mip < 0) return fail_(rtxh_last_error());
       id = rtxh_scene_add_texture(scene, RT_TEX_IMAGE, zero3, -1, -1, -1, mip, map);
     } else if (cls == "checkerboard" && !is_float) {  // checkerboard.rs:44-95
-      if (p.one_int("dimension", 2) != 2 || !uv_mapping_only()) return fail_("checkerboard: only dimension 2 with \"uv\" mapping is supported");
+      if (p.one_int("dimension", 2) != 2) return fail_("checkerboard: only dimension 2 is supported (the reference has unimplemented!() for 3D checkerboards)");
+      const std::string mapping = p.one_string("mapping", "uv");
+      if (mapping == "spherical" || mapping == "cylindrical") return fail_("checkerboard: \"" + mapping + "\" mapping is not supported (the reference has unimplemented!() there)");
       const std::string aa = p.one_string("aamode", "closedform");
-      id = rtxh_scene_add_texture(scene, RT_TEX_CHECKER, zero3, spectrum_texture(p, none, "tex1", 1, 1, 1), spectrum_texture(p, none, "tex2", 0, 0, 0), aa == "none" ? 0 : 1, -1, map);
+      const int t1 = spectrum_texture(p, none, "tex1", 1, 1, 1), t2 = spectrum_texture(p, none, "tex2", 0, 0, 0);
+      if (mapping == "planar") {  // PlanarMapping2D (texture/mod.rs:63-85): v1, v2 as find_vector3f reads them, udelta / vdelta the offsets; uscale / vscale play no part
+        float w[8] = {1, 0, 0, 0, 1, 0, p.one_float("udelta", 0.0f), p.one_float("vdelta", 0.0f)};
+        p.one_vector("v1", w); p.one_vector("v2", w + 3);
+        id = rtxh_scene_add_texture_mapped(scene, RT_TEX_CHECKER_PLANAR, zero3, t1, t2, aa == "none" ? 0 : 1, w, 8);
+      } else {
+        unknown_mapping();
+        id = rtxh_scene_add_texture(scene, RT_TEX_CHECKER, zero3, t1, t2, aa == "none" ? 0 : 1, -1, map);
+      }
     } else if (cls == "uv" && !is_float) {
-      if (!uv_mapping_only()) return fail_("uv texture: only \"uv\" mapping is implemented (as in the reference)");
+      if (!unknown_mapping() && !uv_mapping_only()) return fail_("uv texture: only \"uv\" mapping is implemented (as in the reference)");
       id = rtxh_scene_add_texture(scene, RT_TEX_UV, zero3, -1, -1, -1, -1, map);
-    } else if (cls == "fbm") {  // fbm.rs:25-44; the reference stores the CTM as world-to-texture (texture/mod.rs:96-100): identity only here
-      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) if (ctm.m.a[r][c] != (r == c ? 1.0f : 0.0f)) return fail_("fbm texture under a non-identity transform is not supported");
+    } else if (cls == "fbm") {  // fbm.rs:25-44 over IdentityMapping3D, which keeps the CTM at this directive as its world_to_texture (texture/mod.rs:96-101)
+      bool identity = true;
+      for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) if (ctm.m.a[r][c] != (r == c ? 1.0f : 0.0f)) identity = false;
       const float v[3] = {p.one_float("omega", 0.5f), 0, 0};
-      id = rtxh_scene_add_texture(scene, RT_TEX_FBM, v, -1, -1, p.one_int("octaves", 8), -1, map);
+      if (identity) id = rtxh_scene_add_texture(scene, RT_TEX_FBM, v, -1, -1, p.one_int("octaves", 8), -1, map);
+      else id = rtxh_scene_add_texture_mapped(scene, RT_TEX_FBM_MAPPED, v, -1, -1, p.one_int("octaves", 8), &ctm.m.a[0][0], 16);
     } else return fail_("texture class \"" + cls + "\" is not supported");
     if (id < 0) return fail_(rtxh_last_error());
     (is_float ? gs.float_textures : gs.spectrum_textures)[name] = id;

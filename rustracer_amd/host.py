@@ -206,6 +206,10 @@ class HostScene:
             h, w = m.data.shape[:2]
             _check(L.rtxh_scene_add_mipmap(self.h, w, h, _p(m.data), int(m.trilinear), C.c_float(m.max_aniso), m.wrap), "add_mipmap")
         for t in desc.textures:
+            if getattr(t, "words", None) is not None:  # TEX_CHECKER_PLANAR / TEX_FBM_MAPPED: the word block becomes an image the texture names
+                w = np.ascontiguousarray(t.words, np.float32)
+                _check(L.rtxh_scene_add_texture_mapped(self.h, t.kind, _p(np.float32(t.value)), t.tex1, t.tex2, t.amount, _p(w), w.size), "add_texture_mapped")
+                continue
             _check(L.rtxh_scene_add_texture(self.h, t.kind, _p(np.float32(t.value)), t.tex1, t.tex2, t.amount, t.mip, _p(np.float32(t.mapping))), "add_texture")
         for m in desc.materials:
             _check(L.rtxh_scene_add_material(self.h, m.kind, _p(m.slots(), C.c_int32), int(m.remap_roughness), int(m.bump)), "add_material")
@@ -389,6 +393,33 @@ class HostScene:
         if rc != 0:
             raise BackendError(f"rt_fourier_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
         return dict(f=out[:, 0:3], pdf=out[:, 3], sf=out[:, 4:7], swi=out[:, 7:10], spdf=out[:, 10])
+
+    def texture_eval(self, tex, uv, p=None, duv=None, dpdx=None, dpdy=None):
+        """Texture::evaluate of texture `tex` through the device evaluator of the shade kernels (rt_texture_eval), vectorised over records with the argument
+        names of OracleScene.tex_probe: uv (n, 2), p (n, 3), duv (n, 4) = dudx dvdx dudy dvdy, dpdx / dpdy (n, 3); omitted ones are zero. Returns (n, 3) float32.
+        Uploads the scene first if need be."""
+        uv = np.asarray(uv, np.float32).reshape(-1, 2)
+        n = uv.shape[0]
+        col = lambda v, w: np.zeros((n, w), np.float32) if v is None else np.broadcast_to(np.asarray(v, np.float32).reshape(-1, w), (n, w))
+        rec = np.ascontiguousarray(np.concatenate([uv, col(duv, 4), col(p, 3), col(dpdx, 3), col(dpdy, 3)], axis=1), np.float32)
+        dev = C.c_void_p()
+        _check(lib().rtxh_scene_device(self.h, C.byref(dev)), "scene_device")
+        out = np.zeros((n, 3), np.float32)
+        if n == 0:
+            return out
+        rc = hip_lib().rt_texture_eval(dev, C.c_int32(tex), C.c_uint64(n), _p(rec), _p(out))
+        if rc != 0:
+            raise BackendError(f"rt_texture_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+        return out
+
+    def texture_words(self, tex):
+        """The word block of texture `tex` as the host holds it (float32), or an empty array for a texture that names none."""
+        L = lib()
+        n = _check(L.rtxh_texture_words(self.h, int(tex), None, 0), "texture_words")
+        out = np.zeros(n, np.float32)
+        if n:
+            L.rtxh_texture_words(self.h, int(tex), _p(out), n)
+        return out
 
     def trace(self, rays, any_hit=False, count=True):
         """count=True: the visit-counting kernels (one node per step, the reference's sequence); count=False: the

@@ -106,11 +106,22 @@ class _Writer:
             if typ == _F:
                 raise ValueError("the reference has no float uv texture")
             body = f'"uv" {mapping}'
-        elif t.kind == sd.TEX_FBM:
+        elif t.kind == sd.TEX_CHECKER_PLANAR:
+            if typ == _F:
+                raise ValueError("the reference has no float checkerboard (api.rs:1201-1216)")
+            w = t.words
+            body = (f'"checkerboard" {self.param("tex1", t.tex1, _S)} {self.param("tex2", t.tex2, _S)} "string aamode" "{"none" if t.amount == 0 else "closedform"}" '
+                    f'"string mapping" "planar" "vector v1" [{_nums(w[0:3])}] "vector v2" [{_nums(w[3:6])}] "float udelta" [{_n(w[6])}] "float vdelta" [{_n(w[7])}]')
+        elif t.kind in (sd.TEX_FBM, sd.TEX_FBM_MAPPED):
             body = f'"fbm" "float omega" [{_n(t.value[0])}] "integer octaves" [{int(t.amount)}]'
         else:
             raise ValueError(f"texture kind {t.kind}")
-        self.out.append(f'Texture "{name}" "{"float" if typ == _F else "spectrum"}" {body}')
+        line = f'Texture "{name}" "{"float" if typ == _F else "spectrum"}" {body}'
+        if t.kind == sd.TEX_FBM_MAPPED:  # the CTM at the directive is the mapping's matrix; TransformBegin keeps the texture's name in the graphics state
+            m = np.asarray(t.words, np.float32).reshape(4, 4)
+            self.out += ["TransformBegin", f"  Transform [{_nums(m.T)}]", "  " + line, "TransformEnd"]  # column-major in the file (api.rs:596-600)
+        else:
+            self.out.append(line)
         self.tex_names[key] = name
         return name
 

@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 # --- enums shared (by value) with include/rtx_hip.h and oracle/ -------------------------------
-TEX_CONST, TEX_SCALE, TEX_MIX, TEX_IMAGE, TEX_CHECKER, TEX_UV, TEX_FBM = 0, 1, 2, 3, 4, 5, 6
+TEX_CONST, TEX_SCALE, TEX_MIX, TEX_IMAGE, TEX_CHECKER, TEX_UV, TEX_FBM, TEX_CHECKER_PLANAR, TEX_FBM_MAPPED = 0, 1, 2, 3, 4, 5, 6, 7, 8
 (MAT_MATTE, MAT_PLASTIC, MAT_METAL, MAT_MIRROR, MAT_GLASS, MAT_UBER, MAT_SUBSTRATE, MAT_MIX,
  MAT_TRANSLUCENT, MAT_DISNEY, MAT_FOURIER) = range(11)
 LIGHT_DIFFUSE_AREA, LIGHT_POINT, LIGHT_DISTANT, LIGHT_INFINITE = 0, 1, 2, 3
@@ -45,6 +45,7 @@ class Texture:
     amount: int = -1
     mip: int = -1
     mapping: Sequence[float] = (1.0, 1.0, 0.0, 0.0)  # su sv du dv (rc/texture/mod.rs:38-61)
+    words: Optional[Sequence[float]] = None  # the word block of TEX_CHECKER_PLANAR (v1 v2 udelta vdelta) / TEX_FBM_MAPPED (row-major 4 x 4 matrix)
 
 
 @dataclass
@@ -215,16 +216,29 @@ class SceneDesc:
         self.textures.append(Texture(TEX_IMAGE, mip=mip, mapping=(su, sv, du, dv)))
         return len(self.textures) - 1
 
-    def checker_tex(self, t1, t2, su=1.0, sv=1.0, du=0.0, dv=0.0, aa="closedform") -> int:  # checkerboard.rs:44-95 (dimension 2, "uv" mapping)
-        self.textures.append(Texture(TEX_CHECKER, tex1=self._t(_f(t1)), tex2=self._t(_f(t2)), amount=0 if aa == "none" else 1, mapping=(su, sv, du, dv)))
+    def checker_tex(self, t1, t2, su=1.0, sv=1.0, du=0.0, dv=0.0, aa="closedform", mapping="uv", v1=(1.0, 0.0, 0.0), v2=(0.0, 1.0, 0.0), udelta=0.0,
+                    vdelta=0.0) -> int:  # checkerboard.rs:44-95 (dimension 2)
+        """mapping="uv": UVMapping2D(su, sv, du, dv); mapping="planar": PlanarMapping2D(v1, v2, udelta, vdelta) (texture/mod.rs:63-85; su .. dv unused)."""
+        assert mapping in ("uv", "planar")
+        a, b, aa = self._t(_f(t1)), self._t(_f(t2)), 0 if aa == "none" else 1
+        if mapping == "planar":
+            words = tuple(float(x) for x in tuple(v1) + tuple(v2) + (udelta, vdelta))
+            self.textures.append(Texture(TEX_CHECKER_PLANAR, tex1=a, tex2=b, amount=aa, words=words))
+        else:
+            self.textures.append(Texture(TEX_CHECKER, tex1=a, tex2=b, amount=aa, mapping=(su, sv, du, dv)))
         return len(self.textures) - 1
 
     def uv_tex(self, su=1.0, sv=1.0, du=0.0, dv=0.0) -> int:  # uv.rs:21-40
         self.textures.append(Texture(TEX_UV, mapping=(su, sv, du, dv)))
         return len(self.textures) - 1
 
-    def fbm_tex(self, omega=0.5, octaves=8) -> int:  # fbm.rs:25-44 (identity texture-to-world)
-        self.textures.append(Texture(TEX_FBM, value=(float(omega), 0.0, 0.0), amount=int(octaves)))
+    def fbm_tex(self, omega=0.5, octaves=8, tex2world=None) -> int:  # fbm.rs:25-44
+        """tex2world: the 4 x 4 CTM at the Texture directive (IdentityMapping3D applies it to the hit point, texture/mod.rs:92-115); None = identity."""
+        if tex2world is None:
+            self.textures.append(Texture(TEX_FBM, value=(float(omega), 0.0, 0.0), amount=int(octaves)))
+        else:
+            m = np.asarray(tex2world, np.float32).reshape(4, 4)
+            self.textures.append(Texture(TEX_FBM_MAPPED, value=(float(omega), 0.0, 0.0), amount=int(octaves), words=tuple(float(x) for x in m.ravel())))
         return len(self.textures) - 1
 
     def _t(self, v) -> int:
