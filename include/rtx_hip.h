@@ -372,6 +372,40 @@ int rt_fourier_eval(rt_scene* scene, int32_t material, uint64_t n, const float* 
  * parity tests. */
 int rt_texture_eval(rt_scene* scene, int32_t texture, uint64_t n, const float* records, float* rgb_out);
 
+/* The Bsdf a material builds, on n queries: Material::compute_scattering_functions (TransportMode::Radiance, allow_multiple_lobes = true as path.rs:145
+ * passes it) of material `material` at a surface point, then Bsdf::f(wo, wi, ALL), Bsdf::pdf(wo, wi, ALL) and Bsdf::sample_f(wo, u, ALL)
+ * (rc/bsdf/mod.rs:94-251) - run by the front-end structs of the shade kernels themselves (textures, bump maps, mix materials and Fourier tables apply).
+ * wo, wi: n x 3 floats, WORLD space, as the integrator passes them; u: n x 2. out: n x RT_BSDF_OUT_FLOATS -
+ *   f rgb, pdf, then of sample_f: f rgb, wi xyz (world), pdf, the sampled lobe's type flags (BxDFType bits, as a float), and the number of lobes of the Bsdf.
+ * surface: NULL = the canonical hit for every query (p = 0, n = shading n = +z, dpdu = shading dpdu = +x, dpdv = shading dpdv = +y, uv = (0.5, 0.5), every
+ * differential zero), or n x RT_BSDF_SURFACE_FLOATS floats of SurfaceInteraction in the order
+ *   p.xyz, n.xyz (geometric), shading n.xyz, dpdu.xyz, dpdv.xyz, shading dpdu.xyz, shading dpdv.xyz, dndu.xyz, dndv.xyz, u v, dudx dvdx dudy dvdy,
+ *   dpdx.xyz, dpdy.xyz, flip
+ * flip != 0: the primitive's reverse_orientation ^ transform_swaps_handedness (read by bump maps only: set_shading_geometry, interaction.rs:218-242).
+ * dndu / dndv are carried for completeness and read as zero: every bump-mapped primitive of the backend is a triangle, whose dndu / dndv are zero
+ * (mesh.rs:372-382). The first axis of Bsdf::new's frame is normalize(shading dpdu), as the per-triangle shade records hold it.
+ * front_end: which front-end of the shade kernels builds and evaluates the Bsdf. RT_BSDF_FRONT_AUTO - the one rt_render sends a camera-ray vertex of this
+ * material to (the constant-texture forms where a frame uses them); RT_BSDF_FRONT_GENERIC - the tagged-lobe aggregate, valid for every material;
+ * RT_BSDF_FRONT_LAMBERT / _TWO_LOBE / _TWO_LOBE_WIDE - the register-resident front-ends, refused with RT_ERR_INVALID for a material whose class they do not
+ * serve. One lane per query; host pointers. n up to 2^31 - 1 queries per call. */
+enum { RT_BSDF_FRONT_AUTO = 0, RT_BSDF_FRONT_GENERIC = 1, RT_BSDF_FRONT_LAMBERT = 2, RT_BSDF_FRONT_TWO_LOBE = 3, RT_BSDF_FRONT_TWO_LOBE_WIDE = 4 };
+#define RT_BSDF_SURFACE_FLOATS 40
+#define RT_BSDF_OUT_FLOATS 13
+int rt_bsdf_eval(rt_scene* scene, int32_t material, int32_t front_end, uint64_t n, const float* surface, const float* wo, const float* wi, const float* u,
+                 float* out);
+
+/* The radiance of every sample of a pixel window: the frame of rt_render (same batches, passes, kernels and queues) for the pixels of path->pixel_bounds
+ * intersected with the film's sample bounds, handed back unfiltered. radiance: n_pixels x spp x 4 floats, pixels row-major in that window, sample index s =
+ * the pixel-keyed sampler's index: L rgb exactly as PathIntegrator::li returned it - before the renderer's scrubbing and the max_sample_luminance clamp -
+ * and 1.0 in the fourth float where renderer.rs:115-126 scrubs the sample (NaN, negative or infinite luminance), else 0.0. p_film (may be NULL): n_pixels x
+ * spp x 2, the samples' film positions. spp is rounded up to a power of two as in rt_render and sizes the outputs. A window of more than
+ * RT_SAMPLES_MAX (2^27) samples - 2 GiB of radiance and 1 GiB of film positions - is refused with RT_ERR_INVALID before any device work; so are an empty
+ * window, RT_FLAG_REF_STREAM and a NULL radiance. RT_FLAG_FILM_ON_DEVICE: both outputs are device pointers. RT_FLAG_COUNT_TRAVERSAL and RT_FLAG_TIME_KERNELS
+ * as in rt_render (ms_film: the kernel that moves the samples out). Single device. */
+#define RT_SAMPLES_MAX 134217728
+int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                      uint32_t flags, void* stream, float* radiance, float* p_film, rt_stats* stats);
+
 /* Dense voxel light distribution of SpatialLightDistribution (rc/lightdistrib.rs:101-179):
  * n_voxels[3]; func: nvox*n_lights, cdf: nvox*(n_lights+1), func_int: nvox (host pointers, may be NULL
  * to query n_voxels only). */
@@ -383,7 +417,9 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
        RT_QUERY_LDS_OCCLUSION = 2 /* 1 if the scene is too large for RT_QUERY_LDS_RESIDENT but fits ONE workgroup's 160 KB per CU (<= 2816 nodes, <= 1408 plain triangles): occlusion rays walk an LDS copy of it, closest-hit rays its bounds and link tables;
                                       RT_QUERY_LDS_NODES_TESTED then counts the occlusion walk's nodes */,
        RT_QUERY_SHADOW_PAIRS = 3 /* shadow sets (rt_shadow_sets): voxel / light pairs of the voxels a surface reaches; 0 where the scene has none */,
-       RT_QUERY_SHADOW_EMPTY = 4 /* ... of them EMPTY: no shadow segment of the pair can be occluded */ };
+       RT_QUERY_SHADOW_EMPTY = 4 /* ... of them EMPTY: no shadow segment of the pair can be occluded */,
+       RT_QUERY_BSDF_LAUNCHED = 5 /* the kernel the scene's last rt_bsdf_eval launched: 1 + 2 * mode + const_tex (mode 0 generic, 3 Lambert, 5 two-lobe, 6 two-lobe wide;
+                                     const_tex 1: its constant-texture form), 0 before the first call */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

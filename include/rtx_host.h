@@ -140,6 +140,11 @@ int rtxh_look_at(const float* pos, const float* look, const float* up, float* m1
 /* renderer::render through the HIP backend. film_xyzw: (y1-y0)*(x1-x0)*4 floats over the cropped pixel bounds
  * (host pointer, or device pointer with RT_FLAG_FILM_ON_DEVICE). */
 int rtxh_render(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* film_xyzw, rt_stats* stats);
+/* The same frame's samples, unfiltered (rt_render_samples in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render; the window is the
+ * integrator's pixel bounds ("pixelbounds" intersected with the film's sample bounds; the sample bounds themselves without it), (wy1-wy0)*(wx1-wx0) pixels
+ * row-major. radiance: pixels x spp x 4 floats (spp rounded up to a power of two), p_film: pixels x spp x 2 or NULL; host pointers, or device pointers with
+ * RT_FLAG_FILM_ON_DEVICE. rank / world_size of the parameters are ignored. */
+int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* radiance, float* p_film, rt_stats* stats);
 /* The same frame on several GPUs of this process (rt_multi_* in rtx_hip.h): the scene is replicated on `devices` (kept for later calls with the
  * same list), host threads pull chunks of tile rows, the film is gathered on devices[0] and returned in host memory (or in memory of devices[0]
  * with RT_FLAG_FILM_ON_DEVICE). rank / world_size of the parameters are ignored. */

@@ -104,6 +104,10 @@ struct rt_scene {
   // per-render workspace
   DevBuf ws[32];
   DevBuf film_acc, own_acc, film_out, counters, stats, filter_table, ref_samples, ref_stack;
+  DevBuf samples_rad, samples_pf;  // rt_render_samples with host outputs: [window pixel][sample] radiance (float4) and film position (float2)
+  DevBuf bsdf_self, bsdf_tris;     // rt_bsdf_eval: a copy of `d` whose tri_p names two primitive records that carry nothing but the orientation flag (0, 1) - what a bump map reads of si.prim
+  int bsdf_launched = -1;          // rt_bsdf_eval: 2 * mode + const_tex of the k_bsdf_eval instantiation the last call launched (RT_QUERY_BSDF_LAUNCHED)
+  std::vector<int> mat_class;      // per material: its code class (DMaterial::code_class) - the front-end ranges of rt_render, for rt_bsdf_eval
   DevBuf bin_words, bin_sorted, bin_at;  // material binning of the shade queue (generic shade path); bin_at: u16 per queue entry
   unsigned n_materials = 0, n_code_classes = 0, n_lambert_classes = 0, n_small_classes = 0, n_wide_classes = 0;
   // sampler tables are double-buffered: K0 of batch b+1 runs on aux_stream under the path kernels of batch b
@@ -681,6 +685,8 @@ extern "C" int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene**
     s->n_wide_classes = (unsigned)next - s->n_lambert_classes - s->n_small_classes;
     for (size_t c = 0; c < classes.size(); ++c) if (!lambert[c] && !small[c] && !wide[c]) remap[c] = next++;
     for (uint32_t i = 0; i < desc->n_materials; ++i) hmat[i].code_class = remap[hmat[i].code_class];
+    s->mat_class.resize(desc->n_materials);
+    for (uint32_t i = 0; i < desc->n_materials; ++i) s->mat_class[i] = hmat[i].code_class;
   }
   TRY_RC(upload(s->materials, hmat.data(), hmat.size() * sizeof(DMaterial)));
   {  // per primitive: the code class of its material (bit 15: a quadric) - what the vertex queue is binned by (k_bin_count), ONE two-byte gather instead of the primitive's
@@ -1119,6 +1125,83 @@ extern "C" int rt_texture_eval(rt_scene* scene, int32_t texture, uint64_t n, con
   HIP_TRY(hipMemcpy(rgb_out, b[1].p, (size_t)n * 12, hipMemcpyDeviceToHost));
   return RT_OK;
 }
+// Which shade launches a frame of this scene makes: decided in ONE place for the frame loop (render_frame) and for rt_bsdf_eval's RT_BSDF_FRONT_AUTO.
+struct ShadeRoute {
+  bool use_bins;       // the vertex queue is binned by code class (several classes, not a Lambert scene; one class: every vertex runs the same code, the queue order is kept)
+  bool qlights;        // QLIGHTS forms on the front-end ranges, quadric hits in a generic bin of their own
+  bool split_classes;  // the class ranges of the binned queue go to their front-ends
+  unsigned n_first, n_second, n_third;  // classes of k_shade<3>, <5>, <6>; RTX_SHADE_SPLIT (measurement knob): 0 = every class through the generic front-end, 1 = Lambert classes apart, default = Lambert and two-lobe classes apart
+  bool const_form;     // the register-resident launches are constant-texture forms (launch_shade_t picks the QLIGHTS form first, then GENERAL, then LEAN)
+};
+static ShadeRoute shade_route(const rt_scene* s) {
+  ShadeRoute r;
+  r.use_bins = !s->lambert_materials && s->n_code_classes > 1;
+  r.qlights = s->d.route_quadric_hits != 0 && r.use_bins;
+  const int split_mode = env_int("RTX_SHADE_SPLIT", 2);
+  r.n_first = split_mode >= 1 ? s->n_lambert_classes : 0u; r.n_second = split_mode >= 2 ? s->n_small_classes : 0u; r.n_third = split_mode >= 2 ? s->n_wide_classes : 0u;
+  r.split_classes = r.use_bins && (r.n_first + r.n_second + r.n_third) > 0 && r.n_first + r.n_second + r.n_third < RT_BIN_MAX;
+  r.const_form = r.qlights || (!s->masked_emitters && s->lean_shade);
+  return r;
+}
+// rt_bsdf_eval: which front-end of k_shade rt_render sends a camera-ray vertex of `material` to (mode 0 / 3 / 5 / 6 and whether its constant-texture form): k_shade<1> for
+// constant-matte scenes under area lights, k_shade<3> for Lambert scenes, the class ranges of the binned queue otherwise (shade_route). want: RT_BSDF_FRONT_AUTO or an
+// explicit front-end, which must serve the material's class. Called with the scene's render_mutex held.
+static int bsdf_front_end(const rt_scene* s, int material, int want, int& mode, bool& const_tex) {
+  const ShadeRoute r = shade_route(s);
+  const unsigned c = (unsigned)s->mat_class[material];
+  const unsigned nl = s->n_lambert_classes, ns = s->n_small_classes, nw = s->n_wide_classes;
+  const int served = c < nl ? 3 : (c < nl + ns ? 5 : (c < nl + ns + nw ? 6 : 0));  // the register-resident front-end that serves the class (0: none)
+  if (want == RT_BSDF_FRONT_GENERIC) { mode = 0; const_tex = false; return RT_OK; }
+  if (want == RT_BSDF_FRONT_AUTO) {
+    if (s->lambert_only) { mode = 3; const_tex = true; return RT_OK; }
+    if (s->lambert_materials) { mode = 3; const_tex = r.const_form; return RT_OK; }
+    mode = !r.split_classes ? 0 : (c < r.n_first ? 3 : (c < r.n_first + r.n_second ? 5 : (c < r.n_first + r.n_second + r.n_third ? 6 : 0)));
+    const_tex = mode != 0 && r.const_form;
+    return RT_OK;
+  }
+  const int asked = want == RT_BSDF_FRONT_LAMBERT ? 3 : (want == RT_BSDF_FRONT_TWO_LOBE ? 5 : (want == RT_BSDF_FRONT_TWO_LOBE_WIDE ? 6 : -1));
+  if (asked < 0) return fail(RT_ERR_INVALID, "rt_bsdf_eval: unknown front_end");
+  if (asked != served) {
+    static const char* const names[7] = {"the generic front-end only", "", "", "RT_BSDF_FRONT_LAMBERT", "", "RT_BSDF_FRONT_TWO_LOBE", "RT_BSDF_FRONT_TWO_LOBE_WIDE"};
+    return fail(RT_ERR_INVALID, std::string("rt_bsdf_eval: material ") + std::to_string(material) + " is not of a class this front-end serves (its class is served by " + names[served] + ")");
+  }
+  mode = asked; const_tex = s->lambert_only || r.const_form;  // (both mean: every texture of the scene is a constant)
+  return RT_OK;
+}
+extern "C" int rt_bsdf_eval(rt_scene* scene, int32_t material, int32_t front_end, uint64_t n, const float* surface, const float* wo, const float* wi, const float* u, float* out) {
+  if (!scene || !wo || !wi || !u || !out || n == 0) return fail(RT_ERR_INVALID, "bad rt_bsdf_eval arguments");
+  if (n > 0x7fffffffull) return fail(RT_ERR_INVALID, "rt_bsdf_eval: more than 2^31 - 1 queries in one call");
+  if (material < 0 || (size_t)material >= scene->mat_class.size()) return fail(RT_ERR_INVALID, "rt_bsdf_eval: material out of range");
+  std::lock_guard<std::mutex> lock(scene->render_mutex);  // (a first frame rewrites the scene record)
+  int mode = 0; bool const_tex = false;
+  { const int rc = bsdf_front_end(scene, material, front_end, mode, const_tex); if (rc != RT_OK) return rc; }
+  HIP_TRY(hipSetDevice(scene->device));
+  // the scene record with two stand-in primitives in place of the triangles: all a material reads of its primitive is the orientation flag (bump_map)
+  DScene d = scene->d;
+  {
+    float4 tris[6]; memset(tris, 0, sizeof(tris));
+    const unsigned one = 1u; memcpy(&tris[5].w, &one, 4);
+    HIP_TRY(scene->bsdf_tris.ensure(sizeof(tris))); HIP_TRY(scene->bsdf_self.ensure(sizeof(DScene)));
+    HIP_TRY(hipMemcpy(scene->bsdf_tris.p, tris, sizeof(tris), hipMemcpyHostToDevice));
+    d.tri_p = scene->bsdf_tris.as<float4>(); d.n_tris = 2; d.self = scene->bsdf_self.as<DScene>();
+    HIP_TRY(hipMemcpy(scene->bsdf_self.p, &d, sizeof(DScene), hipMemcpyHostToDevice));
+  }
+  DevBuf b[5];
+  const size_t n3 = (size_t)n * 12, n2 = (size_t)n * 8, ns = (size_t)n * RT_BSDF_SURFACE_FLOATS * 4, no = (size_t)n * RT_BSDF_OUT_FLOATS * 4;
+  HIP_TRY(b[0].ensure(n3)); HIP_TRY(b[1].ensure(n3)); HIP_TRY(b[2].ensure(n2)); HIP_TRY(b[3].ensure(no));
+  HIP_TRY(hipMemcpy(b[0].p, wo, n3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b[1].p, wi, n3, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b[2].p, u, n2, hipMemcpyHostToDevice));
+  if (surface) { HIP_TRY(b[4].ensure(ns)); HIP_TRY(hipMemcpy(b[4].p, surface, ns, hipMemcpyHostToDevice)); }
+  BsdfEvalArgs a{};
+  a.material = material; a.surface = surface ? b[4].as<float4>() : nullptr; a.wo = b[0].as<float>(); a.wi = b[1].as<float>(); a.u = b[2].as<float>(); a.n = (unsigned)n; a.out = b[3].as<float>();
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)scene->n_cu * 16u);
+  rtx_launch_bsdf_eval(mode, const_tex, grid, nullptr, d, a);
+  HIP_TRY(hipGetLastError());
+  scene->bsdf_launched = 2 * mode + (const_tex ? 1 : 0);
+  HIP_TRY(hipMemcpy(out, b[3].p, no, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
 extern "C" int rt_link_tables(const rt_scene_desc* desc, int32_t mid, uint32_t* link_kept, uint32_t* link_full, uint64_t capacity_words, double* stats) {
   if (!desc || !desc->nodes || desc->n_nodes == 0 || !desc->tri_p || !desc->tri_meta || !link_kept || !link_full) return fail(RT_ERR_INVALID, "null argument");
   const size_t words = (size_t)9 * desc->n_nodes + 9;
@@ -1176,6 +1259,7 @@ extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (what == RT_QUERY_LDS_OCCLUSION) return s->mid ? 1 : 0;
   if (what == RT_QUERY_SHADOW_PAIRS) return s->shadow_sets ? (int)s->shadow.pairs : 0;
   if (what == RT_QUERY_SHADOW_EMPTY) return s->shadow_sets ? (int)s->shadow.empty : 0;
+  if (what == RT_QUERY_BSDF_LAUNCHED) return s->bsdf_launched < 0 ? 0 : s->bsdf_launched + 1;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -1705,9 +1789,22 @@ static void launch_shade(bool general, bool lean, bool bounced, unsigned grid, u
   rtx_launch_shade(MODE, general, lean, bounced, grid, block, stream, d, fp, p, qlights, lds);
 }
 
-extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
-                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out) {
-  if (!s || !cam || !film || !smp || !path || !film_xyzw) return fail(RT_ERR_INVALID, "null argument");
+// The frame of rt_render and of rt_render_samples. samples_rad != NULL: the frame of rt_render_samples - every pass hands its samples' radiance and film positions to
+// samples_rad / samples_pf (k_sample_store) instead of filtering them into the film (k_film_accumulate); film_xyzw is then unused.
+static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                        const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf) {
+  const bool samples = samples_rad != nullptr;
+  // the window of rt_render_samples: pixel_bounds inside the sample bounds, and its size - checked before any device work
+  const int wx0 = std::max(path->pixel_bounds[0], film->sample_bounds[0]), wy0 = std::max(path->pixel_bounds[1], film->sample_bounds[1]);
+  const int wx1 = std::min(path->pixel_bounds[2], film->sample_bounds[2]), wy1 = std::min(path->pixel_bounds[3], film->sample_bounds[3]);
+  unsigned long long n_window_samples = 0;
+  if (samples) {
+    if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_samples: the reference-stream frame has no per-sample output");
+    if (wx1 <= wx0 || wy1 <= wy0) return fail(RT_ERR_INVALID, "rt_render_samples: pixel_bounds and the film's sample bounds share no pixel");
+    const unsigned long long spp_r = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
+    n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * spp_r;
+    if (spp_r > 16384ull || n_window_samples > (unsigned long long)RT_SAMPLES_MAX) return fail(RT_ERR_INVALID, "rt_render_samples: the window holds more than RT_SAMPLES_MAX (2^27) samples");
+  }
   std::lock_guard<std::mutex> render_lock(s->render_mutex);
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t stream = (hipStream_t)stream_;
@@ -1798,20 +1895,18 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
   const bool has_infinite = s->d.n_infinite > 0;
   const size_t counter_words = (size_t)(fp.max_depth + 2) * RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;  // one block of {out, shadow, mis, mis-any} shard counts per bounce + raygen's
   // material binning before the generic shade kernel: per bounce {hist, cursor}[RT_BIN_MAX + 1] + the 8 count words of the sorted queue
-  const bool use_bins = !s->lambert_materials && s->n_code_classes > 1;  // one class: every vertex runs the same code, the queue order is kept
+  const ShadeRoute route = shade_route(s);  // (shared with rt_bsdf_eval's RT_BSDF_FRONT_AUTO)
+  const bool use_bins = route.use_bins;
   // (moving the travelling records into sorted order so that the shade launches stream them was measured in round 3: S3 shade 121.6 -> 135.5 ms, S4 3158 -> 3235 - a bin keeps
   // the queue's order in rounds of 256 entries, so the gather through the sorted list already reads runs of neighbouring slots. Removed.)
   const bool gshade = s->masked_emitters;  // quadric / instance hits, quadric or masked emitters: the GENERAL instantiations of the shade kernels
   const bool lean_shade = s->lean_shade;
   const int lds_shade = (s->lds_records_q && s->d.route_quadric_hits != 0) ? 1 : ((lean_shade || gshade) ? (s->lds_mats ? 2 : 0) : (s->lds_tables ? 3 : 0));  // the LEAN / QLIGHTS forms' tables in LDS
-  const bool qlights = s->d.route_quadric_hits != 0 && use_bins;  // QLIGHTS forms on the front-end ranges, quadric hits in a generic bin of their own
+  const bool qlights = route.qlights;
   const unsigned n_bins = std::min<unsigned>(s->n_code_classes, RT_BIN_MAX - 1) + 1u + (qlights ? 1u : 0u);
   const size_t bin_stride = (RT_BIN_MAX + 1) + (size_t)(RT_BIN_MAX + 1) * RT_CNT_STRIDE + (size_t)RT_QSHARDS * RT_CNT_STRIDE + 10;  // hist, cursors (spread), the sorted queue's counts (laid out as shard counters)  // + {begin, end} of the four class ranges and of the miss bin
-  // RTX_SHADE_SPLIT (measurement knob): 0 = every class through the generic front-end, 1 = Lambert classes apart, default = Lambert and two-lobe classes apart
-  const int split_mode = env_int("RTX_SHADE_SPLIT", 2);
-  const unsigned n_first = split_mode >= 1 ? s->n_lambert_classes : 0u, n_second = split_mode >= 2 ? s->n_small_classes : 0u;
-  const unsigned n_third = split_mode >= 2 ? s->n_wide_classes : 0u;
-  const bool split_classes = use_bins && (n_first + n_second + n_third) > 0 && n_first + n_second + n_third < RT_BIN_MAX;
+  const unsigned n_first = route.n_first, n_second = route.n_second, n_third = route.n_third;
+  const bool split_classes = route.split_classes;
   const unsigned pgrid_q = (unsigned)s->n_cu * 8u;
   const unsigned long long table_bytes_per_pixel = 2ull * dims * spp * 2ull;
 
@@ -1855,7 +1950,10 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
         {&s->sampler_plan.partners, (size_t)(chunk_pixels * table_bytes_per_pixel)}};
     if (use_bins) { want.push_back({&s->bin_words, (size_t)(fp.max_depth + 1) * bin_stride * 4}); want.push_back({&s->bin_sorted, (size_t)cap * 4}); want.push_back({&s->bin_at, (size_t)cap * 2}); }
     if (multi_batch) { want.push_back({&s->scrambles[1], (size_t)chunk_pixels * 3 * dims * 4}); want.push_back({&s->perms[1], (size_t)(chunk_pixels * table_bytes_per_pixel)}); }
-    if (!(flags & RT_FLAG_FILM_ON_DEVICE)) want.push_back({&s->film_out, (size_t)cw * ch * 16});
+    if (!(flags & RT_FLAG_FILM_ON_DEVICE)) {
+      if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
+      else { want.push_back({&s->samples_rad, (size_t)n_window_samples * 16}); if (samples_pf) want.push_back({&s->samples_pf, (size_t)n_window_samples * 8}); }
+    }
     size_t grow = 0;  // bytes the buffers have to grow by (a buffer that is too small is freed and allocated anew)
     for (const Want& w : want) if (!w.buf->p || w.buf->bytes < w.bytes) grow += w.bytes;
     size_t held = 0;
@@ -1875,8 +1973,12 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
     HIP_TRY(hipEventCreateWithFlags(&s->ev_frame_begin, hipEventDisableTiming));
   }
   float4* const d_out = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)film_xyzw : s->film_out.as<float4>();
-  HIP_TRY(hipMemcpyAsync(s->filter_table.p, film->filter_table, 1024, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)cw * ch * 16, stream));
+  float4* const d_samples_rad = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)samples_rad : s->samples_rad.as<float4>();
+  float2* const d_samples_pf = !samples_pf ? nullptr : ((flags & RT_FLAG_FILM_ON_DEVICE) ? (float2*)samples_pf : s->samples_pf.as<float2>());
+  if (!samples) {  // (no kernel of a samples frame reads the filter table or the film sums)
+    HIP_TRY(hipMemcpyAsync(s->filter_table.p, film->filter_table, 1024, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)cw * ch * 16, stream));
+  }
   HIP_TRY(hipMemsetAsync(s->stats.p, 0, ST_COUNT * 8, stream));
 
   PassState ps{};
@@ -2023,21 +2125,27 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
         stats.launches_trace_closest += 2; stats.launches_trace_path += 1; stats.launches_trace_mis += 1; stats.launches_trace_shadow += 1; stats.launches_trace_mis_any += ps.mis_any ? 1 : 0;
       }
       tm.begin(&stats.ms_film);
-      hipLaunchKernelGGL(k_film_accumulate, dim3(pgrid), dim3(256), 0, stream, fp, ps, s->filter_table.as<float>(), s->film_acc.as<float4>());
+      if (samples) hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, ps, wx0, wy0, wx1 - wx0, d_samples_rad, d_samples_pf);
+      else hipLaunchKernelGGL(k_film_accumulate, dim3(pgrid), dim3(256), 0, stream, fp, ps, s->filter_table.as<float>(), s->film_acc.as<float4>());
       tm.end();
       stats.n_passes += 1;
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(s->ev_batch_done[buf], stream));
   }
-  tm.begin(&stats.ms_film);
-  {
-    unsigned long long n = (unsigned long long)cw * ch;
-    hipLaunchKernelGGL(k_film_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, s->film_acc.as<float4>(), d_out, n);
+  if (!samples) {
+    tm.begin(&stats.ms_film);
+    {
+      unsigned long long n = (unsigned long long)cw * ch;
+      hipLaunchKernelGGL(k_film_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, s->film_acc.as<float4>(), d_out, n);
+    }
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    if (!(flags & RT_FLAG_FILM_ON_DEVICE)) HIP_TRY(hipMemcpyAsync(film_xyzw, d_out, (size_t)cw * ch * 16, hipMemcpyDeviceToHost, stream));
+  } else if (!(flags & RT_FLAG_FILM_ON_DEVICE)) {
+    HIP_TRY(hipMemcpyAsync(samples_rad, d_samples_rad, (size_t)n_window_samples * 16, hipMemcpyDeviceToHost, stream));
+    if (samples_pf) HIP_TRY(hipMemcpyAsync(samples_pf, d_samples_pf, (size_t)n_window_samples * 8, hipMemcpyDeviceToHost, stream));
   }
-  tm.end();
-  HIP_TRY(hipGetLastError());
-  if (!(flags & RT_FLAG_FILM_ON_DEVICE)) HIP_TRY(hipMemcpyAsync(film_xyzw, d_out, (size_t)cw * ch * 16, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   tm.collect();
   stats.ms_shade = stats.ms_shade_lambert_const + stats.ms_shade_lambert + stats.ms_shade_two_lobe + stats.ms_shade_generic + stats.ms_shade_bin + stats.ms_shade_miss;
@@ -2059,6 +2167,16 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* 
   stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   if (stats_out) *stats_out = stats;
   return RT_OK;
+}
+extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out) {
+  if (!s || !cam || !film || !smp || !path || !film_xyzw) return fail(RT_ERR_INVALID, "null argument");
+  return render_frame(s, cam, film, smp, path, shard, flags, stream_, film_xyzw, stats_out, nullptr, nullptr);
+}
+extern "C" int rt_render_samples(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                                 uint32_t flags, void* stream_, float* radiance, float* p_film, rt_stats* stats_out) {
+  if (!s || !cam || !film || !smp || !path || !radiance) return fail(RT_ERR_INVALID, "rt_render_samples: null argument");
+  return render_frame(s, cam, film, smp, path, nullptr, flags, stream_, nullptr, stats_out, radiance, p_film);
 }
 
 // ---------------------------------------------------------------------------------------------- several GPUs, one process

@@ -1267,6 +1267,27 @@ int rtxh_render(rtxh_scene* s, const rtxh_render_params* p, void* stream, float*
   rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
   return rt_render(s->dev, &cf.cam, &cf.film, &smp, &path, &shard, p->flags, stream, film_xyzw, stats);
 }
+int rtxh_render_samples(rtxh_scene* s, const rtxh_render_params* p, void* stream, float* radiance, float* p_film, rt_stats* stats) {
+  if (!s || !p || !radiance) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  int pb[4] = {cf.film.sample_bounds[0], cf.film.sample_bounds[1], cf.film.sample_bounds[2], cf.film.sample_bounds[3]};  // as rtxh_render
+  if (p->has_pixel_bounds) {
+    pb[0] = std::max(pb[0], p->pixel_bounds[0]); pb[1] = std::max(pb[1], p->pixel_bounds[2]);
+    pb[2] = std::min(pb[2], p->pixel_bounds[1]); pb[3] = std::min(pb[3], p->pixel_bounds[3]);
+  }
+  memcpy(path.pixel_bounds, pb, 16);
+  {  // the size rt_render_samples refuses, before the scene is uploaded for it
+    unsigned long long spp = 1; while (spp < (unsigned long long)std::max(p->spp, 1)) spp <<= 1;
+    if (pb[2] <= pb[0] || pb[3] <= pb[1]) return fail(RT_ERR_INVALID, "rtxh_render_samples: the pixel bounds hold no pixel");
+    if ((unsigned long long)(pb[2] - pb[0]) * (unsigned long long)(pb[3] - pb[1]) * spp > (unsigned long long)RT_SAMPLES_MAX)
+      return fail(RT_ERR_INVALID, "rtxh_render_samples: the window holds more than RT_SAMPLES_MAX (2^27) samples");
+  }
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_samples(s->dev, &cf.cam, &cf.film, &smp, &path, p->flags, stream, radiance, p_film, stats);
+}
 int rtxh_render_multi(rtxh_scene* s, const rtxh_render_params* p, const int32_t* devices, int32_t n_devices, int32_t chunks_per_device, float* film_xyzw,
                       rt_stats* total, rt_stats* per_device) {
   if (!s || !p || !film_xyzw || !devices || n_devices < 1) return fail(RT_ERR_INVALID, "null argument");

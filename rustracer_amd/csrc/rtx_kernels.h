@@ -2394,6 +2394,28 @@ static __global__ void k_film_finalize(const float4* film_acc, float4* film_xyzw
   film_xyzw[i] = make_float4(X, Y, Z, a.w);
 }
 
+// rt_render_samples: instead of k_film_accumulate, a pass hands its samples out unfiltered. One lane per path of the pass - a wave reads 64 consecutive records of
+// lacc / pfilm, the once-through streams the film kernel reads - and each lane stores its sample at [window pixel][sample] of the output (16- and 8-byte stores,
+// spp records apart). rad.w = 1 where renderer.rs:115-126 scrubs the sample; rgb is what PathIntegrator::li returned, before that scrubbing and the luminance clamp.
+static __global__ void __launch_bounds__(256) k_sample_store(FrameParams fp, PassState ps, int wx0, int wy0, int ww, float4* __restrict__ rad, float2* __restrict__ pf) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  unsigned scrubbed = 0;
+  for (unsigned pid = blockIdx.x * blockDim.x + threadIdx.x; pid < ps.cap; pid += stride) {
+    const float4 l4 = ps.lacc[pid]; const float2 p2 = ps.pfilm[pid];
+    if (__float_as_uint(l4.w) & RT_STATE_OUT_OF_BOUNDS) continue;  // outside pixel_bounds or the sample rows: never traced, no slot in the window
+    unsigned sl, pix; split_path_id(ps, pid, sl, pix);
+    int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+    const rgb3 c = mkc(l4.x, l4.y, l4.z);
+    const bool bad = has_nan(c) || lum_y(c) < -1e-5f || isinf(lum_y(c));
+    scrubbed += bad ? 1u : 0u;
+    const size_t o = ((size_t)(y - wy0) * (size_t)ww + (size_t)(x - wx0)) * ps.spp + ps.s0 + sl;
+    rad[o] = make_float4(l4.x, l4.y, l4.z, bad ? 1.0f : 0.0f);
+    if (pf) pf[o] = p2;
+  }
+  for (int off = 32; off > 0; off >>= 1) scrubbed += __shfl_down(scrubbed, off);
+  if ((threadIdx.x & 63u) == 0u && scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
+}
+
 // ================================================================================ per-triangle / per-light constants (rt_scene_create)
 // What Triangle::intersect computes of the triangle alone (dpdu, dpdv, the geometric normal and - without per-vertex normals or tangents - the whole shading
 // frame and the first axis of Bsdf::new's frame) is evaluated once here, by the functions the per-vertex path uses (tri_geo, tri_frame: IEEE + - * / sqrt

@@ -8,4 +8,8 @@ void rtx_launch_shade(int mode, bool general, bool lean, bool bounced, unsigned 
 // k_shade<1> (constant matte, area lights): ldsrec 0 / 1 / 3
 void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p);
 void rtx_shade_set_ewa_lut(const float* lut128);  // kEwaLut of that translation unit
+// rt_bsdf_eval: one Bsdf front-end of k_shade - mode 0 GenericBsdf, 3 SingleLambertT, 5 SmallBsdfT<false>, 6 SmallBsdfT<true>; const_tex: the constant-texture form
+// k_shade<1> and the LEAN forms use - on n queries, one lane each. Device pointers; surface NULL = the canonical hit. d.tri_p: record k carries orientation flag k (0, 1).
+struct BsdfEvalArgs { int material; const float4* surface; const float* wo; const float* wi; const float* u; unsigned n; float* out; };
+void rtx_launch_bsdf_eval(int mode, bool const_tex, unsigned grid, hipStream_t stream, const DScene& d, const BsdfEvalArgs& a);
 }

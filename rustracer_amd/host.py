@@ -24,6 +24,13 @@ RT_FLAG_FILM_ON_DEVICE = 2
 RT_FLAG_TIME_KERNELS = 4
 RT_FLAG_COUNT_AS_RENDERED = 8
 RT_FLAG_REF_STREAM = 16
+RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
+RT_BSDF_SURFACE_FLOATS = 40
+RT_BSDF_OUT_FLOATS = 13
+RT_SAMPLES_MAX = 1 << 27
+RT_QUERY_BSDF_LAUNCHED = 5  # rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
+BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
+                       two_lobe_wide=RT_BSDF_FRONT_TWO_LOBE_WIDE)
 
 
 class BackendError(RuntimeError):
@@ -412,6 +419,55 @@ class HostScene:
             raise BackendError(f"rt_texture_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
         return out
 
+    def bsdf_eval(self, material, wo, wi, u, surface=None, front_end="auto"):
+        """The Bsdf material `material` builds at a surface point, evaluated per query by a front-end of the shade kernels (rt_bsdf_eval): wo, wi (n, 3) in WORLD space,
+        u (n, 2); surface None = the canonical hit (n = +z, dpdu = +x, dpdv = +y, uv = (0.5, 0.5)) or (n, 40) records (`surface_records`); front_end one of
+        "auto", "generic", "lambert", "two_lobe", "two_lobe_wide". Returns dict(f=(n, 3), pdf=(n,), sf=(n, 3), swi=(n, 3), spdf=(n,), stype=(n,) int, n_lobes=(n,) int,
+        raw=(n, 13) float32). Uploads the scene first if need be."""
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = wo.shape[0]
+        assert wi.shape[0] == n and u.shape[0] == n
+        if surface is not None:
+            surface = np.ascontiguousarray(surface, np.float32).reshape(-1, RT_BSDF_SURFACE_FLOATS)
+            assert surface.shape[0] == n
+        dev = C.c_void_p()
+        _check(lib().rtxh_scene_device(self.h, C.byref(dev)), "scene_device")
+        out = np.zeros((n, RT_BSDF_OUT_FLOATS), np.float32)
+        rc = hip_lib().rt_bsdf_eval(dev, C.c_int32(material), C.c_int32(BSDF_FRONT_ENDS[front_end] if isinstance(front_end, str) else int(front_end)), C.c_uint64(n),
+                                    _p(surface), _p(wo), _p(wi), _p(u), _p(out))
+        if rc != 0:
+            raise BackendError(f"rt_bsdf_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+        return dict(f=out[:, 0:3], pdf=out[:, 3], sf=out[:, 4:7], swi=out[:, 7:10], spdf=out[:, 10], stype=out[:, 11].astype(np.int32), n_lobes=out[:, 12].astype(np.int32), raw=out)
+
+    def samples_window(self):
+        """(x0, y0, x1, y1) of the pixels render_samples returns: the integrator's "pixelbounds" inside the film's sample bounds (PathIntegrator::create, path.rs:53-69)."""
+        st = self.setup()
+        sb, p = [int(v) for v in st["sample_bounds"]], st["params"]
+        if p.has_pixel_bounds:  # x0 x1 y0 y1, as the scene file lists them
+            pb = list(p.pixel_bounds)
+            sb = [max(sb[0], pb[0]), max(sb[1], pb[2]), min(sb[2], pb[1]), min(sb[3], pb[3])]
+        return tuple(sb)
+
+    def render_samples(self, count_traversal=False, time_kernels=False, with_p_film=True, stream=0):
+        """The frame of `render`, sample by sample (rt_render_samples): returns (radiance (h, w, spp, 4), p_film (h, w, spp, 2) or None, stats dict) over
+        `samples_window()`; radiance[..., :3] is L as PathIntegrator::li returned it, radiance[..., 3] is 1 where the renderer scrubs the sample."""
+        x0, y0, x1, y1 = self.samples_window()
+        w, h = x1 - x0, y1 - y0
+        p = self.setup()["params"]
+        spp = 1
+        while spp < max(int(p.spp), 1):
+            spp *= 2
+        if w <= 0 or h <= 0 or w * h * spp > RT_SAMPLES_MAX:
+            raise BackendError(f"render_samples: a window of {max(w, 0)} x {max(h, 0)} pixels x {spp} samples is empty or holds more than RT_SAMPLES_MAX samples")
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        rad = np.zeros((h, w, spp, 4), np.float32)
+        pf = np.zeros((h, w, spp, 2), np.float32) if with_p_film else None
+        stats = Stats()
+        _check(lib().rtxh_render_samples(self.h, C.byref(p), C.c_void_p(stream), _p(rad), _p(pf), C.byref(stats)), "render_samples")
+        return rad, pf, stats.as_dict()
+
     def texture_words(self, tex):
         """The word block of texture `tex` as the host holds it (float32), or an empty array for a texture that names none."""
         L = lib()
@@ -589,6 +645,18 @@ def offset_ray_origin(p, p_error, n, w):
     if rc < 0:
         raise BackendError(f"rt_offset_ray_origin failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
     return out
+
+
+def surface_records(n, p=None, n_geom=None, n_shading=None, dpdu=None, dpdv=None, sh_dpdu=None, sh_dpdv=None, uv=None, duv=None, dpdx=None, dpdy=None, flip=None):
+    """(n, 40) float32 surface records for HostScene.bsdf_eval in the order rtx_hip.h documents (p, n, shading n, dpdu, dpdv, shading dpdu, shading dpdv, dndu, dndv,
+    uv, dudx dvdx dudy dvdy, dpdx, dpdy, flip). Omitted fields take the canonical hit's values; shading fields default to the geometric ones."""
+    col = lambda v, w, d: np.broadcast_to(np.asarray(d if v is None else v, np.float32).reshape(-1, w), (n, w))
+    ng = col(n_geom, 3, (0, 0, 1))
+    du, dv = col(dpdu, 3, (1, 0, 0)), col(dpdv, 3, (0, 1, 0))
+    rec = np.concatenate([col(p, 3, (0, 0, 0)), ng, ng if n_shading is None else col(n_shading, 3, None), du, dv, du if sh_dpdu is None else col(sh_dpdu, 3, None),
+                          dv if sh_dpdv is None else col(sh_dpdv, 3, None), np.zeros((n, 6), np.float32), col(uv, 2, (0.5, 0.5)), col(duv, 4, (0, 0, 0, 0)),
+                          col(dpdx, 3, (0, 0, 0)), col(dpdy, 3, (0, 0, 0)), col(flip, 1, (0,))], axis=1)
+    return np.ascontiguousarray(rec, np.float32)
 
 
 def film_to_rgb(film_xyzw: np.ndarray, scale: float = 1.0) -> np.ndarray:

@@ -1,10 +1,12 @@
 """Render a pbrt-v3 scene file on the GPU.
 
-    python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N]
+    python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
-8-bit sRGB PNG with write_image_png's quantisation (rc/imageio.rs:52-74). A .pfm name gets the linear film values."""
+8-bit sRGB PNG with write_image_png's quantisation (rc/imageio.rs:52-74). A .pfm name gets the linear film values.
+--samples out.npy: instead of an image, the radiance of every sample of the integrator's pixel bounds (rt_render_samples), float32
+[height, width, spp, 6] = L rgb as PathIntegrator::li returned it, 1.0 where the renderer scrubs the sample, the sample's film position."""
 import argparse
 import os
 import sys
@@ -19,11 +21,19 @@ def main():
     ap.add_argument("scene")
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
+    ap.add_argument("--samples", metavar="OUT.npy", default=None, help="write the per-sample radiance and film positions of the pixel bounds instead of an image")
     a = ap.parse_args()
     host.build()
     s = host.PbrtScene(a.scene)
     if a.spp:
         s.params.spp = a.spp
+    if a.samples:
+        import numpy as np
+        rad, pf, stats = s.render_samples()
+        np.save(a.samples, np.concatenate([rad, pf], axis=-1))
+        x0, y0, x1, y1 = s.samples_window()
+        print(f"{a.samples}: pixels [{x0}, {x1}) x [{y0}, {y1}), {rad.shape[2]} samples each, {int(rad[..., 3].sum())} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
+        return
     film, stats = s.render()
     out = a.out or s.film_filename
     rgb = host.film_to_rgb(film, s.params.film_scale)
