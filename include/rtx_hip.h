@@ -21,7 +21,8 @@ extern "C" {
 
 #define RT_OK 0
 #define RT_ERR_INVALID (-1)   /* bad argument / inconsistent description            */
-#define RT_ERR_NO_DEVICE (-2) /* no usable gfx950 device; there is NO CPU fallback  */
+#define RT_ERR_NO_DEVICE (-2) /* no usable gfx950 device; there is NO CPU fallback. rt_scene_create / rt_multi_create check the whole description first: a faulty
+                                 one is refused with RT_ERR_INVALID / RT_ERR_UNSUPPORTED and the same message on any machine, a valid one gets this code */
 #define RT_ERR_HIP (-3)       /* a HIP call failed; see rt_last_error()             */
 #define RT_ERR_OOM (-4)
 #define RT_ERR_UNSUPPORTED (-5) /* input the reference accepts and this backend does not  */
@@ -111,10 +112,10 @@ typedef struct rt_texture {
  * or else a Fourier BSDF table (FourierBSDFTable, rc/bsdf/fourier.rs:281-371) that an RT_MAT_FOURIER material names:
  * `texels` points to 3 * n_texels packed 32-bit words (zero-padded to a whole texel) - the header {nMu, mMax, nChannels, nCoeffs as u32, eta as f32},
  * then mu[nMu] (f32, strictly ascending), cdf[nMu * nMu] (f32), offset_and_length[2 * nMu * nMu] (u32) and a[nCoeffs] (f32), as a .bsdf file lists them.
- * rt_scene_create / rt_multi_create refuse with RT_ERR_INVALID (before any device is touched) a table whose sizes do not add up, with nMu outside [2, 8192],
+ * rt_scene_create / rt_multi_create refuse with RT_ERR_INVALID (as every fault of a description: before any device is touched) a table whose sizes do not add up, with nMu outside [2, 8192],
  * nChannels not 1 or 3, mu not ascending, a cell longer than mMax or whose coefficients run past nCoeffs, more than 2^28 table words in the scene, a Fourier
  * material whose slot M1 names a MIP pyramid, and an image texture or infinite light that names a table. width / height / offset / trilinear / wrap are unused.
- * They refuse as well (RT_ERR_INVALID, before any device is touched) a word block shorter than its texture's words, a mapped texture that names a MIP
+ * They refuse as well (RT_ERR_INVALID) a word block shorter than its texture's words, a mapped texture that names a MIP
  * pyramid, a Fourier material, image texture or infinite light that names a word block, a texture graph with a cycle and an operand out of range. */
 enum { RT_WRAP_REPEAT = 0, RT_WRAP_BLACK = 1, RT_WRAP_CLAMP = 2 };
 #define RT_MAX_MIP_LEVELS 16

@@ -13,6 +13,7 @@ from rustracer_amd.pbrt_export import write_pbrt
 from rustracer_amd.scenes import cornell_box
 
 import fourier_ref as fr
+from util import RtImage, RtMaterial, RtSceneDesc, RtTexture
 
 RT_ERR_INVALID, RT_ERR_NO_DEVICE = -1, -2
 
@@ -100,28 +101,6 @@ def test_reader_refuses_a_missing_or_empty_name(tmp_path):
 
 
 # ---------------------------------------------------------------- rt_scene_create's checks (made before any device is touched)
-class RtImage(C.Structure):
-    _fields_ = [("n_levels", C.c_int32), ("width", C.c_int32 * 16), ("height", C.c_int32 * 16), ("offset", C.c_uint64 * 16), ("texels", C.c_void_p),
-                ("n_texels", C.c_uint64), ("trilinear", C.c_int32), ("max_anisotropy", C.c_float), ("wrap", C.c_int32)]
-
-
-class RtMaterial(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("slot", C.c_int32 * 16), ("remap_roughness", C.c_int32), ("bump", C.c_int32)]
-
-
-class RtTexture(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("value", C.c_float * 3), ("tex1", C.c_int32), ("tex2", C.c_int32), ("amount", C.c_int32), ("image", C.c_int32),
-                ("mapping", C.c_float * 4)]
-
-
-class RtSceneDesc(C.Structure):
-    _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_tris", C.c_uint32), ("tri_p", C.c_void_p), ("tri_n", C.c_void_p), ("tri_uv", C.c_void_p),
-                ("tri_s", C.c_void_p), ("tri_meta", C.c_void_p), ("tri_alpha", C.c_void_p), ("n_spheres", C.c_uint32), ("spheres", C.c_void_p),
-                ("n_textures", C.c_uint32), ("textures", C.c_void_p), ("n_images", C.c_uint32), ("images", C.c_void_p), ("n_materials", C.c_uint32),
-                ("materials", C.c_void_p), ("n_lights", C.c_uint32), ("lights", C.c_void_p), ("n_instances", C.c_uint32), ("instances", C.c_void_p),
-                ("n_top_nodes", C.c_uint32), ("n_top_prims", C.c_uint32), ("n_unlisted_lights", C.c_uint32)]
-
-
 def test_mirrors_have_the_header_sizes():
     for cls, name in ((RtImage, b"rt_image"), (RtMaterial, b"rt_material"), (RtTexture, b"rt_texture"), (RtSceneDesc, b"rt_scene_desc")):
         assert host.hip_lib().rt_sizeof(name) == C.sizeof(cls), name

@@ -1,3 +1,5 @@
+import ctypes as C
+
 import numpy as np
 
 
@@ -62,3 +64,51 @@ def tables_from_perm(scr, perm, dims):
         t2[d, :, 0] = _unit(scr[dims + 2 * d] ^ _brev(k ^ (k >> np.uint32(1))))
         t2[d, :, 1] = _unit(scr[dims + 2 * d + 1] ^ _sobol1(k))
     return t1, t2
+
+
+# ---------------------------------------------------------------- ctypes mirrors of the scene description (include/rtx_hip.h), for tests that call librtx_hip.so directly
+class RtBvhNode(C.Structure):
+    _fields_ = [("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("offset", C.c_uint32), ("n_prims", C.c_uint16), ("axis", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class RtTriMeta(C.Structure):
+    _fields_ = [("material", C.c_int32), ("light", C.c_int32), ("flags", C.c_uint32), ("source_index", C.c_uint32)]
+
+
+class RtSphere(C.Structure):
+    _fields_ = [("o2w", C.c_float * 16), ("w2o", C.c_float * 16), ("radius", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("theta_min", C.c_float),
+                ("theta_max", C.c_float), ("phi_max", C.c_float), ("reverse_orientation", C.c_int32), ("swaps_handedness", C.c_int32), ("kind", C.c_int32),
+                ("height", C.c_float), ("inner_radius", C.c_float)]
+
+
+class RtInstance(C.Structure):
+    _fields_ = [("o2w", C.c_float * 16), ("w2o", C.c_float * 16), ("node_base", C.c_uint32), ("n_nodes", C.c_uint32), ("prim_base", C.c_uint32), ("n_prims", C.c_uint32)]
+
+
+class RtImage(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("width", C.c_int32 * 16), ("height", C.c_int32 * 16), ("offset", C.c_uint64 * 16), ("texels", C.c_void_p),
+                ("n_texels", C.c_uint64), ("trilinear", C.c_int32), ("max_anisotropy", C.c_float), ("wrap", C.c_int32)]
+
+
+class RtMaterial(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("slot", C.c_int32 * 16), ("remap_roughness", C.c_int32), ("bump", C.c_int32)]
+
+
+class RtTexture(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("value", C.c_float * 3), ("tex1", C.c_int32), ("tex2", C.c_int32), ("amount", C.c_int32), ("image", C.c_int32),
+                ("mapping", C.c_float * 4)]
+
+
+class RtLight(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("prim", C.c_int32), ("rgb", C.c_float * 3), ("two_sided", C.c_int32), ("vec", C.c_float * 3), ("area", C.c_float),
+                ("world_radius", C.c_float), ("image", C.c_int32), ("l2w", C.c_float * 12), ("w2l", C.c_float * 12), ("dist_nu", C.c_int32), ("dist_nv", C.c_int32),
+                ("dist_func", C.c_void_p), ("dist_cdf", C.c_void_p), ("dist_func_int", C.c_void_p), ("marg_func", C.c_void_p), ("marg_cdf", C.c_void_p),
+                ("marg_func_int", C.c_float)]
+
+
+class RtSceneDesc(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_tris", C.c_uint32), ("tri_p", C.c_void_p), ("tri_n", C.c_void_p), ("tri_uv", C.c_void_p),
+                ("tri_s", C.c_void_p), ("tri_meta", C.c_void_p), ("tri_alpha", C.c_void_p), ("n_spheres", C.c_uint32), ("spheres", C.c_void_p),
+                ("n_textures", C.c_uint32), ("textures", C.c_void_p), ("n_images", C.c_uint32), ("images", C.c_void_p), ("n_materials", C.c_uint32),
+                ("materials", C.c_void_p), ("n_lights", C.c_uint32), ("lights", C.c_void_p), ("n_instances", C.c_uint32), ("instances", C.c_void_p),
+                ("n_top_nodes", C.c_uint32), ("n_top_prims", C.c_uint32), ("n_unlisted_lights", C.c_uint32)]
