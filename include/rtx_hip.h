@@ -407,6 +407,36 @@ int rt_bsdf_eval(rt_scene* scene, int32_t material, int32_t front_end, uint64_t 
 int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
                       uint32_t flags, void* stream, float* radiance, float* p_film, rt_stats* stats);
 
+/* Progressive frames: the frame of rt_render rendered in steps, with the film readable between them. The reference's CLI offers "display image as it is
+ * rendered" (-p / --display); it has no checkpoint or resume. The pixel-keyed sampler makes sample s of pixel p the same whichever call renders it, so a frame
+ * can stop after any number of samples per pixel and go on later.
+ * rt_frame_begin copies camera, film, sampler and path, builds the light distribution as a first rt_render would, and allocates the frame's own state on the
+ *   scene's device: the film sums (one float4 per cropped pixel), each pixel's own sum (one float4 per owned pixel of the shard), the filter table and - if
+ *   owned_pixels * (2 * dims * spp * 2 + 3 * dims * 4) bytes fit table_budget_bytes (0: the smaller of 32 GiB and a quarter of the free device memory) - the
+ *   sampler tables of the whole shard, built once by the first step. Otherwise every step rebuilds each batch's tables as rt_render does; the film is the same
+ *   byte for byte. Path-state workspace stays the scene's. Refused with RT_ERR_INVALID before any device work: RT_FLAG_REF_STREAM, spp > 16384, dimensions
+ *   outside [2, 8], a bad shard, an empty film, a NULL out. flags: RT_FLAG_COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED act per step as in rt_render.
+ * rt_frame_advance renders samples [done, min(done + n_samples, spp)) of every owned pixel (spp rounded up to a power of two) with the kernels, queues and routes
+ *   of rt_render; stats are those of the step. n_samples <= 0: RT_ERR_INVALID; a finished frame: RT_OK, zeroed stats, no device work. A pixel's own sum receives
+ *   its samples in index order whatever the steps are: the finished frame is rt_render's (bit for bit where the filter reaches no further than the pixel and a pixel
+ *   receives at most one edge splat; else up to the order of the float additions, which rt_render does not fix either).
+ * rt_frame_read resolves the film as it stands (zeros before the first step) without changing the frame. RT_FRAME_XYZW: W*H float4 (X, Y, Z, filter weight
+ *   sum), what rt_render hands back (scale ignored); RT_FRAME_RGB: W*H*3 floats, Film::write_image's pixel (rc/film.rs:196-234: XYZ -> RGB, / weight where
+ *   it is not zero, max(0, .), * scale); RT_FRAME_RGB8: W*H*3 bytes, that pixel through write_image_png's sRGB quantisation (rc/imageio.rs:52-63; NaN -> 0).
+ *   out: host memory, or device memory with RT_FLAG_FILM_ON_DEVICE in `flags`.
+ * rt_frame_query: RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP (rounded), RT_FRAME_TABLES_RESIDENT (0 / 1), RT_FRAME_STATE_BYTES (device bytes the frame holds).
+ * Any number of frames may live on one scene; their steps and rt_render calls on that scene take turns on the scene's mutex and change no byte of each other.
+ * A FRAME MUST BE ENDED BEFORE ITS SCENE IS DESTROYED. rt_frame_end(NULL) is a no-op. Single device; rt_shard is honoured (rows of other ranks read as zero). */
+enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2 };
+enum { RT_FRAME_SAMPLES_DONE = 0, RT_FRAME_SPP = 1, RT_FRAME_TABLES_RESIDENT = 2, RT_FRAME_STATE_BYTES = 3 };
+typedef struct rt_frame rt_frame;
+int rt_frame_begin(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                   const rt_shard* shard /* may be NULL */, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out);
+int rt_frame_advance(rt_frame* frame, int32_t n_samples, void* stream, rt_stats* stats /* of this step, may be NULL */);
+int rt_frame_read(rt_frame* frame, int32_t what, float scale, uint32_t flags, void* stream, void* out);
+int rt_frame_query(rt_frame* frame, int32_t what, uint64_t* value);
+void rt_frame_end(rt_frame* frame);
+
 /* Dense voxel light distribution of SpatialLightDistribution (rc/lightdistrib.rs:101-179):
  * n_voxels[3]; func: nvox*n_lights, cdf: nvox*(n_lights+1), func_int: nvox (host pointers, may be NULL
  * to query n_voxels only). */

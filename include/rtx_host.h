@@ -145,6 +145,15 @@ int rtxh_render(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float*
  * row-major. radiance: pixels x spp x 4 floats (spp rounded up to a power of two), p_film: pixels x spp x 2 or NULL; host pointers, or device pointers with
  * RT_FLAG_FILM_ON_DEVICE. rank / world_size of the parameters are ignored. */
 int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* radiance, float* p_film, rt_stats* stats);
+/* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
+ * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
+ * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */
+typedef struct rtxh_frame rtxh_frame;
+int rtxh_frame_begin(rtxh_scene*, const rtxh_render_params*, uint64_t table_budget_bytes, rtxh_frame** out);
+int rtxh_frame_advance(rtxh_frame*, int32_t n_samples, void* hip_stream, rt_stats* stats /* of this step, may be NULL */);
+int rtxh_frame_read(rtxh_frame*, int32_t what, float scale, uint32_t flags, void* hip_stream, void* out);
+int rtxh_frame_query(rtxh_frame*, int32_t what, uint64_t* value);
+void rtxh_frame_end(rtxh_frame*);
 /* The same frame on several GPUs of this process (rt_multi_* in rtx_hip.h): the scene is replicated on `devices` (kept for later calls with the
  * same list), host threads pull chunks of tile rows, the film is gathered on devices[0] and returned in host memory (or in memory of devices[0]
  * with RT_FLAG_FILM_ON_DEVICE). rank / world_size of the parameters are ignored. */

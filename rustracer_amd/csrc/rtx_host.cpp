@@ -1288,6 +1288,49 @@ int rtxh_render_samples(rtxh_scene* s, const rtxh_render_params* p, void* stream
   if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_render_samples(s->dev, &cf.cam, &cf.film, &smp, &path, p->flags, stream, radiance, p_film, stats);
 }
+// A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
+struct rtxh_frame { rt_frame* f = nullptr; };
+int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {
+  if (!s || !p || !out) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  *out = nullptr;
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  int pb[4] = {cf.film.sample_bounds[0], cf.film.sample_bounds[1], cf.film.sample_bounds[2], cf.film.sample_bounds[3]};  // as rtxh_render
+  if (p->has_pixel_bounds) {
+    pb[0] = std::max(pb[0], p->pixel_bounds[0]); pb[1] = std::max(pb[1], p->pixel_bounds[2]);
+    pb[2] = std::min(pb[2], p->pixel_bounds[1]); pb[3] = std::min(pb[3], p->pixel_bounds[3]);
+  }
+  memcpy(path.pixel_bounds, pb, 16);
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  rt_frame* f = nullptr;
+  rc = rt_frame_begin(s->dev, &cf.cam, &cf.film, &smp, &path, &shard, p->flags, table_budget_bytes, &f);
+  if (rc != RT_OK) return rc;
+  *out = new rtxh_frame{f};
+  return RT_OK;
+}
+int rtxh_frame_advance(rtxh_frame* f, int32_t n_samples, void* stream, rt_stats* stats) {
+  if (!f) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  return rt_frame_advance(f->f, n_samples, stream, stats);
+}
+int rtxh_frame_read(rtxh_frame* f, int32_t what, float scale, uint32_t flags, void* stream, void* out) {
+  if (!f || !out) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  return rt_frame_read(f->f, what, scale, flags, stream, out);
+}
+int rtxh_frame_query(rtxh_frame* f, int32_t what, uint64_t* value) {
+  if (!f || !value) return fail(RT_ERR_INVALID, "null argument");
+  g_err.clear();
+  return rt_frame_query(f->f, what, value);
+}
+void rtxh_frame_end(rtxh_frame* f) {
+  if (!f) return;
+  rt_frame_end(f->f);
+  delete f;
+}
 int rtxh_render_multi(rtxh_scene* s, const rtxh_render_params* p, const int32_t* devices, int32_t n_devices, int32_t chunks_per_device, float* film_xyzw,
                       rt_stats* total, rt_stats* per_device) {
   if (!s || !p || !film_xyzw || !devices || n_devices < 1) return fail(RT_ERR_INVALID, "null argument");

@@ -2317,6 +2317,57 @@ __global__ void __launch_bounds__(256) k_resolve(DScene sc, PassState ps) {
 // therefore accumulated in exactly the reference's per-tile order and flushed once after the last pass;
 // splats onto other pixels (filter radius > 0.5, or a sample exactly on a pixel edge) go through float
 // atomics. film_acc: float4 (R, G, B sums, weight sum) per cropped pixel.
+// One sample of pixel (x, y) into the pixel's own sum and its neighbours' (FilmTile::add_sample): shared by the film kernel of rt_render and the one of rt_frame_advance.
+RT_DEV void film_add_sample(const FrameParams& fp, const float* __restrict__ filter_table, float4* film_acc, int cw, float inv_rx, float inv_ry, int x, int y,
+                            const float4 l4, const float2 pf, rgb3& own, float& own_w, unsigned& scrubbed) {
+  if (__float_as_uint(l4.w) & RT_STATE_OUT_OF_BOUNDS) return;
+  rgb3 c = mkc(l4.x, l4.y, l4.z);
+  bool bad = false;  // renderer.rs:115-126
+  if (has_nan(c)) { c = mkc(0, 0, 0); bad = true; }
+  if (lum_y(c) < -1e-5f) { c = mkc(0, 0, 0); bad = true; }
+  if (isinf(lum_y(c))) { c = mkc(0, 0, 0); bad = true; }
+  scrubbed += bad;
+  rgb3 Lc = lum_y(c) > fp.max_sample_luminance ? c * fp.max_sample_luminance / lum_y(c) : c;
+  float dx = pf.x - 0.5f, dy = pf.y - 0.5f;
+  float p0x = ceilf(dx - fp.radius_x), p0y = ceilf(dy - fp.radius_y);
+  float p1x = floorf(dx + fp.radius_x + 1.0f), p1y = floorf(dy + fp.radius_y + 1.0f);
+  int x0 = f2i_sat(max_po(p0x, (float)fp.crop_x0)), y0 = f2i_sat(max_po(p0y, (float)fp.crop_y0));
+  int x1 = f2i_sat(min_po(p1x, (float)fp.crop_x1)), y1 = f2i_sat(min_po(p1y, (float)fp.crop_y1));
+  for (int yy = y0; yy < y1; ++yy) {
+    float fy = fabsf(((float)yy - dy) * inv_ry * 16.0f);
+    int iy = (int)f2u_sat(fminf(floorf(fy), 15.0f));
+    for (int xx = x0; xx < x1; ++xx) {
+      float fx = fabsf(((float)xx - dx) * inv_rx * 16.0f);
+      int ix = (int)f2u_sat(fminf(floorf(fx), 15.0f));
+      float fw = filter_table[iy * 16 + ix];
+      if (xx == x && yy == y) { own = own + Lc * fw; own_w += fw; }
+      else {
+        float* dst = (float*)&film_acc[(size_t)(yy - fp.crop_y0) * cw + (xx - fp.crop_x0)];
+        rgb3 v = Lc * fw;
+        atomicAdd(dst + 0, v.r); atomicAdd(dst + 1, v.g); atomicAdd(dst + 2, v.b); atomicAdd(dst + 3, fw);
+      }
+    }
+  }
+}
+// The pass's samples of batch pixel `pix`, in sample order, into (own, own_w) and the neighbours' sums.
+// Round 6: the records of EIGHT samples are requested together, then added in order. A pixel's samples are one lane's sequential loop (the reference's order of a
+// pixel's sum); with one load per iteration a launch over few pixels - a shard's batch of 2^15 on an 8-GPU frame - waited a memory round trip per sample (1024 of them:
+// 3.8 ms of film time per S1 shard against 1.3 for its share of the whole frame's). Same loads, same adds, same order.
+RT_DEV void film_add_pass(const FrameParams& fp, const PassState& ps, const float* __restrict__ filter_table, float4* film_acc, int cw, float inv_rx, float inv_ry,
+                          unsigned pix, int x, int y, rgb3& own, float& own_w, unsigned& scrubbed) {
+  constexpr unsigned KF = 8;
+  for (unsigned s0 = 0; s0 < ps.n_samples; s0 += KF) {
+    float4 lb[KF]; float2 pb[KF];
+#pragma unroll
+    for (unsigned k = 0; k < KF; ++k) {
+      const unsigned sl = s0 + k < ps.n_samples ? s0 + k : ps.n_samples - 1u;
+      const unsigned pid = sl * ps.n_pixels + pix;
+      lb[k] = ps.lacc[pid]; pb[k] = ps.pfilm[pid];
+    }
+#pragma unroll
+    for (unsigned k = 0; k < KF; ++k) if (s0 + k < ps.n_samples) film_add_sample(fp, filter_table, film_acc, cw, inv_rx, inv_ry, x, y, lb[k], pb[k], own, own_w, scrubbed);
+  }
+}
 static __global__ void __launch_bounds__(256) k_film_accumulate(FrameParams fp, PassState ps, const float* __restrict__ filter_table, float4* film_acc) {
   const unsigned stride = gridDim.x * blockDim.x;
   const int cw = fp.crop_x1 - fp.crop_x0;
@@ -2329,58 +2380,71 @@ static __global__ void __launch_bounds__(256) k_film_accumulate(FrameParams fp, 
     rgb3 own = mkc(0, 0, 0); float own_w = 0.0f;
     if (!first_pass) { float4 a = ps.own_acc[pix]; own = mkc(a.x, a.y, a.z); own_w = a.w; }
     unsigned scrubbed = 0;
-    // one sample into the pixel's own sum and its neighbours' (FilmTile::add_sample), in sample order
-    auto add_sample = [&](const float4 l4, const float2 pf) {
-      if (__float_as_uint(l4.w) & RT_STATE_OUT_OF_BOUNDS) return;
-      rgb3 c = mkc(l4.x, l4.y, l4.z);
-      bool bad = false;  // renderer.rs:115-126
-      if (has_nan(c)) { c = mkc(0, 0, 0); bad = true; }
-      if (lum_y(c) < -1e-5f) { c = mkc(0, 0, 0); bad = true; }
-      if (isinf(lum_y(c))) { c = mkc(0, 0, 0); bad = true; }
-      scrubbed += bad;
-      rgb3 Lc = lum_y(c) > fp.max_sample_luminance ? c * fp.max_sample_luminance / lum_y(c) : c;
-      float dx = pf.x - 0.5f, dy = pf.y - 0.5f;
-      float p0x = ceilf(dx - fp.radius_x), p0y = ceilf(dy - fp.radius_y);
-      float p1x = floorf(dx + fp.radius_x + 1.0f), p1y = floorf(dy + fp.radius_y + 1.0f);
-      int x0 = f2i_sat(max_po(p0x, (float)fp.crop_x0)), y0 = f2i_sat(max_po(p0y, (float)fp.crop_y0));
-      int x1 = f2i_sat(min_po(p1x, (float)fp.crop_x1)), y1 = f2i_sat(min_po(p1y, (float)fp.crop_y1));
-      for (int yy = y0; yy < y1; ++yy) {
-        float fy = fabsf(((float)yy - dy) * inv_ry * 16.0f);
-        int iy = (int)f2u_sat(fminf(floorf(fy), 15.0f));
-        for (int xx = x0; xx < x1; ++xx) {
-          float fx = fabsf(((float)xx - dx) * inv_rx * 16.0f);
-          int ix = (int)f2u_sat(fminf(floorf(fx), 15.0f));
-          float fw = filter_table[iy * 16 + ix];
-          if (xx == x && yy == y) { own = own + Lc * fw; own_w += fw; }
-          else {
-            float* dst = (float*)&film_acc[(size_t)(yy - fp.crop_y0) * cw + (xx - fp.crop_x0)];
-            rgb3 v = Lc * fw;
-            atomicAdd(dst + 0, v.r); atomicAdd(dst + 1, v.g); atomicAdd(dst + 2, v.b); atomicAdd(dst + 3, fw);
-          }
-        }
-      }
-        };
-    // Round 6: the records of EIGHT samples are requested together, then added in order. A pixel's samples are one lane's sequential loop (the reference's order of a
-    // pixel's sum); with one load per iteration a launch over few pixels - a shard's batch of 2^15 on an 8-GPU frame - waited a memory round trip per sample (1024 of them:
-    // 3.8 ms of film time per S1 shard against 1.3 for its share of the whole frame's). Same loads, same adds, same order.
-    constexpr unsigned KF = 8;
-    for (unsigned s0 = 0; s0 < ps.n_samples; s0 += KF) {
-      float4 lb[KF]; float2 pb[KF];
-#pragma unroll
-      for (unsigned k = 0; k < KF; ++k) {
-        const unsigned sl = s0 + k < ps.n_samples ? s0 + k : ps.n_samples - 1u;
-        const unsigned pid = sl * ps.n_pixels + pix;
-        lb[k] = ps.lacc[pid]; pb[k] = ps.pfilm[pid];
-      }
-#pragma unroll
-      for (unsigned k = 0; k < KF; ++k) if (s0 + k < ps.n_samples) add_sample(lb[k], pb[k]);
-    }
+    film_add_pass(fp, ps, filter_table, film_acc, cw, inv_rx, inv_ry, pix, x, y, own, own_w, scrubbed);
     if (!last_pass) ps.own_acc[pix] = make_float4(own.r, own.g, own.b, own_w);
     else if (x >= fp.crop_x0 && x < fp.crop_x1 && y >= fp.crop_y0 && y < fp.crop_y1) {
       float* dst = (float*)&film_acc[(size_t)(y - fp.crop_y0) * cw + (x - fp.crop_x0)];
       atomicAdd(dst + 0, own.r); atomicAdd(dst + 1, own.g); atomicAdd(dst + 2, own.b); atomicAdd(dst + 3, own_w);
     }
     if (scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
+  }
+}
+// The film kernel of a progressive frame (rt_frame_advance): k_film_accumulate with the pixel's own sum kept in the FRAME's plane - own_plane[owned pixel], one
+// float4 per owned pixel of the whole shard, read and written on every pass (zero before the first step) - and never flushed: a pixel's own sum therefore sees its
+// samples in index order whatever steps, batches and passes they arrive in, and film_acc holds what other pixels' samples splat onto it only. k_frame_resolve adds
+// the two when the frame is read.
+static __global__ void __launch_bounds__(256) k_film_accumulate_frame(FrameParams fp, PassState ps, const float* __restrict__ filter_table, float4* film_acc, float4* own_plane) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  const int cw = fp.crop_x1 - fp.crop_x0;
+  const float inv_rx = 1.0f / fp.radius_x, inv_ry = 1.0f / fp.radius_y;
+  for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < ps.n_pixels; pix += stride) {
+    int x, y; unsigned long long pixel_index;
+    owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+    if (y >= fp.sb_y1) continue;
+    const float4 a = own_plane[fp.chunk_first + pix];
+    rgb3 own = mkc(a.x, a.y, a.z); float own_w = a.w;
+    unsigned scrubbed = 0;
+    film_add_pass(fp, ps, filter_table, film_acc, cw, inv_rx, inv_ry, pix, x, y, own, own_w, scrubbed);
+    own_plane[fp.chunk_first + pix] = make_float4(own.r, own.g, own.b, own_w);
+    if (scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
+  }
+}
+// rt_frame_read: one lane per cropped pixel. The pixel's sums = what other pixels' samples splatted onto it (film_acc) + its own sum (own_plane, if this shard owns
+// the pixel's row) - the value k_film_accumulate's flush leaves in film_acc - then k_film_finalize's RGB -> XYZ. what 0: (X, Y, Z, weight) as rt_render returns it;
+// 1: Film::write_image's pixel (film.rs:196-234): XYZ -> RGB, * (1 / weight) and max(0, .) where the weight is not zero, * scale, three floats; 2: that pixel through
+// write_image_png's quantisation (imageio.rs:52-63, spectrum.rs:387-393), three bytes. Reads the frame, writes `out` only.
+static __global__ void __launch_bounds__(256) k_frame_resolve(FrameParams fp, const float4* __restrict__ film_acc, const float4* __restrict__ own_plane, int what, float scale,
+                                                              void* __restrict__ out, unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  float4 a = film_acc[i];
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
+      const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+      const float4 o = own_plane[j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+      a = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
+    }
+  }
+  const float X = 0.412453f * a.x + 0.357580f * a.y + 0.180423f * a.z;
+  const float Y = 0.212671f * a.x + 0.715160f * a.y + 0.072169f * a.z;
+  const float Z = 0.019334f * a.x + 0.119193f * a.y + 0.950227f * a.z;
+  if (what == 0) { ((float4*)out)[i] = make_float4(X, Y, Z, a.w); return; }
+  float c[3] = {3.240479f * X - 1.537150f * Y - 0.498535f * Z, -0.969256f * X + 1.875991f * Y + 0.041556f * Z, 0.055648f * X - 0.204043f * Y + 1.057311f * Z};
+  if (a.w != 0.0f) {
+    const float inv = 1.0f / a.w;  // (-fno-fast-math: the correctly rounded quotient)
+    for (int k = 0; k < 3; ++k) { const float v = c[k] * inv; c[k] = 0.0f >= v ? 0.0f : v; }  // max(0, v) that keeps a NaN
+  }
+  for (int k = 0; k < 3; ++k) c[k] = c[k] * scale;
+  if (what == 1) { float* o = (float*)out + 3ull * i; o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; return; }
+  unsigned char* o = (unsigned char*)out + 3ull * i;
+  for (int k = 0; k < 3; ++k) {
+    const float v = c[k];
+    const float g = v <= 0.0031308f ? 12.92f * v : 1.055f * powf(v, 1.0f / 2.4f) - 0.055f;
+    const float q = 255.0f * g + 0.5f;
+    o[k] = q != q ? (unsigned char)0 : (unsigned char)fminf(fmaxf(q, 0.0f), 255.0f);
   }
 }
 // merge_film_tile's RGB -> XYZ (spectrum.rs:98-106); output (X, Y, Z, filter_weight_sum)

@@ -29,6 +29,8 @@ RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
 RT_SAMPLES_MAX = 1 << 27
 RT_QUERY_BSDF_LAUNCHED = 5  # rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
+RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8 = range(3)                                                    # rt_frame_read: what
+RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES = range(4)          # rt_frame_query: what
 BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
                        two_lobe_wide=RT_BSDF_FRONT_TWO_LOBE_WIDE)
 
@@ -363,6 +365,11 @@ class HostScene:
         _check(lib().rtxh_render(self.h, C.byref(p), C.c_void_p(stream), _p(film), C.byref(stats)), "render")
         return film, stats.as_dict()
 
+    def progressive(self, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False):
+        """The frame of `render` in steps (rt_frame_*): a ProgressiveFrame whose film can be read after any number of samples per pixel. `table_budget`: bytes the
+        frame may spend on sampler tables that stay resident between steps (None: the backend's default; too small: every step rebuilds them - same film)."""
+        return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels)
+
     def render_multi(self, devices, chunks_per_device=1, count_traversal=False, time_kernels=False, count_as_rendered=False, device_out=None):
         """The frame on several GPUs of this process (rt_multi_render): one host thread per entry of `devices`, chunks of tile rows pulled from a
         shared queue, rows gathered on devices[0]. Returns (film, total stats, [per-device stats]).
@@ -509,6 +516,88 @@ class HostScene:
         fint = np.zeros(total, np.float32)
         _check(lib().rtxh_light_distribution(self.h, _p(nv, C.c_int32), _p(func), _p(cdf), _p(fint)), "light_distribution")
         return dict(n_voxels=nv, func=func, cdf=cdf, func_int=fint)
+
+
+class ProgressiveFrame:
+    """A frame rendered in steps (HostScene.progressive). `advance(n)` renders the next n samples of every pixel; `film()`, `rgb()` and `display()` read the film as
+    it stands. A context manager; it keeps its scene alive and must be closed (or left) before the scene goes."""
+
+    def __init__(self, scene, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False):
+        L = lib()
+        L.rtxh_frame_end.argtypes = [C.c_void_p]
+        self.scene = scene   # (the frame's device state belongs to the scene's device: the scene must outlive it)
+        self.h = None
+        st = scene.setup(rank=rank, world_size=world_size)
+        cr = st["cropped"]
+        self.width, self.height = int(cr[2] - cr[0]), int(cr[3] - cr[1])
+        p = st["params"]
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        self.scale = float(p.film_scale)
+        h = C.c_void_p()
+        _check(L.rtxh_frame_begin(scene.h, C.byref(p), C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)), C.byref(h)), "frame_begin")
+        self.h = h
+
+    def close(self):
+        if self.h is not None:
+            lib().rtxh_frame_end(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _query(self, what):
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        v = C.c_uint64()
+        _check(lib().rtxh_frame_query(self.h, C.c_int32(what), C.byref(v)), "frame_query")
+        return int(v.value)
+
+    samples_done = property(lambda self: self._query(RT_FRAME_SAMPLES_DONE))
+    spp = property(lambda self: self._query(RT_FRAME_SPP))
+    tables_resident = property(lambda self: bool(self._query(RT_FRAME_TABLES_RESIDENT)))
+    state_bytes = property(lambda self: self._query(RT_FRAME_STATE_BYTES))
+
+    def advance(self, n, stream=0):
+        """Renders samples [samples_done, min(samples_done + n, spp)) of every pixel; returns the step's stats dict (all zero once the frame is finished)."""
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        stats = Stats()
+        _check(lib().rtxh_frame_advance(self.h, C.c_int32(int(n)), C.c_void_p(stream), C.byref(stats)), "frame_advance")
+        return stats.as_dict()
+
+    def _read(self, what, scale, channels, dtype, device_out, stream):
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        shape = (self.height, self.width, channels)
+        if device_out is not None:
+            assert tuple(device_out.shape) == shape and device_out.is_contiguous() and device_out.element_size() == np.dtype(dtype).itemsize
+            _check(lib().rtxh_frame_read(self.h, C.c_int32(what), C.c_float(scale), C.c_uint32(RT_FLAG_FILM_ON_DEVICE), C.c_void_p(stream), C.c_void_p(device_out.data_ptr())), "frame_read")
+            return device_out
+        out = np.zeros(shape, dtype)
+        _check(lib().rtxh_frame_read(self.h, C.c_int32(what), C.c_float(scale), C.c_uint32(0), C.c_void_p(stream), out.ctypes.data_as(C.c_void_p)), "frame_read")
+        return out
+
+    def film(self, device_out=None, stream=0):
+        """(H, W, 4) float32 (X, Y, Z, filter weight sum) of the samples so far: what `render` returns once the frame is finished."""
+        return self._read(RT_FRAME_XYZW, 1.0, 4, np.float32, device_out, stream)
+
+    def rgb(self, scale=None, device_out=None, stream=0):
+        """(H, W, 3) float32: Film::write_image's pixels (film_to_rgb of `film()`); `scale` defaults to the film's own."""
+        return self._read(RT_FRAME_RGB, self.scale if scale is None else float(scale), 3, np.float32, device_out, stream)
+
+    def display(self, scale=None, device_out=None, stream=0):
+        """(H, W, 3) uint8: the pixels of `rgb()` through the PNG writer's sRGB quantisation (rgb_to_png8)."""
+        return self._read(RT_FRAME_RGB8, self.scale if scale is None else float(scale), 3, np.uint8, device_out, stream)
 
 
 def copper():

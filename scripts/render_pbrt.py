@@ -1,12 +1,14 @@
 """Render a pbrt-v3 scene file on the GPU.
 
-    python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy]
+    python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
 8-bit sRGB PNG with write_image_png's quantisation (rc/imageio.rs:52-74). A .pfm name gets the linear film values.
 --samples out.npy: instead of an image, the radiance of every sample of the integrator's pixel bounds (rt_render_samples), float32
-[height, width, spp, 6] = L rgb as PathIntegrator::li returned it, 1.0 where the renderer scrubs the sample, the sample's film position."""
+[height, width, spp, 6] = L rgb as PathIntegrator::li returned it, 1.0 where the renderer scrubs the sample, the sample's film position.
+--preview-every N: the frame is rendered in steps of N samples per pixel (rt_frame_*) and the output image rewritten after each, as the reference's
+-p / --display shows the image while it renders; the last image written is the one the run without the flag writes."""
 import argparse
 import os
 import sys
@@ -22,6 +24,7 @@ def main():
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
     ap.add_argument("--samples", metavar="OUT.npy", default=None, help="write the per-sample radiance and film positions of the pixel bounds instead of an image")
+    ap.add_argument("--preview-every", type=int, default=0, metavar="N", help="rewrite the output image after every N samples per pixel")
     a = ap.parse_args()
     host.build()
     s = host.PbrtScene(a.scene)
@@ -34,15 +37,29 @@ def main():
         x0, y0, x1, y1 = s.samples_window()
         print(f"{a.samples}: pixels [{x0}, {x1}) x [{y0}, {y1}), {rad.shape[2]} samples each, {int(rad[..., 3].sum())} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
         return
-    film, stats = s.render()
     out = a.out or s.film_filename
-    rgb = host.film_to_rgb(film, s.params.film_scale)
-    if out.endswith(".pfm"):
-        write_pfm(out, rgb)
-    elif out.endswith(".png"):
-        write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
-    else:
+    if not out.endswith((".pfm", ".png")):
         raise SystemExit("Unsupported file format")   # rc/imageio.rs:47-49 (EXR output is not written here)
+
+    def write(film):
+        rgb = host.film_to_rgb(film, s.params.film_scale)
+        if out.endswith(".pfm"):
+            write_pfm(out, rgb)
+        else:
+            write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
+
+    if a.preview_every > 0:
+        stats = {"ms_total": 0.0}
+        with s.progressive() as frame:
+            spp = frame.spp
+            while frame.samples_done < spp:
+                stats["ms_total"] += frame.advance(a.preview_every)["ms_total"]
+                film = frame.film()
+                write(film)
+                print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
+    else:
+        film, stats = s.render()
+        write(film)
     print(f"{out}: {film.shape[1]}x{film.shape[0]}, {s.params.spp} spp, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
 
 
