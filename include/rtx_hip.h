@@ -282,6 +282,7 @@ typedef struct rt_stats {
                                 (rc/renderer.rs:83-84) - instead of the pixel-keyed one: one lane per tile walks the reference's loop (slow by construction; for the configuration
                                 the reference itself runs). The film then equals the oracle's SAMPLER_REF mode sample for sample: weights exact, radiance inside the image gate.
                                 Single device, plain-triangle scenes; stats: camera_rays and the three ray counts. */
+#define RT_FLAG_FRAME_STATS 32u /* rt_frame_begin only (other entry points ignore it): the frame keeps per-pixel luminance moments and accepts rt_frame_advance_adaptive */
 
 typedef struct rt_scene rt_scene;
 
@@ -426,13 +427,37 @@ int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_de
  *   out: host memory, or device memory with RT_FLAG_FILM_ON_DEVICE in `flags`.
  * rt_frame_query: RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP (rounded), RT_FRAME_TABLES_RESIDENT (0 / 1), RT_FRAME_STATE_BYTES (device bytes the frame holds).
  * Any number of frames may live on one scene; their steps and rt_render calls on that scene take turns on the scene's mutex and change no byte of each other.
- * A FRAME MUST BE ENDED BEFORE ITS SCENE IS DESTROYED. rt_frame_end(NULL) is a no-op. Single device; rt_shard is honoured (rows of other ranks read as zero). */
-enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2 };
-enum { RT_FRAME_SAMPLES_DONE = 0, RT_FRAME_SPP = 1, RT_FRAME_TABLES_RESIDENT = 2, RT_FRAME_STATE_BYTES = 3 };
+ * A FRAME MUST BE ENDED BEFORE ITS SCENE IS DESTROYED. rt_frame_end(NULL) is a no-op. Single device; rt_shard is honoured (rows of other ranks read as zero).
+ *
+ * Frame statistics and adaptive steps (opt-in: a frame begun without RT_FLAG_FRAME_STATS launches exactly the kernels described above).
+ * RT_FLAG_FRAME_STATS gives the frame one more plane, 32 B per owned pixel, zero at begin and counted in RT_FRAME_STATE_BYTES: {double sum_y, double sum_y2,
+ *   uint32 n, padding}. The frame's film kernel then adds, for every sample of the pixel that was traced (inside pixel_bounds and the sample rows, and taken by
+ *   the pixel), in sample-index order: y = luminance (float32: 0.212671 r + 0.715160 g + 0.072169 b, left to right, no contraction) of the value the film splats
+ *   - after the renderer's scrubbing (a scrubbed sample counts as 0) and the max_sample_luminance clamp -, n += 1, sum_y += (double)y, sum_y2 += (double)y *
+ *   (double)y. One lane owns a pixel's entry: no atomics, and the sums are those of a sequential loop. The film itself is unchanged by the flag, byte for byte.
+ * rt_frame_read(RT_FRAME_STATS): W*H*3 doubles over the cropped pixel bounds, (n, sum_y, sum_y2) per pixel; zeros in rows of other ranks and before the first
+ *   step; scale ignored; RT_ERR_INVALID on a frame begun without the flag.
+ * rt_frame_advance_adaptive offers sample indices [done, min(done + n_samples, spp)) as rt_frame_advance does - afterwards `done` is that end - but a pixel takes
+ *   them only if it is ACTIVE. Activity is decided once per call, before any path work, from the plane as it stands, in IEEE double arithmetic:
+ *       active = inside pixel_bounds and the sample bounds and (n < max(min_samples, 2) or se > threshold * max(mean, floor_y))
+ *       mean = sum_y / n,  var = max(0, sum_y2 - sum_y * mean) / (n - 1),  se = sqrt(var / n)
+ *   An inactive pixel's samples are never traced (they cost one ray-generation lane and one film-kernel read). When no pixel is active no path kernel is
+ *   launched, `done` still advances and the stats are zero. RT_ERR_INVALID before any device work: a NULL frame, a frame without RT_FLAG_FRAME_STATS,
+ *   n_samples <= 0, min_samples < 0, a NaN or negative threshold or floor_y (+inf is legal: no pixel past min_samples is active). A finished frame: RT_OK, zeroed
+ *   stats. rt_frame_advance on a stats frame works as before - every pixel takes the samples - and updates the moments.
+ *   A FRAME THAT USED ADAPTIVE STEPS IS NO LONGER rt_render'S FRAME. Each pixel is still sum(w L) / sum(w) over the samples taken - the pixel-keyed sampler
+ *   shuffles a pixel's sample order at random, so any subset of its indices is as good a sample set as a prefix - and a wide filter splats the taken samples as
+ *   before; but which pixels go on sampling depends on their own estimates, which gives the small bias every variance-driven sampler has (a pixel whose early
+ *   samples happen to agree stops early). RT_FRAME_SAMPLES_DONE then means "sample indices offered", not "samples every pixel holds".
+ * rt_frame_query, further: RT_FRAME_SAMPLES_TAKEN - the sum of camera_rays over the frame's steps (kept on the host); RT_FRAME_ACTIVE_PIXELS - the number of
+ *   active pixels of the last adaptive step, 0 before one has run. */
+enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2, RT_FRAME_STATS = 3 };
+enum { RT_FRAME_SAMPLES_DONE = 0, RT_FRAME_SPP = 1, RT_FRAME_TABLES_RESIDENT = 2, RT_FRAME_STATE_BYTES = 3, RT_FRAME_SAMPLES_TAKEN = 4, RT_FRAME_ACTIVE_PIXELS = 5 };
 typedef struct rt_frame rt_frame;
 int rt_frame_begin(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
                    const rt_shard* shard /* may be NULL */, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out);
 int rt_frame_advance(rt_frame* frame, int32_t n_samples, void* stream, rt_stats* stats /* of this step, may be NULL */);
+int rt_frame_advance_adaptive(rt_frame* frame, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* stream, rt_stats* stats /* of this step, may be NULL */);
 int rt_frame_read(rt_frame* frame, int32_t what, float scale, uint32_t flags, void* stream, void* out);
 int rt_frame_query(rt_frame* frame, int32_t what, uint64_t* value);
 void rt_frame_end(rt_frame* frame);

@@ -151,6 +151,9 @@ int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream
 typedef struct rtxh_frame rtxh_frame;
 int rtxh_frame_begin(rtxh_scene*, const rtxh_render_params*, uint64_t table_budget_bytes, rtxh_frame** out);
 int rtxh_frame_advance(rtxh_frame*, int32_t n_samples, void* hip_stream, rt_stats* stats /* of this step, may be NULL */);
+/* rt_frame_advance_adaptive of a frame begun with RT_FLAG_FRAME_STATS among the parameters' flags: only pixels whose luminance estimate is still noisier than
+ * threshold (standard error over max(mean, floor_y)), or that hold fewer than max(min_samples, 2) samples, take the step's samples. */
+int rtxh_frame_advance_adaptive(rtxh_frame*, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* hip_stream, rt_stats* stats /* of this step, may be NULL */);
 int rtxh_frame_read(rtxh_frame*, int32_t what, float scale, uint32_t flags, void* hip_stream, void* out);
 int rtxh_frame_query(rtxh_frame*, int32_t what, uint64_t* value);
 void rtxh_frame_end(rtxh_frame*);

@@ -1012,7 +1012,11 @@ struct rt_frame {
   DevBuf scrambles, perms;
   unsigned long long batch_pixels = 0, lead_pixels = 0;
   std::vector<size_t> scr_off, perm_off;
-  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes; }
+  // RT_FLAG_FRAME_STATS: [owned pixel] luminance moments (32 B, zero at begin), the byte mask of the last adaptive step and the word that counts its set bytes
+  bool stats = false;
+  DevBuf moments, active, n_active;
+  unsigned long long samples_taken = 0, active_pixels = 0;  // sum of camera_rays over the steps; set bytes of the last adaptive step's mask
+  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes; }
 };
 static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u * (size_t)(owned_pixels / 4096u + 4u); }  // alignment room: a batch holds >= 4096 pixels, plus a leading and a last one
 
@@ -1020,9 +1024,11 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // samples_rad / samples_pf (k_sample_store) instead of filtering them into the film (k_film_accumulate); film_xyzw is then unused.
 // fr != NULL: the step of rt_frame_advance - samples [fr->done, step_end) of every owned pixel through the same batches, passes, kernels and queues, filtered into the
 // FRAME's sums by k_film_accumulate_frame (nothing is zeroed, nothing is finalised or copied out), with the frame's resident sampler tables where it has them.
+// A frame with RT_FLAG_FRAME_STATS launches k_film_accumulate_frame_stats instead. active_mask != NULL: the step of rt_frame_advance_adaptive, which holds the scene's
+// mutex already (have_lock) - k_raygen_masked marks the samples of pixels whose byte is 0 out of bounds, so every pass takes the route of a cropping pixel_bounds.
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
-                        rt_frame* fr = nullptr, unsigned step_end = 0) {
+                        rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false) {
   const bool samples = samples_rad != nullptr;
   // the window of rt_render_samples: pixel_bounds inside the sample bounds, and its size - checked before any device work
   const int wx0 = std::max(path->pixel_bounds[0], film->sample_bounds[0]), wy0 = std::max(path->pixel_bounds[1], film->sample_bounds[1]);
@@ -1035,7 +1041,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * spp_r;
     if (spp_r > 16384ull || n_window_samples > (unsigned long long)RT_SAMPLES_MAX) return fail(RT_ERR_INVALID, "rt_render_samples: the window holds more than RT_SAMPLES_MAX (2^27) samples");
   }
-  std::lock_guard<std::mutex> render_lock(s->render_mutex);
+  std::unique_lock<std::mutex> render_lock(s->render_mutex, std::defer_lock);
+  if (!have_lock) render_lock.lock();
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t stream = (hipStream_t)stream_;
   const unsigned spp = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
@@ -1110,7 +1117,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     return RT_OK;
   }
   // pixel_bounds (path.rs:30) that do not crop the sample bounds: every generated sample is traced
-  const bool all_in_bounds = path->pixel_bounds[0] <= film->sample_bounds[0] && path->pixel_bounds[2] >= film->sample_bounds[2] &&
+  const bool all_in_bounds = !active_mask && path->pixel_bounds[0] <= film->sample_bounds[0] && path->pixel_bounds[2] >= film->sample_bounds[2] &&
                              path->pixel_bounds[1] <= film->sample_bounds[1] && path->pixel_bounds[3] >= film->sample_bounds[3];
   // batch / pass sizing. A batch is a range of owned pixels whose sampler tables (2*dims u16 per sample) are built
   // at once; it is rendered in passes of n_samples consecutive samples of all its pixels, ~2^29 paths (211 GB of path state) per pass.
@@ -1315,7 +1322,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       static const bool tail_off = env_is("RTX_DEAD_TAIL", '0');  // measurement knob: cast the rays nothing reads as well
       ps.skip_dead_tail = (!tail_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
       tm.begin(&stats.ms_raygen);
-      hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
+      if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
+      else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
       tm.end();
       for (int bounce = 0; bounce <= fp.max_depth; ++bounce) {
         ps.cnt_in = cb + (size_t)bounce * RT_NQ * RT_QSHARDS * RT_CNT_STRIDE; ps.cnt_out = cb + (size_t)(bounce + 1) * RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;
@@ -1375,6 +1383,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       }
       tm.begin(&stats.ms_film);
       if (samples) hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, ps, wx0, wy0, wx1 - wx0, d_samples_rad, d_samples_pf);
+      else if (fr && fr->stats) hipLaunchKernelGGL(k_film_accumulate_frame_stats, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), fr->moments.as<PixMoments>());
       else if (fr) hipLaunchKernelGGL(k_film_accumulate_frame, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>());
       else hipLaunchKernelGGL(k_film_accumulate, dim3(pgrid), dim3(256), 0, stream, fp, ps, s->filter_table.as<float>(), s->film_acc.as<float4>());
       tm.end();
@@ -1474,6 +1483,15 @@ extern "C" int rt_frame_begin(rt_scene* s, const rt_camera* cam, const rt_film_d
   HIP_TRY(hipMemset(fr->film_acc.p, 0, film_bytes));
   HIP_TRY(hipMemset(fr->own_acc.p, 0, own_bytes));
   HIP_TRY(hipMemcpy(fr->filter_table.p, film->filter_table, 1024, hipMemcpyHostToDevice));
+  if (flags & RT_FLAG_FRAME_STATS) {  // the moments plane, and the mask an adaptive step writes before its ray generation
+    const size_t mom_bytes = std::max<size_t>((size_t)fr->owned_pixels * sizeof(PixMoments), sizeof(PixMoments)), mask_bytes = std::max<size_t>((size_t)fr->owned_pixels, 16);
+    if (fr->moments.ensure(mom_bytes) != hipSuccess || fr->active.ensure(mask_bytes) != hipSuccess || fr->n_active.ensure(16) != hipSuccess) {
+      (void)hipGetLastError(); return fail(RT_ERR_OOM, "rt_frame_begin: not enough device memory for the frame's statistics plane");
+    }
+    HIP_TRY(hipMemset(fr->moments.p, 0, mom_bytes));
+    HIP_TRY(hipMemset(fr->active.p, 0, mask_bytes));
+    fr->stats = true;
+  }
   if (fr->owned_pixels > 0 && perm_bytes + scr_bytes <= budget) {
     const size_t slack = frame_table_slack(fr->owned_pixels);
     if (fr->scrambles.ensure((size_t)scr_bytes + slack) == hipSuccess && fr->perms.ensure((size_t)perm_bytes + slack) == hipSuccess) fr->resident = true;
@@ -1488,31 +1506,77 @@ extern "C" int rt_frame_advance(rt_frame* fr, int32_t n_samples, void* stream, r
   if (n_samples <= 0) return fail(RT_ERR_INVALID, "rt_frame_advance: n_samples must be positive");
   if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
   const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
-  const int rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, stats_out, nullptr, nullptr, fr, end);
-  if (rc == RT_OK) fr->done = end;
+  rt_stats st{};
+  const int rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, &st, nullptr, nullptr, fr, end);
+  if (rc == RT_OK) { fr->done = end; fr->samples_taken += st.camera_rays; if (stats_out) *stats_out = st; }
   return rc;
+}
+// The film geometry of a frame, for the kernels that walk its pixels outside a step (k_frame_resolve, k_frame_stats_read, k_frame_active)
+static FrameParams frame_pixel_params(const rt_frame* fr) {
+  const rt_film_desc& film = fr->film;
+  const int W = film.sample_bounds[2] - film.sample_bounds[0], H = film.sample_bounds[3] - film.sample_bounds[1];
+  FrameParams fp{};
+  fp.crop_x0 = film.cropped_pixel_bounds[0]; fp.crop_y0 = film.cropped_pixel_bounds[1]; fp.crop_x1 = film.cropped_pixel_bounds[2]; fp.crop_y1 = film.cropped_pixel_bounds[3];
+  fp.sb_x0 = film.sample_bounds[0]; fp.sb_y0 = film.sample_bounds[1]; fp.sb_x1 = film.sample_bounds[2]; fp.sb_y1 = film.sample_bounds[3];
+  fp.pb_x0 = fr->path.pixel_bounds[0]; fp.pb_y0 = fr->path.pixel_bounds[1]; fp.pb_x1 = fr->path.pixel_bounds[2]; fp.pb_y1 = fr->path.pixel_bounds[3];
+  fp.rank = fr->shard.rank; fp.world = fr->shard.world_size;
+  const int band = RT_SHARD_ROWS(H, fp.world);
+  fp.shard_log2 = 0; while ((1 << fp.shard_log2) < band) fp.shard_log2 += 1;
+  fp.w_recip = W > 1 ? (unsigned)((1ull << 32) / (unsigned long long)W) : 0u;
+  return fp;
+}
+// One adaptive step: k_frame_active decides every owned pixel from its moments as they stand, then the step of rt_frame_advance runs with that mask in front of its
+// ray generation. The scene's mutex is held from the mask to the last film kernel, so no other step of the frame can move the moments in between.
+extern "C" int rt_frame_advance_adaptive(rt_frame* fr, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* stream_, rt_stats* stats_out) {
+  if (!fr) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: null frame");
+  if (!fr->stats) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: the frame was begun without RT_FLAG_FRAME_STATS");
+  if (n_samples <= 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: n_samples must be positive");
+  if (min_samples < 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: min_samples must not be negative");
+  if (!(threshold >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: threshold must be a number >= 0 (+inf: no pixel past min_samples)");
+  if (!(floor_y >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: floor_y must be a number >= 0");
+  if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
+  const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
+  rt_scene* s = fr->scene;
+  std::lock_guard<std::mutex> render_lock(s->render_mutex);
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  unsigned long long n_active = 0;
+  if (fr->owned_pixels > 0) {
+    const FrameParams fp = frame_pixel_params(fr);
+    HIP_TRY(hipMemsetAsync(fr->n_active.p, 0, 8, stream));
+    hipLaunchKernelGGL(k_frame_active, dim3((unsigned)((fr->owned_pixels + 255) / 256)), dim3(256), 0, stream, fp, fr->moments.as<PixMoments>(), fr->owned_pixels,
+                       (unsigned)std::max<int32_t>(min_samples, 2), (double)threshold, (double)floor_y, fr->active.as<unsigned char>(), fr->n_active.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&n_active, fr->n_active.p, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  fr->active_pixels = n_active;
+  rt_stats st{};
+  if (n_active > 0) {  // (no active pixel: no path kernel, no film kernel - the step only moves `done`)
+    const int rc = render_frame(s, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, &st, nullptr, nullptr, fr, end,
+                                fr->active.as<unsigned char>(), true);
+    if (rc != RT_OK) return rc;
+  }
+  fr->done = end; fr->samples_taken += st.camera_rays;
+  if (stats_out) *stats_out = st;
+  return RT_OK;
 }
 extern "C" int rt_frame_read(rt_frame* fr, int32_t what, float scale, uint32_t flags, void* stream_, void* out) {
   if (!fr || !out) return fail(RT_ERR_INVALID, "rt_frame_read: null argument");
-  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
+  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
+  if (what == RT_FRAME_STATS && !fr->stats) return fail(RT_ERR_INVALID, "rt_frame_read: RT_FRAME_STATS needs a frame begun with RT_FLAG_FRAME_STATS");
   rt_scene* s = fr->scene;
   std::lock_guard<std::mutex> render_lock(s->render_mutex);  // (steps of this frame on other threads, and the staging buffer)
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t stream = (hipStream_t)stream_;
-  const rt_film_desc& film = fr->film;
-  const int H = film.sample_bounds[3] - film.sample_bounds[1];
-  FrameParams fp{};
-  fp.crop_x0 = film.cropped_pixel_bounds[0]; fp.crop_y0 = film.cropped_pixel_bounds[1]; fp.crop_x1 = film.cropped_pixel_bounds[2]; fp.crop_y1 = film.cropped_pixel_bounds[3];
-  fp.sb_x0 = film.sample_bounds[0]; fp.sb_y0 = film.sample_bounds[1]; fp.sb_x1 = film.sample_bounds[2]; fp.sb_y1 = film.sample_bounds[3];
-  fp.rank = fr->shard.rank; fp.world = fr->shard.world_size;
-  const int band = RT_SHARD_ROWS(H, fp.world);
-  fp.shard_log2 = 0; while ((1 << fp.shard_log2) < band) fp.shard_log2 += 1;
+  const FrameParams fp = frame_pixel_params(fr);
   const unsigned long long n = (unsigned long long)(fp.crop_x1 - fp.crop_x0) * (unsigned long long)(fp.crop_y1 - fp.crop_y0);
-  const size_t bytes = (size_t)n * (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3));
+  const size_t bytes = (size_t)n * (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
   const bool on_device = (flags & RT_FLAG_FILM_ON_DEVICE) != 0;
-  if (!on_device) HIP_TRY(fr->out.ensure((size_t)n * 16));
+  if (!on_device) HIP_TRY(fr->out.ensure((size_t)n * (what == RT_FRAME_STATS ? 24 : 16)));  // (ensure only ever grows the staging buffer)
   void* const d_out = on_device ? out : fr->out.p;
-  hipLaunchKernelGGL(k_frame_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), (int)what, scale, d_out, n);
+  if (what == RT_FRAME_STATS) hipLaunchKernelGGL(k_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->moments.as<PixMoments>(), (double*)d_out, n);
+  else hipLaunchKernelGGL(k_frame_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), (int)what, scale, d_out, n);
   HIP_TRY(hipGetLastError());
   if (!on_device) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
@@ -1525,6 +1589,8 @@ extern "C" int rt_frame_query(rt_frame* fr, int32_t what, uint64_t* value) {
     case RT_FRAME_SPP: *value = fr->spp; return RT_OK;
     case RT_FRAME_TABLES_RESIDENT: *value = fr->resident ? 1u : 0u; return RT_OK;
     case RT_FRAME_STATE_BYTES: *value = fr->state_bytes(); return RT_OK;
+    case RT_FRAME_SAMPLES_TAKEN: *value = fr->samples_taken; return RT_OK;
+    case RT_FRAME_ACTIVE_PIXELS: *value = fr->active_pixels; return RT_OK;
     default: return fail(RT_ERR_INVALID, "rt_frame_query: unknown query");
   }
 }

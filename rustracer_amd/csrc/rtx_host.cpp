@@ -1316,6 +1316,11 @@ int rtxh_frame_advance(rtxh_frame* f, int32_t n_samples, void* stream, rt_stats*
   g_err.clear();
   return rt_frame_advance(f->f, n_samples, stream, stats);
 }
+int rtxh_frame_advance_adaptive(rtxh_frame* f, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* stream, rt_stats* stats) {
+  if (!f) return fail(RT_ERR_INVALID, "rtxh_frame_advance_adaptive: null frame");
+  g_err.clear();
+  return rt_frame_advance_adaptive(f->f, n_samples, threshold, floor_y, min_samples, stream, stats);
+}
 int rtxh_frame_read(rtxh_frame* f, int32_t what, float scale, uint32_t flags, void* stream, void* out) {
   if (!f || !out) return fail(RT_ERR_INVALID, "null argument");
   g_err.clear();

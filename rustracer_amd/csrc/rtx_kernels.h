@@ -765,46 +765,16 @@ RT_DEV CameraRay generate_camera_ray(const FrameParams& fp, f2 p_film, f2 p_lens
   return r;
 }
 
+// k_raygen_masked (the adaptive step of a progressive frame, rt_frame_advance_adaptive): active[owned pixel] != 0 where the pixel takes the step's samples. An
+// inactive pixel's samples are out of bounds - no path, RT_STATE_OUT_OF_BOUNDS in lacc.w, skipped by the film kernel -, so such a pass always appends through
+// block_push (PassState::all_in_bounds = 0).
 static __global__ void __launch_bounds__(256) k_raygen(FrameParams fp, PassState ps) {
-  const unsigned stride = gridDim.x * blockDim.x;
-  const Tables tb = tables_of(ps);
-  unsigned n_camera = 0;
-  for (unsigned base = blockIdx.x * blockDim.x; base < ps.cap; base += stride) {
-    const unsigned pid = base + threadIdx.x;
-    bool in_bounds = false;
-    CameraRay cr; unsigned long long rng_state = 0ull;
-    if (pid < ps.cap) {
-      unsigned sl, pix; split_path_id(ps, pid, sl, pix); const unsigned s = ps.s0 + sl;
-      int x, y; unsigned long long pixel_index;
-      owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
-      in_bounds = y < fp.sb_y1 && x >= fp.pb_x0 && x < fp.pb_x1 && y >= fp.pb_y0 && y < fp.pb_y1;  // renderer.rs:103
-      // get_camera_sample (zerotwosequence.rs:182-192): 2D#0 film, 1D#0 time, 2D#1 lens
-      f2 o = table_2d(tb, pix, 0, s);
-      f2 p_film = mk2((float)x + o.x, (float)y + o.y);
-      const f2 p_lens = fp.lens_radius > 0.0f ? table_2d(tb, pix, 1, s) : mk2(0.0f, 0.0f);  // (a pinhole camera never reads it, and a frame then does not build it: table_groups_frame)
-      cr = generate_camera_ray(fp, p_film, p_lens, 1.0f / sqrtf((float)ps.spp));
-      Pcg32 rng; rng.set_sequence(pixel_index * (unsigned long long)ps.spp + s + (1ull << 32));  // keyed per-sample stream
-      rng_state = rng.state;
-      ps.lacc[pid] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(in_bounds ? 0u : RT_STATE_OUT_OF_BOUNDS));
-      ps.pfilm[pid] = make_float2(p_film.x, p_film.y);
-    }
-    n_camera += in_bounds ? 1u : 0u;
-    unsigned slot = pid;  // every sample traced: path i is entry i is slot i
-    if (!ps.all_in_bounds) {
-      const int ci[1] = {0}; const bool pr[1] = {in_bounds}; unsigned sl_[1];
-      block_push<1>(ps.cnt_out, ps.shard_cap, ci, pr, sl_);
-      slot = sl_[0];
-    }
-    if (in_bounds) {  // the path's travelling records, at its slot of bounce 0's queue
-      ps.out.o[slot] = make_float4(cr.o.x, cr.o.y, cr.o.z, kInf);
-      ps.out.d[slot] = make_float4(cr.d.x, cr.d.y, cr.d.z, 0.0f);
-      if (!RT_FRESH_BETA(ps)) ps.out.beta[slot] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);  // (left out: bounce 0 rebuilds the record from the slot, PassState::fresh)
-      if (!RT_FRESH_ST(ps)) ps.out.st[slot] = make_uint4(pack_state(0, false, 1, 2), pid, (unsigned)rng_state, (unsigned)(rng_state >> 32));
-    }
-  }
-  // camera samples actually generated: calls of PathIntegrator::li (samples outside pixel_bounds are skipped, renderer.rs:103)
-  for (int off = 32; off > 0; off >>= 1) n_camera += __shfl_down(n_camera, off);
-  if ((threadIdx.x & 63u) == 0u && n_camera) atomicAdd(&ps.stats[ST_CAMERA], (unsigned long long)n_camera);
+#include "rtx_raygen_body.inl"
+}
+static __global__ void __launch_bounds__(256) k_raygen_masked(FrameParams fp, PassState ps, const unsigned char* __restrict__ active) {
+#define RT_RAYGEN_MASKED
+#include "rtx_raygen_body.inl"
+#undef RT_RAYGEN_MASKED
 }
 
 // Without the mask evaluator a GENERAL trace kernel's largest part is the quadric test (134 VGPRs inline) or the nested instance walk (133): bound to four
@@ -2318,8 +2288,13 @@ __global__ void __launch_bounds__(256) k_resolve(DScene sc, PassState ps) {
 // splats onto other pixels (filter radius > 0.5, or a sample exactly on a pixel edge) go through float
 // atomics. film_acc: float4 (R, G, B sums, weight sum) per cropped pixel.
 // One sample of pixel (x, y) into the pixel's own sum and its neighbours' (FilmTile::add_sample): shared by the film kernel of rt_render and the one of rt_frame_advance.
+// STATS (a frame begun with RT_FLAG_FRAME_STATS): the sample's luminance y = lum_y(Lc) - of the value that is splatted: scrubbed samples count as 0, the clamp
+// applies - also goes into the pixel's moments, n += 1, sum_y += y, sum_y2 += y * y in double (y * y is exact: 48 bits).
+struct alignas(16) PixMoments { double sum_y, sum_y2; unsigned n, pad[3]; };  // 32 B per owned pixel
+struct MomentSums { double sum_y, sum_y2; unsigned n; };                        // ... in registers while a lane walks the pixel's samples
+template <bool STATS = false>
 RT_DEV void film_add_sample(const FrameParams& fp, const float* __restrict__ filter_table, float4* film_acc, int cw, float inv_rx, float inv_ry, int x, int y,
-                            const float4 l4, const float2 pf, rgb3& own, float& own_w, unsigned& scrubbed) {
+                            const float4 l4, const float2 pf, rgb3& own, float& own_w, unsigned& scrubbed, MomentSums* mom = nullptr) {
   if (__float_as_uint(l4.w) & RT_STATE_OUT_OF_BOUNDS) return;
   rgb3 c = mkc(l4.x, l4.y, l4.z);
   bool bad = false;  // renderer.rs:115-126
@@ -2328,6 +2303,7 @@ RT_DEV void film_add_sample(const FrameParams& fp, const float* __restrict__ fil
   if (isinf(lum_y(c))) { c = mkc(0, 0, 0); bad = true; }
   scrubbed += bad;
   rgb3 Lc = lum_y(c) > fp.max_sample_luminance ? c * fp.max_sample_luminance / lum_y(c) : c;
+  if constexpr (STATS) { const double yl = (double)lum_y(Lc); mom->n += 1u; mom->sum_y += yl; mom->sum_y2 += yl * yl; }
   float dx = pf.x - 0.5f, dy = pf.y - 0.5f;
   float p0x = ceilf(dx - fp.radius_x), p0y = ceilf(dy - fp.radius_y);
   float p1x = floorf(dx + fp.radius_x + 1.0f), p1y = floorf(dy + fp.radius_y + 1.0f);
@@ -2353,8 +2329,9 @@ RT_DEV void film_add_sample(const FrameParams& fp, const float* __restrict__ fil
 // Round 6: the records of EIGHT samples are requested together, then added in order. A pixel's samples are one lane's sequential loop (the reference's order of a
 // pixel's sum); with one load per iteration a launch over few pixels - a shard's batch of 2^15 on an 8-GPU frame - waited a memory round trip per sample (1024 of them:
 // 3.8 ms of film time per S1 shard against 1.3 for its share of the whole frame's). Same loads, same adds, same order.
+template <bool STATS = false>
 RT_DEV void film_add_pass(const FrameParams& fp, const PassState& ps, const float* __restrict__ filter_table, float4* film_acc, int cw, float inv_rx, float inv_ry,
-                          unsigned pix, int x, int y, rgb3& own, float& own_w, unsigned& scrubbed) {
+                          unsigned pix, int x, int y, rgb3& own, float& own_w, unsigned& scrubbed, MomentSums* mom = nullptr) {
   constexpr unsigned KF = 8;
   for (unsigned s0 = 0; s0 < ps.n_samples; s0 += KF) {
     float4 lb[KF]; float2 pb[KF];
@@ -2365,7 +2342,7 @@ RT_DEV void film_add_pass(const FrameParams& fp, const PassState& ps, const floa
       lb[k] = ps.lacc[pid]; pb[k] = ps.pfilm[pid];
     }
 #pragma unroll
-    for (unsigned k = 0; k < KF; ++k) if (s0 + k < ps.n_samples) film_add_sample(fp, filter_table, film_acc, cw, inv_rx, inv_ry, x, y, lb[k], pb[k], own, own_w, scrubbed);
+    for (unsigned k = 0; k < KF; ++k) if (s0 + k < ps.n_samples) film_add_sample<STATS>(fp, filter_table, film_acc, cw, inv_rx, inv_ry, x, y, lb[k], pb[k], own, own_w, scrubbed, mom);
   }
 }
 static __global__ void __launch_bounds__(256) k_film_accumulate(FrameParams fp, PassState ps, const float* __restrict__ filter_table, float4* film_acc) {
@@ -2408,6 +2385,70 @@ static __global__ void __launch_bounds__(256) k_film_accumulate_frame(FrameParam
     own_plane[fp.chunk_first + pix] = make_float4(own.r, own.g, own.b, own_w);
     if (scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
   }
+}
+// ... of a frame begun with RT_FLAG_FRAME_STATS: the same walk, and the pixel's luminance moments (moments[owned pixel], zero at rt_frame_begin) updated by the one
+// lane that owns the pixel - no atomics - with its samples in index order.
+static __global__ void __launch_bounds__(256) k_film_accumulate_frame_stats(FrameParams fp, PassState ps, const float* __restrict__ filter_table, float4* film_acc, float4* own_plane,
+                                                                            PixMoments* moments) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  const int cw = fp.crop_x1 - fp.crop_x0;
+  const float inv_rx = 1.0f / fp.radius_x, inv_ry = 1.0f / fp.radius_y;
+  for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < ps.n_pixels; pix += stride) {
+    int x, y; unsigned long long pixel_index;
+    owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+    if (y >= fp.sb_y1) continue;
+    const float4 a = own_plane[fp.chunk_first + pix];
+    rgb3 own = mkc(a.x, a.y, a.z); float own_w = a.w;
+    PixMoments* const pm = &moments[fp.chunk_first + pix];
+    MomentSums m = {pm->sum_y, pm->sum_y2, pm->n};
+    unsigned scrubbed = 0;
+    film_add_pass<true>(fp, ps, filter_table, film_acc, cw, inv_rx, inv_ry, pix, x, y, own, own_w, scrubbed, &m);
+    own_plane[fp.chunk_first + pix] = make_float4(own.r, own.g, own.b, own_w);
+    pm->sum_y = m.sum_y; pm->sum_y2 = m.sum_y2; pm->n = m.n;  // (the padding stays the zero of rt_frame_begin)
+    if (scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
+  }
+}
+// rt_frame_advance_adaptive, before any path work of the step: one lane per owned pixel of the shard decides from the pixel's moments as they stand whether it
+// takes the step's samples. active = inside pixel_bounds and the sample rows and (n < min_n or se > threshold * max(mean, floor_y)), mean = sum_y / n,
+// var = max(0, sum_y2 - sum_y * mean) / (n - 1), se = sqrt(var / n): IEEE double divisions and square root (min_n >= 2 keeps n - 1 > 0). One byte per owned pixel;
+// n_active[0] counts the set bytes (one atomic per wave).
+static __global__ void __launch_bounds__(256) k_frame_active(FrameParams fp, const PixMoments* __restrict__ moments, unsigned long long owned_pixels, unsigned min_n, double threshold,
+                                                             double floor_y, unsigned char* __restrict__ active, unsigned long long* __restrict__ n_active) {
+  const unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool on = false;
+  if (k < owned_pixels) {
+    int x, y; unsigned long long pixel_index;
+    owned_pixel(fp, k, x, y, pixel_index);
+    if (y < fp.sb_y1 && x >= fp.pb_x0 && x < fp.pb_x1 && y >= fp.pb_y0 && y < fp.pb_y1) {
+      const double sum_y = moments[k].sum_y, sum_y2 = moments[k].sum_y2; const unsigned cnt = moments[k].n;
+      if (cnt < min_n) on = true;
+      else {
+        const double n = (double)cnt, mean = sum_y / n;
+        const double d = sum_y2 - sum_y * mean, var = (d > 0.0 ? d : 0.0) / (n - 1.0), se = sqrt(var / n);
+        on = se > threshold * (mean > floor_y ? mean : floor_y);
+      }
+    }
+    active[k] = on ? (unsigned char)1 : (unsigned char)0;
+  }
+  const unsigned long long ballot = __ballot(on);
+  if (__lane_id() == 0u && ballot) atomicAdd(n_active, (unsigned long long)__popcll(ballot));
+}
+// rt_frame_read(RT_FRAME_STATS): one lane per cropped pixel, (n, sum_y, sum_y2) as three doubles; zeros where another rank owns the pixel's row.
+static __global__ void __launch_bounds__(256) k_frame_stats_read(FrameParams fp, const PixMoments* __restrict__ moments, double* __restrict__ out, unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel, as in k_frame_resolve
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
+      const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+      const PixMoments* const m = &moments[j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+      v0 = (double)m->n; v1 = m->sum_y; v2 = m->sum_y2;
+    }
+  }
+  out[3ull * i] = v0; out[3ull * i + 1ull] = v1; out[3ull * i + 2ull] = v2;
 }
 // rt_frame_read: one lane per cropped pixel. The pixel's sums = what other pixels' samples splatted onto it (film_acc) + its own sum (own_plane, if this shard owns
 // the pixel's row) - the value k_film_accumulate's flush leaves in film_acc - then k_film_finalize's RGB -> XYZ. what 0: (X, Y, Z, weight) as rt_render returns it;

@@ -24,13 +24,14 @@ RT_FLAG_FILM_ON_DEVICE = 2
 RT_FLAG_TIME_KERNELS = 4
 RT_FLAG_COUNT_AS_RENDERED = 8
 RT_FLAG_REF_STREAM = 16
+RT_FLAG_FRAME_STATS = 32   # rt_frame_begin: per-pixel luminance moments, adaptive steps
 RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
 RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
 RT_SAMPLES_MAX = 1 << 27
 RT_QUERY_BSDF_LAUNCHED = 5  # rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
-RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8 = range(3)                                                    # rt_frame_read: what
-RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES = range(4)          # rt_frame_query: what
+RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS = range(4)                                    # rt_frame_read: what
+RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES, RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS = range(6)   # rt_frame_query: what
 BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
                        two_lobe_wide=RT_BSDF_FRONT_TWO_LOBE_WIDE)
 
@@ -365,10 +366,12 @@ class HostScene:
         _check(lib().rtxh_render(self.h, C.byref(p), C.c_void_p(stream), _p(film), C.byref(stats)), "render")
         return film, stats.as_dict()
 
-    def progressive(self, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False):
+    def progressive(self, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
         """The frame of `render` in steps (rt_frame_*): a ProgressiveFrame whose film can be read after any number of samples per pixel. `table_budget`: bytes the
-        frame may spend on sampler tables that stay resident between steps (None: the backend's default; too small: every step rebuilds them - same film)."""
-        return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels)
+        frame may spend on sampler tables that stay resident between steps (None: the backend's default; too small: every step rebuilds them - same film).
+        `pixel_stats`: the frame keeps per-pixel luminance moments (RT_FLAG_FRAME_STATS) - `pixel_stats()`, `noise()` and `advance_adaptive()` need it."""
+        return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels,
+                                pixel_stats=pixel_stats)
 
     def render_multi(self, devices, chunks_per_device=1, count_traversal=False, time_kernels=False, count_as_rendered=False, device_out=None):
         """The frame on several GPUs of this process (rt_multi_render): one host thread per entry of `devices`, chunks of tile rows pulled from a
@@ -522,7 +525,7 @@ class ProgressiveFrame:
     """A frame rendered in steps (HostScene.progressive). `advance(n)` renders the next n samples of every pixel; `film()`, `rgb()` and `display()` read the film as
     it stands. A context manager; it keeps its scene alive and must be closed (or left) before the scene goes."""
 
-    def __init__(self, scene, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False):
+    def __init__(self, scene, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
         L = lib()
         L.rtxh_frame_end.argtypes = [C.c_void_p]
         self.scene = scene   # (the frame's device state belongs to the scene's device: the scene must outlive it)
@@ -531,7 +534,7 @@ class ProgressiveFrame:
         cr = st["cropped"]
         self.width, self.height = int(cr[2] - cr[0]), int(cr[3] - cr[1])
         p = st["params"]
-        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0)
         self.scale = float(p.film_scale)
         h = C.c_void_p()
         _check(L.rtxh_frame_begin(scene.h, C.byref(p), C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)), C.byref(h)), "frame_begin")
@@ -566,6 +569,8 @@ class ProgressiveFrame:
     spp = property(lambda self: self._query(RT_FRAME_SPP))
     tables_resident = property(lambda self: bool(self._query(RT_FRAME_TABLES_RESIDENT)))
     state_bytes = property(lambda self: self._query(RT_FRAME_STATE_BYTES))
+    samples_taken = property(lambda self: self._query(RT_FRAME_SAMPLES_TAKEN))    # camera samples traced so far, over all steps
+    active_pixels = property(lambda self: self._query(RT_FRAME_ACTIVE_PIXELS))    # pixels the last adaptive step sampled (0 before one has run)
 
     def advance(self, n, stream=0):
         """Renders samples [samples_done, min(samples_done + n, spp)) of every pixel; returns the step's stats dict (all zero once the frame is finished)."""
@@ -574,6 +579,32 @@ class ProgressiveFrame:
         stats = Stats()
         _check(lib().rtxh_frame_advance(self.h, C.c_int32(int(n)), C.c_void_p(stream), C.byref(stats)), "frame_advance")
         return stats.as_dict()
+
+    def advance_adaptive(self, n, threshold, floor_y=0.0, min_samples=4, stream=0):
+        """Offers samples [samples_done, min(samples_done + n, spp)) to the pixels that are still noisy (rt_frame_advance_adaptive; the frame needs pixel_stats=True):
+        a pixel takes them if it holds fewer than max(min_samples, 2) samples or the standard error of its mean luminance exceeds threshold * max(mean, floor_y).
+        Returns the step's stats dict (camera_rays = samples taken; all zero when no pixel is active). The frame is then no longer `render`'s frame."""
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        stats = Stats()
+        _check(lib().rtxh_frame_advance_adaptive(self.h, C.c_int32(int(n)), C.c_float(threshold), C.c_float(floor_y), C.c_int32(int(min_samples)), C.c_void_p(stream),
+                                                 C.byref(stats)), "frame_advance_adaptive")
+        return stats.as_dict()
+
+    def pixel_stats(self, device_out=None, stream=0):
+        """(n, sum_y, sum_y2): three (H, W) float64 arrays over the cropped pixel bounds - the number of samples each pixel took and the sums of their luminance and
+        its square (RT_FRAME_STATS). With `device_out`, a torch CUDA tensor (H, W, 3) float64, the three are views of it."""
+        a = self._read(RT_FRAME_STATS, 1.0, 3, np.float64, device_out, stream)
+        return a[..., 0], a[..., 1], a[..., 2]
+
+    def noise(self):
+        """(mean, se): each pixel's mean luminance and the standard error of that mean, from `pixel_stats()` with the arithmetic of the adaptive criterion
+        (var = max(0, sum_y2 - sum_y * mean) / (n - 1), se = sqrt(var / n)); mean is 0 where n = 0, se is inf where n < 2."""
+        n, sy, sy2 = self.pixel_stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(n > 0, sy / n, 0.0)
+            se = np.where(n > 1, np.sqrt(np.maximum(0.0, sy2 - sy * mean) / (n - 1) / n), np.inf)
+        return mean, se
 
     def _read(self, what, scale, channels, dtype, device_out, stream):
         if self.h is None:

@@ -1,6 +1,7 @@
 """Render a pbrt-v3 scene file on the GPU.
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
+                                  [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -8,7 +9,11 @@ name the image goes where the reference writes it: "rt-" + the Film's filename, 
 --samples out.npy: instead of an image, the radiance of every sample of the integrator's pixel bounds (rt_render_samples), float32
 [height, width, spp, 6] = L rgb as PathIntegrator::li returned it, 1.0 where the renderer scrubs the sample, the sample's film position.
 --preview-every N: the frame is rendered in steps of N samples per pixel (rt_frame_*) and the output image rewritten after each, as the reference's
--p / --display shows the image while it renders; the last image written is the one the run without the flag writes."""
+-p / --display shows the image while it renders; the last image written is the one the run without the flag writes.
+--adaptive T: the frame is rendered in steps of --preview-every samples (4 if not given) that only the pixels still noisier than T take (rt_frame_advance_adaptive:
+the standard error of a pixel's mean luminance over max(mean, --noise-floor), every pixel at least --min-samples), until no pixel is active or the sampler's count is
+reached; prints samples taken / samples of the full frame; --sample-map out.npy gets the per-pixel sample counts (float64 [height, width]). Such an image is no longer
+the one the run without the flag writes."""
 import argparse
 import os
 import sys
@@ -25,6 +30,10 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
     ap.add_argument("--samples", metavar="OUT.npy", default=None, help="write the per-sample radiance and film positions of the pixel bounds instead of an image")
     ap.add_argument("--preview-every", type=int, default=0, metavar="N", help="rewrite the output image after every N samples per pixel")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="T", help="stop sampling a pixel once the relative standard error of its luminance is at most T")
+    ap.add_argument("--min-samples", type=int, default=8, metavar="M", help="with --adaptive: samples every pixel takes before it may stop")
+    ap.add_argument("--noise-floor", type=float, default=1e-3, metavar="F", help="with --adaptive: the error is relative to max(mean luminance, F)")
+    ap.add_argument("--sample-map", metavar="OUT.npy", default=None, help="with --adaptive: write the per-pixel sample counts")
     a = ap.parse_args()
     host.build()
     s = host.PbrtScene(a.scene)
@@ -48,7 +57,27 @@ def main():
         else:
             write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
 
-    if a.preview_every > 0:
+    if a.adaptive is not None:
+        import numpy as np
+        stats = {"ms_total": 0.0}
+        step = a.preview_every if a.preview_every > 0 else 4
+        with s.progressive(pixel_stats=True) as frame:
+            spp = frame.spp
+            while frame.samples_done < spp:
+                stats["ms_total"] += frame.advance_adaptive(step, a.adaptive, a.noise_floor, a.min_samples)["ms_total"]
+                if frame.active_pixels == 0:
+                    break
+                if a.preview_every > 0:
+                    write(frame.film())
+                    print(f"{out}: {frame.samples_done} / {spp} sample indices offered, {frame.active_pixels} pixels active", flush=True)
+            film = frame.film()
+            write(film)
+            counts = frame.pixel_stats()[0]
+            full = int(np.count_nonzero(counts)) * spp
+            print(f"{out}: {frame.samples_taken} samples taken / {full} of the full frame ({frame.samples_taken / max(full, 1):.3f}), stopped after {frame.samples_done} of {spp} indices")
+            if a.sample_map:
+                np.save(a.sample_map, counts)
+    elif a.preview_every > 0:
         stats = {"ms_total": 0.0}
         with s.progressive() as frame:
             spp = frame.spp
