@@ -427,7 +427,8 @@ int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_de
  *   out: host memory, or device memory with RT_FLAG_FILM_ON_DEVICE in `flags`.
  * rt_frame_query: RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP (rounded), RT_FRAME_TABLES_RESIDENT (0 / 1), RT_FRAME_STATE_BYTES (device bytes the frame holds).
  * Any number of frames may live on one scene; their steps and rt_render calls on that scene take turns on the scene's mutex and change no byte of each other.
- * A FRAME MUST BE ENDED BEFORE ITS SCENE IS DESTROYED. rt_frame_end(NULL) is a no-op. Single device; rt_shard is honoured (rows of other ranks read as zero).
+ * A FRAME MUST BE ENDED BEFORE ITS SCENE IS DESTROYED. rt_frame_end(NULL) is a no-op. One device per rt_frame; rt_shard is honoured (rows of other ranks read as zero) - rt_multi_frame_* below
+ * spans the devices of an rt_multi with one rt_frame each and merges their films on the device.
  *
  * Frame statistics and adaptive steps (opt-in: a frame begun without RT_FLAG_FRAME_STATS launches exactly the kernels described above).
  * RT_FLAG_FRAME_STATS gives the frame one more plane, 32 B per owned pixel, zero at begin and counted in RT_FRAME_STATE_BYTES: {double sum_y, double sum_y2,
@@ -461,6 +462,41 @@ int rt_frame_advance_adaptive(rt_frame* frame, int32_t n_samples, float threshol
 int rt_frame_read(rt_frame* frame, int32_t what, float scale, uint32_t flags, void* stream, void* out);
 int rt_frame_query(rt_frame* frame, int32_t what, uint64_t* value);
 void rt_frame_end(rt_frame* frame);
+
+/* Progressive and adaptive frames across the workers of an rt_multi: the frame of rt_frame_* spread over the devices of rt_multi_create, read as ONE film.
+ * rt_multi_frame_begin opens one rt_frame per worker k on the multi's replica k with rt_shard{k, n_devices} - the static split into interleaved bands of
+ *   RT_SHARD_ROWS rows: a pixel's own sum, its sampler tables and its moments live on one device for the life of the frame, so the chunk queue of rt_multi_render
+ *   does not apply. It refuses what rt_frame_begin refuses, before any device work and with rt_frame_begin's messages, and a NULL multi; if one worker's begin
+ *   fails, the frames already opened are ended and the first error is returned. table_budget_bytes is per worker (0: rt_frame_begin's default). flags:
+ *   RT_FLAG_FRAME_STATS / _COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED pass through. A worker with nothing to trace - it owns no row (fewer bands than workers), or
+ *   none of its rows lies inside pixel_bounds - is legal: its steps launch nothing and its step stats are zero.
+ * rt_multi_frame_advance / _advance_adaptive: one host thread per worker runs rt_frame_advance (_adaptive) on its own frame and stream, all at once. per_device
+ *   (n_devices entries, may be NULL): worker k's step stats; total (may be NULL): their sum, with ms_total the wall time of the call. An adaptive step decides
+ *   each pixel from its owner's plane - a per-pixel decision, so the one a single-device frame makes. Every RT_ERR_INVALID case of the single-device calls is
+ *   refused before any thread starts; a finished frame: RT_OK, zeroed stats. If a step fails on a worker the first error is returned once every worker has
+ *   stopped, and the frame is BROKEN (the workers' sample counts may differ): every later call except rt_multi_frame_end answers RT_ERR_INVALID and says so.
+ * rt_multi_frame_read yields the merged frame on devices[0]: worker k forms c_k[i] = film_acc_k[i] + own_k[i] where it owns pixel i's row, else film_acc_k[i]
+ *   (float32 RGB sums, before any colour conversion) for the film rows it can have touched - its bands widened by the filter's reach -, only those rows travel to
+ *   devices[0] (hipMemcpyPeerAsync), and one kernel there adds c_0[i] + c_1[i] + ... left to right in worker order over the workers whose rows hold i and reads
+ *   the sum out with rt_frame_read's arithmetic. what / scale as in rt_frame_read; RT_FRAME_STATS takes each pixel's (n, sum_y, sum_y2) from its owner, nothing
+ *   is added. out: host memory, or memory of devices[0] with RT_FLAG_FILM_ON_DEVICE in `flags`. The frame owns every buffer of the read: an rt_multi_render on the
+ *   same rt_multi between two steps disturbs nothing.
+ * rt_multi_frame_query: RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP as for one frame; RT_FRAME_TABLES_RESIDENT: 1 only if resident on every worker that owns pixels;
+ *   RT_FRAME_STATE_BYTES (the workers' frames and the buffers of the read), RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS: sums over the workers.
+ * A MULTI FRAME MUST BE ENDED BEFORE rt_multi_destroy. rt_multi_frame_end(NULL) is a no-op. Thread safety is rt_multi_render's: calls on one rt_multi - its
+ *   frames' calls and rt_multi_render alike - from one thread at a time.
+ * What equals what. One worker: every read-out is the rt_frame's, bit for bit, for any filter. Several workers, at every step: the statistics plane is bit-equal
+ *   to a single-device frame's after the same calls, and so are RT_FRAME_ACTIVE_PIXELS, RT_FRAME_SAMPLES_TAKEN and which pixels took which samples; the film is
+ *   bit-equal where the filter reaches no further than the pixel and a pixel receives at most one edge splat (the caveat of rt_frame_advance), otherwise equal up
+ *   to the order of the float additions, which neither rt_render nor rt_multi_render fixes. */
+typedef struct rt_multi_frame rt_multi_frame;
+int rt_multi_frame_begin(rt_multi* multi, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                         uint32_t flags, uint64_t table_budget_bytes, rt_multi_frame** out);
+int rt_multi_frame_advance(rt_multi_frame* frame, int32_t n_samples, rt_stats* total /* may be NULL */, rt_stats* per_device /* n_devices entries, may be NULL */);
+int rt_multi_frame_advance_adaptive(rt_multi_frame* frame, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, rt_stats* total, rt_stats* per_device);
+int rt_multi_frame_read(rt_multi_frame* frame, int32_t what, float scale, uint32_t flags, void* out);
+int rt_multi_frame_query(rt_multi_frame* frame, int32_t what, uint64_t* value);
+void rt_multi_frame_end(rt_multi_frame* frame);
 
 /* Dense voxel light distribution of SpatialLightDistribution (rc/lightdistrib.rs:101-179):
  * n_voxels[3]; func: nvox*n_lights, cdf: nvox*(n_lights+1), func_int: nvox (host pointers, may be NULL

@@ -162,6 +162,18 @@ void rtxh_frame_end(rtxh_frame*);
  * with RT_FLAG_FILM_ON_DEVICE). rank / world_size of the parameters are ignored. */
 int rtxh_render_multi(rtxh_scene*, const rtxh_render_params*, const int32_t* devices, int32_t n_devices, int32_t chunks_per_device, float* film_xyzw,
                       rt_stats* total, rt_stats* per_device /* n_devices entries or NULL */);
+/* The frame in steps on several GPUs of this process (rt_multi_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, the flags of
+ * the parameters are the frame's, rank / world_size are ignored (worker k is rank k of n_devices). The scene's replicas are those of rtxh_render_multi: made by the
+ * first call that names a device list, reused by every later frame and rtxh_render_multi call with the same list. While a multi frame lives, a call that would
+ * replace the replicas (another device list, a re-committed scene) is refused with RT_ERR_INVALID. table_budget_bytes is per worker. total / per_device (n_devices
+ * entries) may be NULL. A frame must be ended before its scene is freed; rtxh_multi_frame_end(NULL) is a no-op. One thread at a time per scene. */
+typedef struct rtxh_multi_frame rtxh_multi_frame;
+int rtxh_multi_frame_begin(rtxh_scene*, const rtxh_render_params*, const int32_t* devices, int32_t n_devices, uint64_t table_budget_bytes, rtxh_multi_frame** out);
+int rtxh_multi_frame_advance(rtxh_multi_frame*, int32_t n_samples, rt_stats* total, rt_stats* per_device);
+int rtxh_multi_frame_advance_adaptive(rtxh_multi_frame*, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, rt_stats* total, rt_stats* per_device);
+int rtxh_multi_frame_read(rtxh_multi_frame*, int32_t what, float scale, uint32_t flags, void* out);
+int rtxh_multi_frame_query(rtxh_multi_frame*, int32_t what, uint64_t* value);
+void rtxh_multi_frame_end(rtxh_multi_frame*);
 /* Kernel-level pass-throughs on the uploaded scene (prim indices are leaf-order). */
 int rtxh_trace(rtxh_scene*, const float* rays, uint64_t n, int32_t any_hit, float* hits4_or_occ, uint64_t counters[2]);
 int rtxh_trace_device(rtxh_scene*, const void* d_rays, uint64_t n, void* d_hits, int32_t reps, void* hip_stream, float* ms_per_launch);

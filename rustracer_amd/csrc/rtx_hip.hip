@@ -1782,3 +1782,204 @@ extern "C" int rt_multi_render(rt_multi* m, const rt_camera* cam, const rt_film_
   }
   return RT_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- progressive frames across the workers of an rt_multi
+// One rt_frame per worker k on replicas[k] with rt_shard{k, n_devices}: the static split into interleaved bands of RT_SHARD_ROWS rows - a pixel's own sum, its sampler
+// tables and its moments stay on one device for the life of the frame, so rt_multi_render's chunk queue does not apply. A step runs the workers' rt_frame_advance
+// concurrently, one host thread each; a read packs each worker's contribution for the film rows it can have touched (k_multi_frame_pack, on its device), sends only
+// those rows to devices[0] and resolves their sum there (k_multi_frame_resolve). Every buffer of the read is the frame's own.
+struct rt_multi_frame {
+  rt_multi* m = nullptr;
+  std::vector<rt_frame*> frames;
+  bool broken = false, stats = false;
+  std::vector<char> idle;  // per worker: it owns no row, or none of its rows lies inside pixel_bounds - its steps launch nothing
+  int cw = 0, ch = 0;
+  struct Worker {
+    std::vector<int> rows;                 // film rows (cropped coordinates, ascending) the worker can have touched: its bands widened by the filter's reach
+    DevBuf rows_dev, packed;               // on the worker's device: `rows`, and c_k for them
+    DevBuf staged, moments_staged;         // on devices[0], for a worker of another device: where its packed rows / its moments plane arrive
+    hipEvent_t ready = nullptr;            // on the worker's device: its rows (or its plane) are on devices[0]
+  };
+  std::vector<Worker> w;
+  DevBuf slot, packed_ptrs, moment_ptrs, out;  // on devices[0]: [worker][film row] -> row of its packed buffer or -1, the workers' buffers as the merge kernels see them, read staging
+  size_t state_bytes() const {
+    size_t b = slot.bytes + packed_ptrs.bytes + moment_ptrs.bytes + out.bytes;
+    for (const Worker& k : w) b += k.rows_dev.bytes + k.packed.bytes + k.staged.bytes + k.moments_staged.bytes;
+    return b;
+  }
+};
+static void multi_frame_free(rt_multi_frame* mf) {
+  for (size_t k = 0; k < mf->frames.size(); ++k) if (mf->frames[k]) rt_frame_end(mf->frames[k]);
+  for (size_t k = 0; k < mf->w.size(); ++k) if (mf->w[k].ready) { (void)hipSetDevice(mf->m->devices[k]); (void)hipEventDestroy(mf->w[k].ready); }
+  delete mf;
+}
+extern "C" int rt_multi_frame_begin(rt_multi* m, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path, uint32_t flags,
+                                    uint64_t table_budget_bytes, rt_multi_frame** out) {
+  if (!out) return fail(RT_ERR_INVALID, "rt_multi_frame_begin: NULL out");
+  *out = nullptr;
+  if (!m) return fail(RT_ERR_INVALID, "rt_multi_frame_begin: null multi");
+  const int n = (int)m->devices.size();
+  std::unique_ptr<rt_multi_frame, void (*)(rt_multi_frame*)> mf(new rt_multi_frame(), multi_frame_free);
+  mf->m = m; mf->frames.assign(n, nullptr); mf->w.resize(n); mf->stats = (flags & RT_FLAG_FRAME_STATS) != 0;
+  for (int k = 0; k < n; ++k) {  // (worker 0's begin refuses a faulty description before any device work, with rt_frame_begin's message; a later failure ends the frames opened so far)
+    const rt_shard sh{k, n};
+    const int rc = rt_frame_begin(m->replicas[k], cam, film, smp, path, &sh, flags, table_budget_bytes, &mf->frames[k]);
+    if (rc != RT_OK) return rc;
+  }
+  const int cw = film->cropped_pixel_bounds[2] - film->cropped_pixel_bounds[0], ch = film->cropped_pixel_bounds[3] - film->cropped_pixel_bounds[1];
+  const int H = film->sample_bounds[3] - film->sample_bounds[1];
+  mf->cw = cw; mf->ch = ch;
+  mf->idle.assign(n, 1);
+  if (std::min(path->pixel_bounds[2], film->sample_bounds[2]) > std::max(path->pixel_bounds[0], film->sample_bounds[0]))
+    for (int y = std::max(path->pixel_bounds[1], film->sample_bounds[1]); y < std::min(path->pixel_bounds[3], film->sample_bounds[3]); ++y)
+      mf->idle[((y - film->sample_bounds[1]) / RT_SHARD_ROWS(H, n)) % n] = 0;
+  // film rows worker k can have written: its bands, widened by the filter's reach (the arithmetic of rt_multi_render's bands() with world = n_devices)
+  const int halo = (int)std::ceil(film->filter_radius[1] - 0.5f) + 1;
+  const int band = RT_SHARD_ROWS(H, n), n_bands = (H + band - 1) / band;
+  std::vector<int> slot((size_t)n * ch, -1);
+  std::vector<const void*> packed_ptrs(n, nullptr), moment_ptrs(n, nullptr);
+  for (int k = 0; k < n; ++k) {
+    rt_multi_frame::Worker& wk = mf->w[k];
+    for (int t = k; t < n_bands; t += n) {
+      const int y0 = film->sample_bounds[1] + band * t - halo - film->cropped_pixel_bounds[1], y1 = film->sample_bounds[1] + std::min(band * t + band, H) + halo - film->cropped_pixel_bounds[1];
+      for (int y = std::max(std::max(0, y0), wk.rows.empty() ? 0 : wk.rows.back() + 1); y < std::min(ch, y1); ++y) { slot[(size_t)k * ch + y] = (int)wk.rows.size(); wk.rows.push_back(y); }
+    }
+    const bool remote = m->devices[k] != m->devices[0];
+    HIP_TRY(hipSetDevice(m->devices[k]));
+    HIP_TRY(hipEventCreateWithFlags(&wk.ready, hipEventDisableTiming));
+    if (!wk.rows.empty()) {
+      HIP_TRY(wk.rows_dev.ensure(wk.rows.size() * sizeof(int)));
+      HIP_TRY(hipMemcpy(wk.rows_dev.p, wk.rows.data(), wk.rows.size() * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(wk.packed.ensure(wk.rows.size() * (size_t)cw * 16));
+    }
+    packed_ptrs[k] = wk.packed.p; moment_ptrs[k] = mf->frames[k]->moments.p;
+    if (remote) {
+      HIP_TRY(hipSetDevice(m->devices[0]));
+      if (!wk.rows.empty()) { HIP_TRY(wk.staged.ensure(wk.packed.bytes)); packed_ptrs[k] = wk.staged.p; }
+      if (mf->stats) { HIP_TRY(wk.moments_staged.ensure(mf->frames[k]->moments.bytes)); moment_ptrs[k] = wk.moments_staged.p; }
+    }
+  }
+  HIP_TRY(hipSetDevice(m->devices[0]));
+  HIP_TRY(mf->slot.ensure(slot.size() * sizeof(int)));
+  HIP_TRY(hipMemcpy(mf->slot.p, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(mf->packed_ptrs.ensure((size_t)n * sizeof(void*)));
+  HIP_TRY(hipMemcpy(mf->packed_ptrs.p, packed_ptrs.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice));
+  HIP_TRY(mf->moment_ptrs.ensure((size_t)n * sizeof(void*)));
+  HIP_TRY(hipMemcpy(mf->moment_ptrs.p, moment_ptrs.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice));
+  *out = mf.release();
+  return RT_OK;
+}
+// One step on every worker at once (the worker pattern of rt_multi_render: first error wins, no early return while workers run). adaptive: each worker decides its
+// own pixels from its own plane - a per-pixel decision, so the one a single-device frame makes.
+static int multi_frame_step(rt_multi_frame* mf, const char* who, bool adaptive, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, rt_stats* total, rt_stats* per_device) {
+  const std::string name = who;
+  if (!mf) return fail(RT_ERR_INVALID, name + ": null frame");
+  if (mf->broken) return fail(RT_ERR_INVALID, name + ": the frame is broken (an earlier step failed on a worker, the workers' sample counts may differ): end it");
+  if (adaptive && !mf->stats) return fail(RT_ERR_INVALID, name + ": the frame was begun without RT_FLAG_FRAME_STATS");
+  if (n_samples <= 0) return fail(RT_ERR_INVALID, name + ": n_samples must be positive");
+  if (adaptive && min_samples < 0) return fail(RT_ERR_INVALID, name + ": min_samples must not be negative");
+  if (adaptive && !(threshold >= 0.0f)) return fail(RT_ERR_INVALID, name + ": threshold must be a number >= 0 (+inf: no pixel past min_samples)");
+  if (adaptive && !(floor_y >= 0.0f)) return fail(RT_ERR_INVALID, name + ": floor_y must be a number >= 0");
+  const int n = (int)mf->frames.size();
+  std::vector<rt_stats> dev_stats(n, rt_stats{});
+  const auto t_begin = std::chrono::steady_clock::now();
+  const rt_frame* f0 = mf->frames[0];
+  const bool stepped = f0->done < f0->spp;
+  if (stepped) {  // (a finished frame: RT_OK, zeroed stats, no thread)
+    const unsigned end = (unsigned)std::min<unsigned long long>(f0->spp, (unsigned long long)f0->done + (unsigned long long)n_samples);
+    std::mutex err_mtx; int first_rc = RT_OK; std::string first_err;
+    auto worker = [&](int k) {
+      rt_frame* fr = mf->frames[k];
+      if (mf->idle[k]) { fr->done = end; if (adaptive) fr->active_pixels = 0; return; }  // fewer bands than workers, or no row inside pixel_bounds: no sample to trace, nothing to launch
+      const int rc = adaptive ? rt_frame_advance_adaptive(fr, n_samples, threshold, floor_y, min_samples, mf->m->streams[k], &dev_stats[k])
+                              : rt_frame_advance(fr, n_samples, mf->m->streams[k], &dev_stats[k]);
+      if (rc != RT_OK) { std::lock_guard<std::mutex> g(err_mtx); if (first_rc == RT_OK) { first_rc = rc; first_err = g_err; } }  // (g_err is this thread's own)
+    };
+    std::vector<std::thread> threads;
+    for (int k = 1; k < n; ++k) threads.emplace_back(worker, k);
+    worker(0);  // the calling thread is worker 0
+    for (auto& t : threads) t.join();
+    if (first_rc != RT_OK) { mf->broken = true; return fail(first_rc, name + ": " + first_err); }
+  }
+  if (per_device) for (int k = 0; k < n; ++k) per_device[k] = dev_stats[k];
+  if (total) {
+    rt_stats t{};
+    for (const rt_stats& a : dev_stats) stats_add(t, a);  // times are summed over the workers, ms_total is the wall time of the call
+    t.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (!stepped) t = rt_stats{};
+    *total = t;
+  }
+  return RT_OK;
+}
+extern "C" int rt_multi_frame_advance(rt_multi_frame* mf, int32_t n_samples, rt_stats* total, rt_stats* per_device) {
+  return multi_frame_step(mf, "rt_multi_frame_advance", false, n_samples, 0.0f, 0.0f, 0, total, per_device);
+}
+extern "C" int rt_multi_frame_advance_adaptive(rt_multi_frame* mf, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, rt_stats* total, rt_stats* per_device) {
+  return multi_frame_step(mf, "rt_multi_frame_advance_adaptive", true, n_samples, threshold, floor_y, min_samples, total, per_device);
+}
+extern "C" int rt_multi_frame_read(rt_multi_frame* mf, int32_t what, float scale, uint32_t flags, void* out) {
+  if (!mf || !out) return fail(RT_ERR_INVALID, "rt_multi_frame_read: null argument");
+  if (mf->broken) return fail(RT_ERR_INVALID, "rt_multi_frame_read: the frame is broken (an earlier step failed on a worker): end it");
+  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS) return fail(RT_ERR_INVALID, "rt_multi_frame_read: unknown read-out");
+  if (what == RT_FRAME_STATS && !mf->stats) return fail(RT_ERR_INVALID, "rt_multi_frame_read: RT_FRAME_STATS needs a frame begun with RT_FLAG_FRAME_STATS");
+  rt_multi* m = mf->m;
+  const int n_w = (int)mf->frames.size();
+  const unsigned long long n = (unsigned long long)mf->cw * (unsigned long long)mf->ch;
+  const size_t bytes = (size_t)n * (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
+  const bool on_device = (flags & RT_FLAG_FILM_ON_DEVICE) != 0;
+  // every worker's part, on its own stream and device; streams[0] then waits for the parts of the others
+  for (int k = 0; k < n_w; ++k) {
+    rt_multi_frame::Worker& wk = mf->w[k];
+    rt_frame* fr = mf->frames[k];
+    const bool remote = m->devices[k] != m->devices[0];
+    HIP_TRY(hipSetDevice(m->devices[k]));
+    if (what == RT_FRAME_STATS) {
+      if (remote)  // (a plane on devices[0] is read where it lies)
+        HIP_TRY(hipMemcpyPeerAsync(wk.moments_staged.p, m->devices[0], fr->moments.p, m->devices[k], fr->moments.bytes, m->streams[k]));
+    } else if (!wk.rows.empty()) {
+      const FrameParams fp = frame_pixel_params(fr);
+      const unsigned long long np = (unsigned long long)wk.rows.size() * (unsigned long long)mf->cw;
+      hipLaunchKernelGGL(k_multi_frame_pack, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, m->streams[k], fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), wk.rows_dev.as<int>(),
+                         wk.packed.as<float4>(), np);
+      HIP_TRY(hipGetLastError());
+      if (remote) HIP_TRY(hipMemcpyPeerAsync(wk.staged.p, m->devices[0], wk.packed.p, m->devices[k], np * 16, m->streams[k]));
+    }
+    if (k > 0) HIP_TRY(hipEventRecord(wk.ready, m->streams[k]));
+  }
+  HIP_TRY(hipSetDevice(m->devices[0]));
+  hipStream_t s0 = m->streams[0];
+  for (int k = 1; k < n_w; ++k) HIP_TRY(hipStreamWaitEvent(s0, mf->w[k].ready, 0));
+  if (!on_device) HIP_TRY(mf->out.ensure((size_t)n * (what == RT_FRAME_STATS ? 24 : 16)));  // (ensure only ever grows the staging buffer)
+  void* const d_out = on_device ? out : mf->out.p;
+  if (what == RT_FRAME_STATS) {
+    const FrameParams fp = frame_pixel_params(mf->frames[0]);  // (rank is not read: the owner is the band's)
+    hipLaunchKernelGGL(k_multi_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, fp, (const PixMoments* const*)mf->moment_ptrs.p, (double*)d_out, n);
+  } else {
+    hipLaunchKernelGGL(k_multi_frame_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, mf->cw, n_w, mf->ch, (const float4* const*)mf->packed_ptrs.p, mf->slot.as<int>(), (int)what, scale,
+                       d_out, n);
+  }
+  HIP_TRY(hipGetLastError());
+  if (!on_device) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, s0));
+  HIP_TRY(hipStreamSynchronize(s0));
+  return RT_OK;
+}
+extern "C" int rt_multi_frame_query(rt_multi_frame* mf, int32_t what, uint64_t* value) {
+  if (!mf || !value) return fail(RT_ERR_INVALID, "rt_multi_frame_query: null argument");
+  if (mf->broken) return fail(RT_ERR_INVALID, "rt_multi_frame_query: the frame is broken (an earlier step failed on a worker): end it");
+  uint64_t v = 0;
+  switch (what) {
+    case RT_FRAME_SAMPLES_DONE: v = mf->frames[0]->done; break;
+    case RT_FRAME_SPP: v = mf->frames[0]->spp; break;
+    case RT_FRAME_TABLES_RESIDENT: v = 1; for (const rt_frame* f : mf->frames) if (f->owned_pixels > 0 && !f->resident) v = 0; break;
+    case RT_FRAME_STATE_BYTES: v = mf->state_bytes(); for (const rt_frame* f : mf->frames) v += f->state_bytes(); break;
+    case RT_FRAME_SAMPLES_TAKEN: for (const rt_frame* f : mf->frames) v += f->samples_taken; break;
+    case RT_FRAME_ACTIVE_PIXELS: for (const rt_frame* f : mf->frames) v += f->active_pixels; break;
+    default: return fail(RT_ERR_INVALID, "rt_multi_frame_query: unknown query");
+  }
+  *value = v;
+  return RT_OK;
+}
+extern "C" void rt_multi_frame_end(rt_multi_frame* mf) {
+  if (!mf) return;
+  multi_frame_free(mf);
+}

@@ -234,6 +234,7 @@ struct rtxh_scene {
   bool committed = false; unsigned commit_gen = 0, multi_gen = 0;  // multi_gen: the commit the replicas of `multi` were made from
   rt_scene* dev = nullptr;
   rt_multi* multi = nullptr; std::vector<int32_t> multi_devices;  // replicas for rtxh_render_multi, kept while the device list stays the same
+  int multi_frames = 0;  // live rtxh_multi_frame objects: the replicas stay while one of them does
   size_t n_tris() const { return idx.size() / 3; }
 };
 
@@ -1336,29 +1337,83 @@ void rtxh_frame_end(rtxh_frame* f) {
   rt_frame_end(f->f);
   delete f;
 }
-int rtxh_render_multi(rtxh_scene* s, const rtxh_render_params* p, const int32_t* devices, int32_t n_devices, int32_t chunks_per_device, float* film_xyzw,
-                      rt_stats* total, rt_stats* per_device) {
-  if (!s || !p || !film_xyzw || !devices || n_devices < 1) return fail(RT_ERR_INVALID, "null argument");
-  if (!s->committed) return fail(RT_ERR_INVALID, "scene not committed");
-  g_err.clear();
+// The replicas of the scene on `devices`: made on first use, kept while the device list and the commit stay the same.
+static int ensure_multi(rtxh_scene* s, const int32_t* devices, int32_t n_devices) {
   const std::vector<int32_t> want(devices, devices + n_devices);
   if (!s->multi || s->multi_devices != want || s->multi_gen != s->commit_gen) {  // a re-committed scene gets new replicas
+    if (s->multi && s->multi_frames > 0) return fail(RT_ERR_INVALID, "a multi frame lives on the scene's replicas: end it before another device list or a re-committed scene replaces them");
     if (s->multi) { rt_multi_destroy(s->multi); s->multi = nullptr; }
     rt_scene_desc d = make_desc(s);
     const int rc = rt_multi_create(&d, devices, n_devices, &s->multi);
     if (rc != RT_OK) return rc;
     s->multi_devices = want; s->multi_gen = s->commit_gen;
   }
-  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
-  rt_sampler_desc smp{p->spp, p->sampler_dims};
-  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  return RT_OK;
+}
+// sampler and path descriptions of the parameters, pixel bounds as rtxh_render sets them up
+static void sampler_path_of(const rtxh_render_params* p, const CamFilm& cf, rt_sampler_desc& smp, rt_path_desc& path) {
+  smp = rt_sampler_desc{p->spp, p->sampler_dims};
+  path = rt_path_desc{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
   int pb[4] = {cf.film.sample_bounds[0], cf.film.sample_bounds[1], cf.film.sample_bounds[2], cf.film.sample_bounds[3]};
   if (p->has_pixel_bounds) {
     pb[0] = std::max(pb[0], p->pixel_bounds[0]); pb[1] = std::max(pb[1], p->pixel_bounds[2]);
     pb[2] = std::min(pb[2], p->pixel_bounds[1]); pb[3] = std::min(pb[3], p->pixel_bounds[3]);
   }
   memcpy(path.pixel_bounds, pb, 16);
+}
+int rtxh_render_multi(rtxh_scene* s, const rtxh_render_params* p, const int32_t* devices, int32_t n_devices, int32_t chunks_per_device, float* film_xyzw,
+                      rt_stats* total, rt_stats* per_device) {
+  if (!s || !p || !film_xyzw || !devices || n_devices < 1) return fail(RT_ERR_INVALID, "null argument");
+  if (!s->committed) return fail(RT_ERR_INVALID, "scene not committed");
+  g_err.clear();
+  int rc = ensure_multi(s, devices, n_devices); if (rc != RT_OK) return rc;
+  CamFilm cf; rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp; rt_path_desc path; sampler_path_of(p, cf, smp, path);
   return rt_multi_render(s->multi, &cf.cam, &cf.film, &smp, &path, chunks_per_device, p->flags, film_xyzw, total, per_device);
+}
+// A progressive frame across the scene's replicas (rt_multi_frame_* in rtx_hip.h); the rt_multi is the one rtxh_render_multi uses.
+struct rtxh_multi_frame { rt_multi_frame* f = nullptr; rtxh_scene* scene = nullptr; };
+int rtxh_multi_frame_begin(rtxh_scene* s, const rtxh_render_params* p, const int32_t* devices, int32_t n_devices, uint64_t table_budget_bytes, rtxh_multi_frame** out) {
+  if (!out) return fail(RT_ERR_INVALID, "rtxh_multi_frame_begin: NULL out");
+  *out = nullptr;
+  if (!s || !p || !devices || n_devices < 1) return fail(RT_ERR_INVALID, "rtxh_multi_frame_begin: null argument");
+  if (!s->committed) return fail(RT_ERR_INVALID, "rtxh_multi_frame_begin: scene not committed");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp; rt_path_desc path; sampler_path_of(p, cf, smp, path);
+  rc = ensure_multi(s, devices, n_devices); if (rc != RT_OK) return rc;
+  rt_multi_frame* f = nullptr;
+  rc = rt_multi_frame_begin(s->multi, &cf.cam, &cf.film, &smp, &path, p->flags, table_budget_bytes, &f);
+  if (rc != RT_OK) return rc;
+  s->multi_frames += 1;
+  *out = new rtxh_multi_frame{f, s};
+  return RT_OK;
+}
+int rtxh_multi_frame_advance(rtxh_multi_frame* f, int32_t n_samples, rt_stats* total, rt_stats* per_device) {
+  if (!f) return fail(RT_ERR_INVALID, "rtxh_multi_frame_advance: null frame");
+  g_err.clear();
+  return rt_multi_frame_advance(f->f, n_samples, total, per_device);
+}
+int rtxh_multi_frame_advance_adaptive(rtxh_multi_frame* f, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, rt_stats* total, rt_stats* per_device) {
+  if (!f) return fail(RT_ERR_INVALID, "rtxh_multi_frame_advance_adaptive: null frame");
+  g_err.clear();
+  return rt_multi_frame_advance_adaptive(f->f, n_samples, threshold, floor_y, min_samples, total, per_device);
+}
+int rtxh_multi_frame_read(rtxh_multi_frame* f, int32_t what, float scale, uint32_t flags, void* out) {
+  if (!f || !out) return fail(RT_ERR_INVALID, "rtxh_multi_frame_read: null argument");
+  g_err.clear();
+  return rt_multi_frame_read(f->f, what, scale, flags, out);
+}
+int rtxh_multi_frame_query(rtxh_multi_frame* f, int32_t what, uint64_t* value) {
+  if (!f || !value) return fail(RT_ERR_INVALID, "rtxh_multi_frame_query: null argument");
+  g_err.clear();
+  return rt_multi_frame_query(f->f, what, value);
+}
+void rtxh_multi_frame_end(rtxh_multi_frame* f) {
+  if (!f) return;
+  rt_multi_frame_end(f->f);
+  f->scene->multi_frames -= 1;
+  delete f;
 }
 int rtxh_trace(rtxh_scene* s, const float* rays, uint64_t n, int32_t any_hit, float* out, uint64_t counters[2]) {
   if (!s) return fail(RT_ERR_INVALID, "null scene");

@@ -2450,25 +2450,10 @@ static __global__ void __launch_bounds__(256) k_frame_stats_read(FrameParams fp,
   }
   out[3ull * i] = v0; out[3ull * i + 1ull] = v1; out[3ull * i + 2ull] = v2;
 }
-// rt_frame_read: one lane per cropped pixel. The pixel's sums = what other pixels' samples splatted onto it (film_acc) + its own sum (own_plane, if this shard owns
-// the pixel's row) - the value k_film_accumulate's flush leaves in film_acc - then k_film_finalize's RGB -> XYZ. what 0: (X, Y, Z, weight) as rt_render returns it;
+// The read-out of one film pixel from its float32 RGB sums a = (R, G, B, weight): k_film_finalize's RGB -> XYZ, then what 0: (X, Y, Z, weight) as rt_render returns it;
 // 1: Film::write_image's pixel (film.rs:196-234): XYZ -> RGB, * (1 / weight) and max(0, .) where the weight is not zero, * scale, three floats; 2: that pixel through
-// write_image_png's quantisation (imageio.rs:52-63, spectrum.rs:387-393), three bytes. Reads the frame, writes `out` only.
-static __global__ void __launch_bounds__(256) k_frame_resolve(FrameParams fp, const float4* __restrict__ film_acc, const float4* __restrict__ own_plane, int what, float scale,
-                                                              void* __restrict__ out, unsigned long long n) {
-  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
-  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
-  float4 a = film_acc[i];
-  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel
-    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
-    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
-      const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
-      const float4 o = own_plane[j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
-      a = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
-    }
-  }
+// write_image_png's quantisation (imageio.rs:52-63, spectrum.rs:387-393), three bytes. Shared by k_frame_resolve and k_multi_frame_resolve: one arithmetic.
+RT_DEV void frame_resolve_store(const float4 a, int what, float scale, void* __restrict__ out, unsigned long long i) {
   const float X = 0.412453f * a.x + 0.357580f * a.y + 0.180423f * a.z;
   const float Y = 0.212671f * a.x + 0.715160f * a.y + 0.072169f * a.z;
   const float Z = 0.019334f * a.x + 0.119193f * a.y + 0.950227f * a.z;
@@ -2487,6 +2472,83 @@ static __global__ void __launch_bounds__(256) k_frame_resolve(FrameParams fp, co
     const float q = 255.0f * g + 0.5f;
     o[k] = q != q ? (unsigned char)0 : (unsigned char)fminf(fmaxf(q, 0.0f), 255.0f);
   }
+}
+// rt_frame_read: one lane per cropped pixel. The pixel's sums = what other pixels' samples splatted onto it (film_acc) + its own sum (own_plane, if this shard owns
+// the pixel's row) - the value k_film_accumulate's flush leaves in film_acc - then frame_resolve_store. Reads the frame, writes `out` only.
+static __global__ void __launch_bounds__(256) k_frame_resolve(FrameParams fp, const float4* __restrict__ film_acc, const float4* __restrict__ own_plane, int what, float scale,
+                                                              void* __restrict__ out, unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  float4 a = film_acc[i];
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
+      const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+      const float4 o = own_plane[j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+      a = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
+    }
+  }
+  frame_resolve_store(a, what, scale, out, i);
+}
+// A frame that spans the workers of an rt_multi (rt_multi_frame_read). Worker k's contribution to film pixel i is c_k[i] = film_acc_k[i] + own_k[i] where k owns the
+// pixel's row, else film_acc_k[i] - float32 RGB sums, before any colour conversion - and exists for the film rows worker k can have touched only (its bands widened by
+// the filter's reach). k_multi_frame_pack runs on worker k's device: one lane per float4 of the packed buffer, whose row r holds film row rows[r] (ascending).
+static __global__ void __launch_bounds__(256) k_multi_frame_pack(FrameParams fp, const float4* __restrict__ film_acc, const float4* __restrict__ own_plane, const int* __restrict__ rows,
+                                                                 float4* __restrict__ packed, unsigned long long n) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const unsigned long long fy = (unsigned long long)rows[j / cw];  // film row (cropped coordinates)
+  const int x = fp.crop_x0 + (int)(j % cw), y = fp.crop_y0 + (int)fy;
+  float4 a = film_acc[fy * cw + (j % cw)];
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel, as in k_frame_resolve
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
+      const unsigned long long o_row = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+      const float4 o = own_plane[o_row * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+      a = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
+    }
+  }
+  packed[j] = a;
+}
+// ... and on devices[0], once every worker's packed rows have arrived: one lane per cropped pixel adds the contributions left to right in worker order over the workers
+// whose packed rows hold the pixel's film row - slot[k * ch + row] is that row's index in worker k's buffer, or -1 - and reads the sum out as k_frame_resolve does.
+// One worker: a = c_0[i], the value k_frame_resolve forms. A row nobody touched (outside every band and halo) reads as the zero film.
+static __global__ void __launch_bounds__(256) k_multi_frame_resolve(int crop_w, int n_workers, int ch, const float4* const* __restrict__ packed, const int* __restrict__ slot, int what,
+                                                                    float scale, void* __restrict__ out, unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)crop_w;
+  const unsigned long long fy = i / cw, fx = i % cw;
+  float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  bool first = true;
+  for (int k = 0; k < n_workers; ++k) {
+    const int r = slot[(unsigned long long)k * (unsigned long long)ch + fy];
+    if (r < 0) continue;
+    const float4 c = packed[k][(unsigned long long)r * cw + fx];
+    a = first ? c : make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
+    first = false;
+  }
+  frame_resolve_store(a, what, scale, out, i);
+}
+// rt_multi_frame_read(RT_FRAME_STATS) on devices[0]: one lane per cropped pixel takes (n, sum_y, sum_y2) from the moments plane of the worker that owns the pixel's
+// row (the planes are copies of the workers' own, [owned pixel] as k_frame_stats_read indexes them); nothing is added. Zeros outside the sample bounds.
+static __global__ void __launch_bounds__(256) k_multi_frame_stats_read(FrameParams fp, const PixMoments* const* __restrict__ planes, double* __restrict__ out, unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    const unsigned long long owner = band % (unsigned long long)fp.world;
+    const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+    const PixMoments* const m = &planes[owner][j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+    v0 = (double)m->n; v1 = m->sum_y; v2 = m->sum_y2;
+  }
+  out[3ull * i] = v0; out[3ull * i + 1ull] = v1; out[3ull * i + 2ull] = v2;
 }
 // merge_film_tile's RGB -> XYZ (spectrum.rs:98-106); output (X, Y, Z, filter_weight_sum)
 static __global__ void k_film_finalize(const float4* film_acc, float4* film_xyzw, unsigned long long n) {

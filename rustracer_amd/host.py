@@ -373,6 +373,12 @@ class HostScene:
         return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels,
                                 pixel_stats=pixel_stats)
 
+    def progressive_multi(self, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+        """The frame of `progressive` across several GPUs of this process (rt_multi_frame_*): a MultiProgressiveFrame with the methods and properties of
+        ProgressiveFrame whose read-outs are the merged frame, formed on devices[0]. One worker per entry of `devices` (an entry may repeat), worker k owns the
+        interleaved bands k of len(devices); `table_budget` is per worker. `advance*` return (total stats, [per-device stats])."""
+        return MultiProgressiveFrame(self, devices, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels, pixel_stats=pixel_stats)
+
     def render_multi(self, devices, chunks_per_device=1, count_traversal=False, time_kernels=False, count_as_rendered=False, device_out=None):
         """The frame on several GPUs of this process (rt_multi_render): one host thread per entry of `devices`, chunks of tile rows pulled from a
         shared queue, rows gathered on devices[0]. Returns (film, total stats, [per-device stats]).
@@ -629,6 +635,72 @@ class ProgressiveFrame:
     def display(self, scale=None, device_out=None, stream=0):
         """(H, W, 3) uint8: the pixels of `rgb()` through the PNG writer's sRGB quantisation (rgb_to_png8)."""
         return self._read(RT_FRAME_RGB8, self.scale if scale is None else float(scale), 3, np.uint8, device_out, stream)
+
+
+class MultiProgressiveFrame(ProgressiveFrame):
+    """A frame rendered in steps by several GPUs of this process (HostScene.progressive_multi): ProgressiveFrame's methods and properties over the merged frame.
+    `advance` / `advance_adaptive` return (total stats, [per-device stats]); `device_out` tensors live on devices[0]. Calls on one scene's multi frames and
+    `render_multi` come from one thread at a time."""
+
+    def __init__(self, scene, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+        L = lib()
+        L.rtxh_multi_frame_end.argtypes = [C.c_void_p]
+        L.rtxh_multi_frame_end.restype = None
+        self.scene = scene   # (the replicas the frame lives on belong to the scene: the scene must outlive it)
+        self.h = None
+        self.devices = [int(d) for d in devices]
+        st = scene.setup()
+        cr = st["cropped"]
+        self.width, self.height = int(cr[2] - cr[0]), int(cr[3] - cr[1])
+        p = st["params"]
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0)
+        self.scale = float(p.film_scale)
+        dev = np.ascontiguousarray(self.devices, np.int32)
+        h = C.c_void_p()
+        _check(L.rtxh_multi_frame_begin(scene.h, C.byref(p), _p(dev, C.c_int32), len(dev), C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)), C.byref(h)),
+               "multi_frame_begin")
+        self.h = h
+
+    def close(self):
+        if self.h is not None:
+            lib().rtxh_multi_frame_end(self.h)
+            self.h = None
+
+    def _query(self, what):
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        v = C.c_uint64()
+        _check(lib().rtxh_multi_frame_query(self.h, C.c_int32(what), C.byref(v)), "multi_frame_query")
+        return int(v.value)
+
+    def advance(self, n):
+        """Renders samples [samples_done, min(samples_done + n, spp)) of every pixel, each worker its own; returns (total, [per-device]) stats dicts of the step."""
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        total, per = Stats(), (Stats * len(self.devices))()
+        _check(lib().rtxh_multi_frame_advance(self.h, C.c_int32(int(n)), C.byref(total), per), "multi_frame_advance")
+        return total.as_dict(), [s.as_dict() for s in per]
+
+    def advance_adaptive(self, n, threshold, floor_y=0.0, min_samples=4):
+        """ProgressiveFrame.advance_adaptive on every worker at once (each pixel is decided from its owner's plane); returns (total, [per-device]) stats dicts."""
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        total, per = Stats(), (Stats * len(self.devices))()
+        _check(lib().rtxh_multi_frame_advance_adaptive(self.h, C.c_int32(int(n)), C.c_float(threshold), C.c_float(floor_y), C.c_int32(int(min_samples)), C.byref(total), per),
+               "multi_frame_advance_adaptive")
+        return total.as_dict(), [s.as_dict() for s in per]
+
+    def _read(self, what, scale, channels, dtype, device_out, stream):
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        shape = (self.height, self.width, channels)
+        if device_out is not None:
+            assert tuple(device_out.shape) == shape and device_out.is_contiguous() and device_out.element_size() == np.dtype(dtype).itemsize
+            _check(lib().rtxh_multi_frame_read(self.h, C.c_int32(what), C.c_float(scale), C.c_uint32(RT_FLAG_FILM_ON_DEVICE), C.c_void_p(device_out.data_ptr())), "multi_frame_read")
+            return device_out
+        out = np.zeros(shape, dtype)
+        _check(lib().rtxh_multi_frame_read(self.h, C.c_int32(what), C.c_float(scale), C.c_uint32(0), out.ctypes.data_as(C.c_void_p)), "multi_frame_read")
+        return out
 
 
 def copper():

@@ -1,11 +1,16 @@
 """What rendering a frame in steps costs (MEASUREMENTS "Progressive frames").
 
-    python scripts/progressive_cost.py [--scene cornell|room|...] [--res N] [--spp N] [--steps 8,64] [--out results/progressive_cost.json]
+    python scripts/progressive_cost.py [--scene cornell|room|...] [--res N] [--spp N] [--steps 8,64] [--devices 0:0,0:0,0,0] [--out results/progressive_cost.json]
 
 For the bench workload of the scene: rt_render's ms_total (median of --frames frames after a warm-up), then the frame stepped in each of --steps equal steps, with
 resident sampler tables and with table_budget = 1 (every step rebuilds them): the sum of the steps' ms_total, its ratio to rt_render's, the first step's share, one
 rt_frame_read of each kind, RT_FRAME_STATE_BYTES; and, for the first step count with resident tables, the per-stage HIP-event times (RT_FLAG_TIME_KERNELS) of the
-stepped frame beside rt_render's. Every stepped film is compared with rt_render's bytes."""
+stepped frame beside rt_render's. Every stepped film is compared with rt_render's bytes.
+--devices: worker lists separated by ':' (0:0,0:0,0,0 = one, two and three workers on GPU 0). Per list, the frame across those workers (rt_multi_frame_*) in the first
+step count of --steps with resident tables: the steps' wall time, the slowest worker's share of a step (median over the steps), one read of each kind (median of
+--frames), the bytes the film rows of a read hold - touched_rows x cw x 16 per worker, of which the workers on other devices send theirs over the links -, the state
+bytes, and the film against rt_render's. Beside the one-worker list stands the rt_frame with the same steps. Workers that share a GPU share its compute units: such a
+list measures the cost of the mechanism, not scaling."""
 import argparse
 import json
 import os
@@ -29,6 +34,7 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--steps", default="8,64")
     ap.add_argument("--frames", type=int, default=3)
+    ap.add_argument("--devices", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     host.build()
@@ -80,6 +86,64 @@ def main():
                             tot[k] += st[k]
                 res["stepped_stages"] = dict(steps=n_steps, **tot)
                 print("  stage ms, stepped / rt_render: " + ", ".join(f"{k[3:]} {tot[k]:.1f} / {timed[k]:.1f}" for k in STAGES), flush=True)
+    if a.devices:
+        from rustracer_amd.distributed import touched_rows
+        st = h.setup()
+        cropped, sb = [int(v) for v in st["cropped"]], [int(v) for v in st["sample_bounds"]]
+        cw = cropped[2] - cropped[0]
+        ry = float(h.desc.film.filter_params[1])
+        n_steps = int(a.steps.split(",")[0])
+        budget = None if default_resident else 1 << 36
+        res["multi"] = []
+
+        def timed_reads(fr):
+            reads = {}
+            for name, call in (("xyzw", fr.film), ("rgb", fr.rgb), ("rgb8", fr.display)):
+                call()
+                ts = []
+                for _ in range(a.frames):
+                    t0 = time.perf_counter()
+                    got = call()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                reads[name] = float(np.median(ts))
+                if name == "xyzw":
+                    reads["film"] = got
+            return reads
+
+        for devs in [[int(v) for v in part.split(",")] for part in a.devices.split(":")]:
+            rows = [len(touched_rows(cropped, sb, k, len(devs), ry)) for k in range(len(devs))]
+            with h.progressive_multi(devs, table_budget=budget) as fr:
+                n = max(1, fr.spp // n_steps)
+                wall, share = [], []
+                while fr.samples_done < fr.spp:
+                    t0 = time.perf_counter()
+                    total, per = fr.advance(n)
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    share.append(max(p["ms_total"] for p in per) / max(total["ms_total"], 1e-9))
+                reads = timed_reads(fr)
+                got = reads.pop("film")
+                run = dict(devices=devs, steps=len(wall), sum_ms=float(sum(wall)), ratio=float(sum(wall) / whole), first_step_ms=wall[0],
+                           other_steps_median_ms=float(np.median(wall[1:])) if len(wall) > 1 else None, slowest_worker_share=float(np.median(share)), read_ms=reads,
+                           touched_rows=rows, read_bytes=[r * cw * 16 for r in rows], link_bytes=int(sum(r * cw * 16 for r, d in zip(rows, devs) if d != devs[0])),
+                           state_bytes=fr.state_bytes, film_words_differ=int((got.view(np.uint32) != film.view(np.uint32)).sum()))
+            if len(devs) == 1:   # the rt_frame with the same steps, timed the same way
+                with h.progressive(table_budget=budget) as fr:
+                    wall1 = []
+                    while fr.samples_done < fr.spp:
+                        t0 = time.perf_counter()
+                        fr.advance(n)
+                        wall1.append((time.perf_counter() - t0) * 1e3)
+                    reads1 = timed_reads(fr)
+                    reads1.pop("film")
+                run["rt_frame"] = dict(sum_ms=float(sum(wall1)), other_steps_median_ms=float(np.median(wall1[1:])) if len(wall1) > 1 else None, read_ms=reads1)
+            res["multi"].append(run)
+            print(f"  workers {devs}: {run['steps']} steps sum {run['sum_ms']:.1f} ms = {run['ratio']:.3f} x rt_render (first {wall[0]:.1f}, others median {run['other_steps_median_ms']}), slowest worker's share "
+                  f"{run['slowest_worker_share']:.3f}; read xyzw / rgb / rgb8 {reads['xyzw']:.2f} / {reads['rgb']:.2f} / {reads['rgb8']:.2f} ms; rows per worker {rows} = {run['read_bytes']} bytes, "
+                  f"{run['link_bytes']} over links; state {run['state_bytes'] / 2**20:.1f} MiB; film words that differ from rt_render's: {run['film_words_differ']}", flush=True)
+            if "rt_frame" in run:
+                r1 = run["rt_frame"]
+                print(f"    rt_frame, same steps: sum {r1['sum_ms']:.1f} ms (others median {r1['other_steps_median_ms']}), read xyzw / rgb / rgb8 "
+                      f"{r1['read_ms']['xyzw']:.2f} / {r1['read_ms']['rgb']:.2f} / {r1['read_ms']['rgb8']:.2f} ms", flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -1,7 +1,7 @@
 """Render a pbrt-v3 scene file on the GPU.
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
-                                  [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]]
+                                  [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -13,7 +13,9 @@ name the image goes where the reference writes it: "rt-" + the Film's filename, 
 --adaptive T: the frame is rendered in steps of --preview-every samples (4 if not given) that only the pixels still noisier than T take (rt_frame_advance_adaptive:
 the standard error of a pixel's mean luminance over max(mean, --noise-floor), every pixel at least --min-samples), until no pixel is active or the sampler's count is
 reached; prints samples taken / samples of the full frame; --sample-map out.npy gets the per-pixel sample counts (float64 [height, width]). Such an image is no longer
-the one the run without the flag writes."""
+the one the run without the flag writes.
+--devices 0,1,...: with --preview-every or --adaptive, the frame lives on these GPUs of this process (rt_multi_frame_*; an index may repeat): every step runs on all
+of them at once and the image written is the merged frame; prints the slowest worker's share of each step."""
 import argparse
 import os
 import sys
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--min-samples", type=int, default=8, metavar="M", help="with --adaptive: samples every pixel takes before it may stop")
     ap.add_argument("--noise-floor", type=float, default=1e-3, metavar="F", help="with --adaptive: the error is relative to max(mean luminance, F)")
     ap.add_argument("--sample-map", metavar="OUT.npy", default=None, help="with --adaptive: write the per-pixel sample counts")
+    ap.add_argument("--devices", default=None, metavar="0,1,...", help="with --preview-every / --adaptive: render the frame on these GPUs of this process")
     a = ap.parse_args()
     host.build()
     s = host.PbrtScene(a.scene)
@@ -57,14 +60,30 @@ def main():
         else:
             write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
 
+    devices = [int(v) for v in a.devices.split(",")] if a.devices else None
+    if devices and a.adaptive is None and a.preview_every <= 0:
+        raise SystemExit("--devices goes with --preview-every or --adaptive")
+
+    def begin(**kw):
+        return s.progressive_multi(devices, **kw) if devices else s.progressive(**kw)
+
+    def step_ms(st):
+        """ms_total of a step; a multi frame's step is (total, [per worker]): its slowest worker is printed beside the call's wall time."""
+        if not devices:
+            return st["ms_total"]
+        total, per = st
+        worst = max(p["ms_total"] for p in per)
+        print(f"  step {total['ms_total']:.1f} ms on {len(per)} workers; slowest worker {worst:.1f} ms = {worst / max(total['ms_total'], 1e-9):.3f} of it", flush=True)
+        return total["ms_total"]
+
     if a.adaptive is not None:
         import numpy as np
         stats = {"ms_total": 0.0}
         step = a.preview_every if a.preview_every > 0 else 4
-        with s.progressive(pixel_stats=True) as frame:
+        with begin(pixel_stats=True) as frame:
             spp = frame.spp
             while frame.samples_done < spp:
-                stats["ms_total"] += frame.advance_adaptive(step, a.adaptive, a.noise_floor, a.min_samples)["ms_total"]
+                stats["ms_total"] += step_ms(frame.advance_adaptive(step, a.adaptive, a.noise_floor, a.min_samples))
                 if frame.active_pixels == 0:
                     break
                 if a.preview_every > 0:
@@ -79,10 +98,10 @@ def main():
                 np.save(a.sample_map, counts)
     elif a.preview_every > 0:
         stats = {"ms_total": 0.0}
-        with s.progressive() as frame:
+        with begin() as frame:
             spp = frame.spp
             while frame.samples_done < spp:
-                stats["ms_total"] += frame.advance(a.preview_every)["ms_total"]
+                stats["ms_total"] += step_ms(frame.advance(a.preview_every))
                 film = frame.film()
                 write(film)
                 print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
