@@ -283,6 +283,8 @@ typedef struct rt_stats {
                                 the reference itself runs). The film then equals the oracle's SAMPLER_REF mode sample for sample: weights exact, radiance inside the image gate.
                                 Single device, plain-triangle scenes; stats: camera_rays and the three ray counts. */
 #define RT_FLAG_FRAME_STATS 32u /* rt_frame_begin only (other entry points ignore it): the frame keeps per-pixel luminance moments and accepts rt_frame_advance_adaptive */
+#define RT_FLAG_FRAME_FEATURES 64u /* rt_frame_begin / rt_multi_frame_begin only (other entry points ignore it): the frame keeps per-pixel sums of its samples' first-hit features
+                                      (albedo, normal, depth, coverage), read with RT_FRAME_FEATURES */
 
 typedef struct rt_scene rt_scene;
 
@@ -408,6 +410,30 @@ int rt_bsdf_eval(rt_scene* scene, int32_t material, int32_t front_end, uint64_t 
 int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
                       uint32_t flags, void* stream, float* radiance, float* p_film, rt_stats* stats);
 
+/* First-hit features of every sample of a pixel window: what a denoiser takes as guide images, per camera sample, from the vertex the camera ray reaches - the values the
+ * frame loop has in hand at bounce 0. Window, sample indexing and refusals are rt_render_samples': the pixels of path->pixel_bounds intersected with the film's sample bounds,
+ * features: n_pixels x spp x RT_FEATURE_FLOATS floats, pixels row-major in that window, sample index s = the pixel-keyed sampler's index (spp rounded up to a power of two).
+ * Per sample, in this order:
+ *   o.xyz, d.xyz   the camera ray as ray generation wrote it (PerspectiveCamera::generate_ray_differential + Ray::transform);
+ *   prim, b0, b1   its closest hit in rt_trace_closest's numbering (prim as int bits; a hit inside an object instance is n_top_prims + ...); prim = -1 marks a miss;
+ *   depth          length(p - o), p the point of the SurfaceInteraction the shade kernels build at the hit (Triangle / Sphere::intersect, SurfaceInteraction::transform
+ *                  for a hit inside an instance) - by the same device functions;
+ *   normal.xyz     that interaction's SHADING normal: the interpolated vertex normal where the mesh has normals, else the geometric normal, a quadric's own; world space,
+ *                  unit length, negated where dot(n, d) > 0 so that it faces the ray origin. It is the interaction BEFORE Material::compute_scattering_functions:
+ *                  BUMP MAPS ARE NOT APPLIED;
+ *   albedo.rgb     the factor PathIntegrator::li multiplies beta by at the camera vertex (path.rs:172-196): f * |wi . ns| / pdf of the continuation's Bsdf::sample_f
+ *                  draw - the throughput the shade kernel stores for the path's next vertex, beta having entered as 1. A one-sample estimate of the directional
+ *                  albedo for every material (Kd for a Lambertian surface up to rounding, Kr for a mirror); zero where sample_f returns black or pdf <= 0 and where
+ *                  max_depth == 0 (no Bsdf is built).
+ * A miss has prim = -1 and b0, b1, depth, normal and albedo zero (its ray is still reported).
+ * Each pass ends after the camera vertices are shaded: nothing past them is traced. RT_FLAG_REF_STREAM, an empty window and a NULL output are refused with RT_ERR_INVALID,
+ * and so is, before any device work, a window of more than RT_FEATURE_SAMPLES_MAX (2^25) samples - 2 GiB of features. RT_FLAG_FILM_ON_DEVICE: `features` is a device
+ * pointer. Single device. Under RT_FLAG_TIME_KERNELS the feature kernels' time is part of ms_film, here and in a feature frame's steps. */
+#define RT_FEATURE_FLOATS 16
+#define RT_FEATURE_SAMPLES_MAX 33554432
+int rt_render_sample_features(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                              uint32_t flags, void* stream, float* features);
+
 /* Progressive frames: the frame of rt_render rendered in steps, with the film readable between them. The reference's CLI offers "display image as it is
  * rendered" (-p / --display); it has no checkpoint or resume. The pixel-keyed sampler makes sample s of pixel p the same whichever call renders it, so a frame
  * can stop after any number of samples per pixel and go on later.
@@ -451,8 +477,20 @@ int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_de
  *   before; but which pixels go on sampling depends on their own estimates, which gives the small bias every variance-driven sampler has (a pixel whose early
  *   samples happen to agree stops early). RT_FRAME_SAMPLES_DONE then means "sample indices offered", not "samples every pixel holds".
  * rt_frame_query, further: RT_FRAME_SAMPLES_TAKEN - the sum of camera_rays over the frame's steps (kept on the host); RT_FRAME_ACTIVE_PIXELS - the number of
- *   active pixels of the last adaptive step, 0 before one has run. */
-enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2, RT_FRAME_STATS = 3 };
+ *   active pixels of the last adaptive step, 0 before one has run.
+ *
+ * First-hit feature planes (opt-in: a frame begun without RT_FLAG_FRAME_FEATURES launches exactly the kernels described above, and its film and rt_stats are untouched).
+ * RT_FLAG_FRAME_FEATURES gives the frame one more plane, 64 B per owned pixel, zero at begin and counted in RT_FRAME_STATE_BYTES: double sums of albedo rgb, normal xyz and
+ *   depth - the per-sample values of rt_render_sample_features -, uint32 n (samples taken) and uint32 hits (of them, camera rays that hit a surface). Once per pass one
+ *   lane per pixel adds the pixel's samples in sample-index order: no atomics, the sums of a sequential loop. Only samples that were traced count: inside pixel_bounds and
+ *   the shard's rows, and of a pixel that is active in an adaptive step. THE PLANES ARE UNFILTERED: a pixel's entry holds its own samples only, whatever the film's filter.
+ *   The flag combines freely with RT_FLAG_FRAME_STATS; film and statistics plane are the same bytes with and without it. One difference in rt_stats: a feature frame of
+ *   max_depth == 1 casts the continuation rays of its camera vertices, which a frame without the flag leaves out (nothing reads them; the albedo is their stored throughput) -
+ *   rays_tail_not_cast and the rays actually cast differ there, as they do under RTX_DEAD_TAIL=0, and the film does not.
+ * rt_frame_read(RT_FRAME_FEATURES): W*H*8 float32 over the cropped pixel bounds - albedo.rgb = (float)(sum / n), normal.xyz = (float)(sum / n) (not renormalised: misses
+ *   add zero), depth = (float)(sum / hits) or 0 when hits == 0, coverage = (float)((double)hits / n); IEEE double divisions. Zeros where n == 0, in rows of other ranks and
+ *   before the first step; scale ignored; RT_ERR_INVALID on a frame begun without the flag. */
+enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2, RT_FRAME_STATS = 3, RT_FRAME_FEATURES = 4 };
 enum { RT_FRAME_SAMPLES_DONE = 0, RT_FRAME_SPP = 1, RT_FRAME_TABLES_RESIDENT = 2, RT_FRAME_STATE_BYTES = 3, RT_FRAME_SAMPLES_TAKEN = 4, RT_FRAME_ACTIVE_PIXELS = 5 };
 typedef struct rt_frame rt_frame;
 int rt_frame_begin(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
@@ -468,7 +506,7 @@ void rt_frame_end(rt_frame* frame);
  *   RT_SHARD_ROWS rows: a pixel's own sum, its sampler tables and its moments live on one device for the life of the frame, so the chunk queue of rt_multi_render
  *   does not apply. It refuses what rt_frame_begin refuses, before any device work and with rt_frame_begin's messages, and a NULL multi; if one worker's begin
  *   fails, the frames already opened are ended and the first error is returned. table_budget_bytes is per worker (0: rt_frame_begin's default). flags:
- *   RT_FLAG_FRAME_STATS / _COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED pass through. A worker with nothing to trace - it owns no row (fewer bands than workers), or
+ *   RT_FLAG_FRAME_STATS / _FRAME_FEATURES / _COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED pass through. A worker with nothing to trace - it owns no row (fewer bands than workers), or
  *   none of its rows lies inside pixel_bounds - is legal: its steps launch nothing and its step stats are zero.
  * rt_multi_frame_advance / _advance_adaptive: one host thread per worker runs rt_frame_advance (_adaptive) on its own frame and stream, all at once. per_device
  *   (n_devices entries, may be NULL): worker k's step stats; total (may be NULL): their sum, with ms_total the wall time of the call. An adaptive step decides
@@ -479,7 +517,7 @@ void rt_frame_end(rt_frame* frame);
  *   (float32 RGB sums, before any colour conversion) for the film rows it can have touched - its bands widened by the filter's reach -, only those rows travel to
  *   devices[0] (hipMemcpyPeerAsync), and one kernel there adds c_0[i] + c_1[i] + ... left to right in worker order over the workers whose rows hold i and reads
  *   the sum out with rt_frame_read's arithmetic. what / scale as in rt_frame_read; RT_FRAME_STATS takes each pixel's (n, sum_y, sum_y2) from its owner, nothing
- *   is added. out: host memory, or memory of devices[0] with RT_FLAG_FILM_ON_DEVICE in `flags`. The frame owns every buffer of the read: an rt_multi_render on the
+ *   is added, and RT_FRAME_FEATURES likewise takes each pixel's feature sums from its owner's plane. out: host memory, or memory of devices[0] with RT_FLAG_FILM_ON_DEVICE in `flags`. The frame owns every buffer of the read: an rt_multi_render on the
  *   same rt_multi between two steps disturbs nothing.
  * rt_multi_frame_query: RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP as for one frame; RT_FRAME_TABLES_RESIDENT: 1 only if resident on every worker that owns pixels;
  *   RT_FRAME_STATE_BYTES (the workers' frames and the buffers of the read), RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS: sums over the workers.

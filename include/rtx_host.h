@@ -145,6 +145,9 @@ int rtxh_render(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float*
  * row-major. radiance: pixels x spp x 4 floats (spp rounded up to a power of two), p_film: pixels x spp x 2 or NULL; host pointers, or device pointers with
  * RT_FLAG_FILM_ON_DEVICE. rank / world_size of the parameters are ignored. */
 int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* radiance, float* p_film, rt_stats* stats);
+/* The first-hit features of the same window's samples (rt_render_sample_features in rtx_hip.h): features: pixels x spp x RT_FEATURE_FLOATS floats; a host pointer, or a
+ * device pointer with RT_FLAG_FILM_ON_DEVICE. Window and set-up as for rtxh_render_samples; more than RT_FEATURE_SAMPLES_MAX samples are refused. */
+int rtxh_render_sample_features(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* features);
 /* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
  * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
  * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */

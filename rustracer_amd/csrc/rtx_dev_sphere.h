@@ -249,6 +249,15 @@ RT_DEVN bool sphere_test(const DSphere& s, f3 o, f3 d, float t_max, float& t_hit
 // the same inline: for the kernels whose only large callee it would be (RT_GEN_NO_MASKS) - inside the kernel it falls under the kernel's register bound
 RT_DEV bool sphere_test_inl(const DSphere& s, f3 o, f3 d, float t_max, float& t_hit) { return sphere_intersect<false>(s, o, d, t_max, t_hit, nullptr); }
 RT_DEVN bool sphere_fill_interaction(const DSphere& s, f3 o, f3 d, SurfaceInteraction& si) { float t; return sphere_intersect<true>(s, o, d, kInf, t, &si); }
+// The same interaction handed to `f` instead of stored, inline: each kind of quadric fills an interaction of its own and returns f's value (k_feature_hits reads two
+// fields of it: with the three kinds writing one struct the compiler kept part of the struct in memory)
+template <class F>
+RT_DEV auto quadric_interaction_visit(const DSphere& s, f3 o, f3 d, F f) {
+  float t;
+  if (s.kind == 1) { SurfaceInteraction si; (void)disk_intersect<true>(s, o, d, kInf, t, &si); return f(si); }
+  if (s.kind == 2) { SurfaceInteraction si; (void)cylinder_intersect<true>(s, o, d, kInf, t, &si); return f(si); }
+  SurfaceInteraction si; (void)sphere_only_intersect<true>(s, o, d, kInf, t, &si); return f(si);
+}
 
 struct SpherePoint { f3 p, p_error, n; };
 RT_DEV SpherePoint sphere_sample(const DSphere& s, f2 u, float& pdf) {  // Sphere::sample, :227-244

@@ -99,6 +99,8 @@ struct rt_scene {
   DevBuf ws[32];
   DevBuf film_acc, own_acc, film_out, counters, stats, filter_table, ref_samples, ref_stack;
   DevBuf samples_rad, samples_pf;  // rt_render_samples with host outputs: [window pixel][sample] radiance (float4) and film position (float2)
+  DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
+  DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
   DevBuf bsdf_self, bsdf_tris;     // rt_bsdf_eval: a copy of `d` whose tri_p names two primitive records that carry nothing but the orientation flag (0, 1) - what a bump map reads of si.prim
   int bsdf_launched = -1;          // rt_bsdf_eval: 2 * mode + const_tex of the k_bsdf_eval instantiation the last call launched (RT_QUERY_BSDF_LAUNCHED)
   std::vector<int> mat_class;      // per material: its code class (DMaterial::code_class) - the front-end ranges of rt_render, for rt_bsdf_eval
@@ -1016,7 +1018,10 @@ struct rt_frame {
   bool stats = false;
   DevBuf moments, active, n_active;
   unsigned long long samples_taken = 0, active_pixels = 0;  // sum of camera_rays over the steps; set bytes of the last adaptive step's mask
-  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes; }
+  // RT_FLAG_FRAME_FEATURES: [owned pixel] sums of the first-hit features of the pixel's own samples (PixFeatures, 64 B, zero at begin)
+  bool features = false;
+  DevBuf feature_plane;
+  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes + feature_plane.bytes; }
 };
 static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u * (size_t)(owned_pixels / 4096u + 4u); }  // alignment room: a batch holds >= 4096 pixels, plus a leading and a last one
 
@@ -1026,10 +1031,15 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // FRAME's sums by k_film_accumulate_frame (nothing is zeroed, nothing is finalised or copied out), with the frame's resident sampler tables where it has them.
 // A frame with RT_FLAG_FRAME_STATS launches k_film_accumulate_frame_stats instead. active_mask != NULL: the step of rt_frame_advance_adaptive, which holds the scene's
 // mutex already (have_lock) - k_raygen_masked marks the samples of pixels whose byte is 0 out of bounds, so every pass takes the route of a cropping pixel_bounds.
+// First-hit features: a frame begun with RT_FLAG_FRAME_FEATURES (fr->features), or samples_feat != NULL - the frame of rt_render_sample_features, whose passes end after
+// bounce 0's shade launches. Either launches k_feature_hits and k_feature_albedo right after those launches, before bounce 1's trace overwrites the hit records, and casts
+// the continuation rays of a max_depth == 1 frame (nothing reads them: PassState::skip_dead_tail is cleared for bounce 0, whose throughput record is the albedo). No other
+// frame launches either kernel.
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
-                        rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false) {
+                        rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr) {
   const bool samples = samples_rad != nullptr;
+  const bool fsamples = samples_feat != nullptr, features = fsamples || (fr && fr->features);
   // the window of rt_render_samples: pixel_bounds inside the sample bounds, and its size - checked before any device work
   const int wx0 = std::max(path->pixel_bounds[0], film->sample_bounds[0]), wy0 = std::max(path->pixel_bounds[1], film->sample_bounds[1]);
   const int wx1 = std::min(path->pixel_bounds[2], film->sample_bounds[2]), wy1 = std::min(path->pixel_bounds[3], film->sample_bounds[3]);
@@ -1040,6 +1050,13 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     const unsigned long long spp_r = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
     n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * spp_r;
     if (spp_r > 16384ull || n_window_samples > (unsigned long long)RT_SAMPLES_MAX) return fail(RT_ERR_INVALID, "rt_render_samples: the window holds more than RT_SAMPLES_MAX (2^27) samples");
+  }
+  if (fsamples) {
+    if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_sample_features: the reference-stream frame has no per-sample output");
+    if (wx1 <= wx0 || wy1 <= wy0) return fail(RT_ERR_INVALID, "rt_render_sample_features: pixel_bounds and the film's sample bounds share no pixel");
+    const unsigned long long spp_r = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
+    n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * spp_r;
+    if (spp_r > 16384ull || n_window_samples > (unsigned long long)RT_FEATURE_SAMPLES_MAX) return fail(RT_ERR_INVALID, "rt_render_sample_features: the window holds more than RT_FEATURE_SAMPLES_MAX (2^25) samples");
   }
   std::unique_lock<std::mutex> render_lock(s->render_mutex, std::defer_lock);
   if (!have_lock) render_lock.lock();
@@ -1187,13 +1204,15 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         {&s->ws[B_SH], cap * 48}, {&s->ws[B_MI], cap * 100}, {&s->ws[B_OCCSH], cap}, {&s->ws[B_OCCMI], cap},
         {&s->ws[B_QSH], szq}, {&s->ws[B_QMI], szq}, {&s->ws[B_QMA], has_infinite ? szq : 16},
         {&s->counters, counter_words * 4}, {&s->stats, (size_t)ST_COUNT * 8}};
-    if (!fr) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
+    if (!fr && !fsamples) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
     if (!resident) { want.push_back({&s->scrambles[0], (size_t)chunk_pixels * 3 * dims * 4}); want.push_back({&s->perms[0], (size_t)(chunk_pixels * table_bytes_per_pixel)}); }
     if (build_tables) want.push_back({&s->sampler_plan.partners, (size_t)(chunk_pixels * table_bytes_per_pixel)});
     if (use_bins) { want.push_back({&s->bin_words, (size_t)(fp.max_depth + 1) * bin_stride * 4}); want.push_back({&s->bin_sorted, (size_t)cap * 4}); want.push_back({&s->bin_at, (size_t)cap * 2}); }
     if (multi_batch && !resident) { want.push_back({&s->scrambles[1], (size_t)chunk_pixels * 3 * dims * 4}); want.push_back({&s->perms[1], (size_t)(chunk_pixels * table_bytes_per_pixel)}); }
+    if (features && !fsamples) want.push_back({&s->feat, cap * 32});
     if (!(flags & RT_FLAG_FILM_ON_DEVICE) && !fr) {
-      if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
+      if (fsamples) want.push_back({&s->samples_feat, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4});
+      else if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
       else { want.push_back({&s->samples_rad, (size_t)n_window_samples * 16}); if (samples_pf) want.push_back({&s->samples_pf, (size_t)n_window_samples * 8}); }
     }
     size_t grow = 0;  // bytes the buffers have to grow by (a buffer that is too small is freed and allocated anew)
@@ -1217,7 +1236,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   float4* const d_out = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)film_xyzw : s->film_out.as<float4>();
   float4* const d_samples_rad = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)samples_rad : s->samples_rad.as<float4>();
   float2* const d_samples_pf = !samples_pf ? nullptr : ((flags & RT_FLAG_FILM_ON_DEVICE) ? (float2*)samples_pf : s->samples_pf.as<float2>());
-  if (!samples && !fr) {  // (no kernel of a samples frame reads the filter table or the film sums; a progressive frame keeps its own)
+  FeatureOut fo{};
+  if (fsamples) { fo.samples = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)samples_feat : s->samples_feat.as<float4>(); fo.wx0 = wx0; fo.wy0 = wy0; fo.ww = wx1 - wx0; }
+  else if (features) { fo.nd = s->feat.as<float4>(); fo.ah = fo.nd + cap; }
+  if (!samples && !fsamples && !fr) {  // (no kernel of a samples frame reads the filter table or the film sums; a progressive frame keeps its own)
     HIP_TRY(hipMemcpyAsync(s->filter_table.p, film->filter_table, 1024, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)cw * ch * 16, stream));
   }
@@ -1321,6 +1343,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       ps.skip_unreachable_mis = (!reach_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
       static const bool tail_off = env_is("RTX_DEAD_TAIL", '0');  // measurement knob: cast the rays nothing reads as well
       ps.skip_dead_tail = (!tail_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
+      const int skip_dead_tail = ps.skip_dead_tail;
       tm.begin(&stats.ms_raygen);
       if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
       else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
@@ -1329,6 +1352,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         ps.cnt_in = cb + (size_t)bounce * RT_NQ * RT_QSHARDS * RT_CNT_STRIDE; ps.cnt_out = cb + (size_t)(bounce + 1) * RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;
         std::swap(ps.in, ps.out);  // what the previous stage appended is this bounce's input
         if (bounce == 0 && all_in_bounds) ps.cnt_in = nullptr;  // identity: entry i is slot i is path i
+        ps.skip_dead_tail = (features && bounce == 0 && fp.max_depth == 1) ? 0 : skip_dead_tail;  // (a feature frame reads bounce 0's throughput record: the continuation is stored, and cast, at that depth too)
         ps.fresh = bounce == 0 ? fresh_planes : 0;                // ... whose throughput / state records are rebuilt, not read
         io_path.ray_o = ps.in.o; io_path.ray_d = ps.in.d;
         tm.begin(&stats.ms_trace_closest);
@@ -1364,6 +1388,14 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
           pb.range = ranges + 6; tm.begin(&stats.ms_shade_miss); hipLaunchKernelGGL(k_shade_miss, dim3(pgrid), dim3(256), 0, stream, s->d, pb); tm.end();
         }
 #undef RT_SHADE
+        if (features && bounce == 0) {  // the camera vertices' features, while ps.hit still holds bounce 0's hits (timed with the film stage: ms_film)
+          tm.begin(&stats.ms_film);
+          rtx_launch_feature_hits(fsamples, s->has_spheres || s->has_instances, pgrid, stream, s->d, fp, ps, fo);
+          if (fsamples) hipLaunchKernelGGL(k_feature_albedo<true>, dim3(pgrid), dim3(256), 0, stream, fp, ps, fo);
+          else hipLaunchKernelGGL(k_feature_albedo<false>, dim3(pgrid), dim3(256), 0, stream, fp, ps, fo);
+          tm.end();
+          if (fsamples) break;  // (rt_render_sample_features: nothing past the camera vertex is read)
+        }
         tm.begin(&stats.ms_trace_any);
         launch_trace<true>(s, count, io_shadow, ps.q_shadow, ps.cnt_out + RT_QSHARDS * RT_CNT_STRIDE, ps.shard_cap, 0, dstats, ST_RAYS_SHADOW, ST_NODES_SHADOW, ST_TRIS_SHADOW, stream);
         tm.end();
@@ -1382,10 +1414,12 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         stats.launches_trace_closest += 2; stats.launches_trace_path += 1; stats.launches_trace_mis += 1; stats.launches_trace_shadow += 1; stats.launches_trace_mis_any += ps.mis_any ? 1 : 0;
       }
       tm.begin(&stats.ms_film);
-      if (samples) hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, ps, wx0, wy0, wx1 - wx0, d_samples_rad, d_samples_pf);
+      if (fsamples) { }  // (the feature kernels wrote the output)
+      else if (samples) hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, ps, wx0, wy0, wx1 - wx0, d_samples_rad, d_samples_pf);
       else if (fr && fr->stats) hipLaunchKernelGGL(k_film_accumulate_frame_stats, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), fr->moments.as<PixMoments>());
       else if (fr) hipLaunchKernelGGL(k_film_accumulate_frame, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>());
       else hipLaunchKernelGGL(k_film_accumulate, dim3(pgrid), dim3(256), 0, stream, fp, ps, s->filter_table.as<float>(), s->film_acc.as<float4>());
+      if (fr && fr->features) hipLaunchKernelGGL(k_feature_accumulate, dim3(pgrid), dim3(256), 0, stream, fp, ps, fo.nd, fo.ah, fr->feature_plane.as<PixFeatures>());
       tm.end();
       stats.n_passes += 1;
       HIP_TRY(hipGetLastError());
@@ -1397,6 +1431,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       HIP_TRY(hipStreamSynchronize(aux));
       fr->tables_built = true; fr->batch_pixels = batch_pixels; fr->lead_pixels = lead_pixels;
     }
+  } else if (fsamples) {
+    if (!(flags & RT_FLAG_FILM_ON_DEVICE)) HIP_TRY(hipMemcpyAsync(samples_feat, fo.samples, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4, hipMemcpyDeviceToHost, stream));
   } else if (!samples) {
     tm.begin(&stats.ms_film);
     {
@@ -1441,6 +1477,11 @@ extern "C" int rt_render_samples(rt_scene* s, const rt_camera* cam, const rt_fil
                                  uint32_t flags, void* stream_, float* radiance, float* p_film, rt_stats* stats_out) {
   if (!s || !cam || !film || !smp || !path || !radiance) return fail(RT_ERR_INVALID, "rt_render_samples: null argument");
   return render_frame(s, cam, film, smp, path, nullptr, flags, stream_, nullptr, stats_out, radiance, p_film);
+}
+extern "C" int rt_render_sample_features(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                                         uint32_t flags, void* stream_, float* features) {
+  if (!s || !cam || !film || !smp || !path || !features) return fail(RT_ERR_INVALID, "rt_render_sample_features: null argument");
+  return render_frame(s, cam, film, smp, path, nullptr, flags & ~(uint32_t)RT_FLAG_FRAME_FEATURES, stream_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, features);
 }
 
 // ---------------------------------------------------------------------------------------------- progressive frames
@@ -1491,6 +1532,12 @@ extern "C" int rt_frame_begin(rt_scene* s, const rt_camera* cam, const rt_film_d
     HIP_TRY(hipMemset(fr->moments.p, 0, mom_bytes));
     HIP_TRY(hipMemset(fr->active.p, 0, mask_bytes));
     fr->stats = true;
+  }
+  if (flags & RT_FLAG_FRAME_FEATURES) {  // the first-hit feature plane
+    const size_t feat_bytes = std::max<size_t>((size_t)fr->owned_pixels * sizeof(PixFeatures), sizeof(PixFeatures));
+    if (fr->feature_plane.ensure(feat_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(RT_ERR_OOM, "rt_frame_begin: not enough device memory for the frame's feature plane"); }
+    HIP_TRY(hipMemset(fr->feature_plane.p, 0, feat_bytes));
+    fr->features = true;
   }
   if (fr->owned_pixels > 0 && perm_bytes + scr_bytes <= budget) {
     const size_t slack = frame_table_slack(fr->owned_pixels);
@@ -1561,21 +1608,26 @@ extern "C" int rt_frame_advance_adaptive(rt_frame* fr, int32_t n_samples, float 
   if (stats_out) *stats_out = st;
   return RT_OK;
 }
+static size_t frame_read_bytes(int32_t what) {  // bytes per cropped pixel of a read-out
+  return what == RT_FRAME_FEATURES ? 32 : (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
+}
 extern "C" int rt_frame_read(rt_frame* fr, int32_t what, float scale, uint32_t flags, void* stream_, void* out) {
   if (!fr || !out) return fail(RT_ERR_INVALID, "rt_frame_read: null argument");
-  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
+  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS && what != RT_FRAME_FEATURES) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
   if (what == RT_FRAME_STATS && !fr->stats) return fail(RT_ERR_INVALID, "rt_frame_read: RT_FRAME_STATS needs a frame begun with RT_FLAG_FRAME_STATS");
+  if (what == RT_FRAME_FEATURES && !fr->features) return fail(RT_ERR_INVALID, "rt_frame_read: RT_FRAME_FEATURES needs a frame begun with RT_FLAG_FRAME_FEATURES");
   rt_scene* s = fr->scene;
   std::lock_guard<std::mutex> render_lock(s->render_mutex);  // (steps of this frame on other threads, and the staging buffer)
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t stream = (hipStream_t)stream_;
   const FrameParams fp = frame_pixel_params(fr);
   const unsigned long long n = (unsigned long long)(fp.crop_x1 - fp.crop_x0) * (unsigned long long)(fp.crop_y1 - fp.crop_y0);
-  const size_t bytes = (size_t)n * (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
+  const size_t bytes = (size_t)n * frame_read_bytes(what);
   const bool on_device = (flags & RT_FLAG_FILM_ON_DEVICE) != 0;
-  if (!on_device) HIP_TRY(fr->out.ensure((size_t)n * (what == RT_FRAME_STATS ? 24 : 16)));  // (ensure only ever grows the staging buffer)
+  if (!on_device) HIP_TRY(fr->out.ensure((size_t)n * std::max<size_t>(frame_read_bytes(what), 16)));  // (ensure only ever grows the staging buffer)
   void* const d_out = on_device ? out : fr->out.p;
-  if (what == RT_FRAME_STATS) hipLaunchKernelGGL(k_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->moments.as<PixMoments>(), (double*)d_out, n);
+  if (what == RT_FRAME_FEATURES) hipLaunchKernelGGL(k_frame_features_read<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, (const PixFeatures* const*)nullptr, fr->feature_plane.as<PixFeatures>(), (float*)d_out, n);
+  else if (what == RT_FRAME_STATS) hipLaunchKernelGGL(k_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->moments.as<PixMoments>(), (double*)d_out, n);
   else hipLaunchKernelGGL(k_frame_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), (int)what, scale, d_out, n);
   HIP_TRY(hipGetLastError());
   if (!on_device) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, stream));
@@ -1791,20 +1843,20 @@ extern "C" int rt_multi_render(rt_multi* m, const rt_camera* cam, const rt_film_
 struct rt_multi_frame {
   rt_multi* m = nullptr;
   std::vector<rt_frame*> frames;
-  bool broken = false, stats = false;
+  bool broken = false, stats = false, features = false;
   std::vector<char> idle;  // per worker: it owns no row, or none of its rows lies inside pixel_bounds - its steps launch nothing
   int cw = 0, ch = 0;
   struct Worker {
     std::vector<int> rows;                 // film rows (cropped coordinates, ascending) the worker can have touched: its bands widened by the filter's reach
     DevBuf rows_dev, packed;               // on the worker's device: `rows`, and c_k for them
-    DevBuf staged, moments_staged;         // on devices[0], for a worker of another device: where its packed rows / its moments plane arrive
+    DevBuf staged, moments_staged, features_staged;  // on devices[0], for a worker of another device: where its packed rows / its moments plane / its feature plane arrive
     hipEvent_t ready = nullptr;            // on the worker's device: its rows (or its plane) are on devices[0]
   };
   std::vector<Worker> w;
-  DevBuf slot, packed_ptrs, moment_ptrs, out;  // on devices[0]: [worker][film row] -> row of its packed buffer or -1, the workers' buffers as the merge kernels see them, read staging
+  DevBuf slot, packed_ptrs, moment_ptrs, feature_ptrs, out;  // on devices[0]: [worker][film row] -> row of its packed buffer or -1, the workers' buffers as the merge kernels see them, read staging
   size_t state_bytes() const {
-    size_t b = slot.bytes + packed_ptrs.bytes + moment_ptrs.bytes + out.bytes;
-    for (const Worker& k : w) b += k.rows_dev.bytes + k.packed.bytes + k.staged.bytes + k.moments_staged.bytes;
+    size_t b = slot.bytes + packed_ptrs.bytes + moment_ptrs.bytes + feature_ptrs.bytes + out.bytes;
+    for (const Worker& k : w) b += k.rows_dev.bytes + k.packed.bytes + k.staged.bytes + k.moments_staged.bytes + k.features_staged.bytes;
     return b;
   }
 };
@@ -1820,7 +1872,7 @@ extern "C" int rt_multi_frame_begin(rt_multi* m, const rt_camera* cam, const rt_
   if (!m) return fail(RT_ERR_INVALID, "rt_multi_frame_begin: null multi");
   const int n = (int)m->devices.size();
   std::unique_ptr<rt_multi_frame, void (*)(rt_multi_frame*)> mf(new rt_multi_frame(), multi_frame_free);
-  mf->m = m; mf->frames.assign(n, nullptr); mf->w.resize(n); mf->stats = (flags & RT_FLAG_FRAME_STATS) != 0;
+  mf->m = m; mf->frames.assign(n, nullptr); mf->w.resize(n); mf->stats = (flags & RT_FLAG_FRAME_STATS) != 0; mf->features = (flags & RT_FLAG_FRAME_FEATURES) != 0;
   for (int k = 0; k < n; ++k) {  // (worker 0's begin refuses a faulty description before any device work, with rt_frame_begin's message; a later failure ends the frames opened so far)
     const rt_shard sh{k, n};
     const int rc = rt_frame_begin(m->replicas[k], cam, film, smp, path, &sh, flags, table_budget_bytes, &mf->frames[k]);
@@ -1837,7 +1889,7 @@ extern "C" int rt_multi_frame_begin(rt_multi* m, const rt_camera* cam, const rt_
   const int halo = (int)std::ceil(film->filter_radius[1] - 0.5f) + 1;
   const int band = RT_SHARD_ROWS(H, n), n_bands = (H + band - 1) / band;
   std::vector<int> slot((size_t)n * ch, -1);
-  std::vector<const void*> packed_ptrs(n, nullptr), moment_ptrs(n, nullptr);
+  std::vector<const void*> packed_ptrs(n, nullptr), moment_ptrs(n, nullptr), feature_ptrs(n, nullptr);
   for (int k = 0; k < n; ++k) {
     rt_multi_frame::Worker& wk = mf->w[k];
     for (int t = k; t < n_bands; t += n) {
@@ -1852,11 +1904,12 @@ extern "C" int rt_multi_frame_begin(rt_multi* m, const rt_camera* cam, const rt_
       HIP_TRY(hipMemcpy(wk.rows_dev.p, wk.rows.data(), wk.rows.size() * sizeof(int), hipMemcpyHostToDevice));
       HIP_TRY(wk.packed.ensure(wk.rows.size() * (size_t)cw * 16));
     }
-    packed_ptrs[k] = wk.packed.p; moment_ptrs[k] = mf->frames[k]->moments.p;
+    packed_ptrs[k] = wk.packed.p; moment_ptrs[k] = mf->frames[k]->moments.p; feature_ptrs[k] = mf->frames[k]->feature_plane.p;
     if (remote) {
       HIP_TRY(hipSetDevice(m->devices[0]));
       if (!wk.rows.empty()) { HIP_TRY(wk.staged.ensure(wk.packed.bytes)); packed_ptrs[k] = wk.staged.p; }
       if (mf->stats) { HIP_TRY(wk.moments_staged.ensure(mf->frames[k]->moments.bytes)); moment_ptrs[k] = wk.moments_staged.p; }
+      if (mf->features) { HIP_TRY(wk.features_staged.ensure(mf->frames[k]->feature_plane.bytes)); feature_ptrs[k] = wk.features_staged.p; }
     }
   }
   HIP_TRY(hipSetDevice(m->devices[0]));
@@ -1866,6 +1919,8 @@ extern "C" int rt_multi_frame_begin(rt_multi* m, const rt_camera* cam, const rt_
   HIP_TRY(hipMemcpy(mf->packed_ptrs.p, packed_ptrs.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice));
   HIP_TRY(mf->moment_ptrs.ensure((size_t)n * sizeof(void*)));
   HIP_TRY(hipMemcpy(mf->moment_ptrs.p, moment_ptrs.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice));
+  HIP_TRY(mf->feature_ptrs.ensure((size_t)n * sizeof(void*)));
+  HIP_TRY(hipMemcpy(mf->feature_ptrs.p, feature_ptrs.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice));
   *out = mf.release();
   return RT_OK;
 }
@@ -1920,12 +1975,13 @@ extern "C" int rt_multi_frame_advance_adaptive(rt_multi_frame* mf, int32_t n_sam
 extern "C" int rt_multi_frame_read(rt_multi_frame* mf, int32_t what, float scale, uint32_t flags, void* out) {
   if (!mf || !out) return fail(RT_ERR_INVALID, "rt_multi_frame_read: null argument");
   if (mf->broken) return fail(RT_ERR_INVALID, "rt_multi_frame_read: the frame is broken (an earlier step failed on a worker): end it");
-  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS) return fail(RT_ERR_INVALID, "rt_multi_frame_read: unknown read-out");
+  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS && what != RT_FRAME_FEATURES) return fail(RT_ERR_INVALID, "rt_multi_frame_read: unknown read-out");
   if (what == RT_FRAME_STATS && !mf->stats) return fail(RT_ERR_INVALID, "rt_multi_frame_read: RT_FRAME_STATS needs a frame begun with RT_FLAG_FRAME_STATS");
+  if (what == RT_FRAME_FEATURES && !mf->features) return fail(RT_ERR_INVALID, "rt_multi_frame_read: RT_FRAME_FEATURES needs a frame begun with RT_FLAG_FRAME_FEATURES");
   rt_multi* m = mf->m;
   const int n_w = (int)mf->frames.size();
   const unsigned long long n = (unsigned long long)mf->cw * (unsigned long long)mf->ch;
-  const size_t bytes = (size_t)n * (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
+  const size_t bytes = (size_t)n * frame_read_bytes(what);
   const bool on_device = (flags & RT_FLAG_FILM_ON_DEVICE) != 0;
   // every worker's part, on its own stream and device; streams[0] then waits for the parts of the others
   for (int k = 0; k < n_w; ++k) {
@@ -1936,6 +1992,8 @@ extern "C" int rt_multi_frame_read(rt_multi_frame* mf, int32_t what, float scale
     if (what == RT_FRAME_STATS) {
       if (remote)  // (a plane on devices[0] is read where it lies)
         HIP_TRY(hipMemcpyPeerAsync(wk.moments_staged.p, m->devices[0], fr->moments.p, m->devices[k], fr->moments.bytes, m->streams[k]));
+    } else if (what == RT_FRAME_FEATURES) {
+      if (remote) HIP_TRY(hipMemcpyPeerAsync(wk.features_staged.p, m->devices[0], fr->feature_plane.p, m->devices[k], fr->feature_plane.bytes, m->streams[k]));
     } else if (!wk.rows.empty()) {
       const FrameParams fp = frame_pixel_params(fr);
       const unsigned long long np = (unsigned long long)wk.rows.size() * (unsigned long long)mf->cw;
@@ -1949,9 +2007,12 @@ extern "C" int rt_multi_frame_read(rt_multi_frame* mf, int32_t what, float scale
   HIP_TRY(hipSetDevice(m->devices[0]));
   hipStream_t s0 = m->streams[0];
   for (int k = 1; k < n_w; ++k) HIP_TRY(hipStreamWaitEvent(s0, mf->w[k].ready, 0));
-  if (!on_device) HIP_TRY(mf->out.ensure((size_t)n * (what == RT_FRAME_STATS ? 24 : 16)));  // (ensure only ever grows the staging buffer)
+  if (!on_device) HIP_TRY(mf->out.ensure((size_t)n * std::max<size_t>(frame_read_bytes(what), 16)));  // (ensure only ever grows the staging buffer)
   void* const d_out = on_device ? out : mf->out.p;
-  if (what == RT_FRAME_STATS) {
+  if (what == RT_FRAME_FEATURES) {
+    const FrameParams fp = frame_pixel_params(mf->frames[0]);  // (rank is not read: the owner is the band's)
+    hipLaunchKernelGGL(k_frame_features_read<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, fp, (const PixFeatures* const*)mf->feature_ptrs.p, (const PixFeatures*)nullptr, (float*)d_out, n);
+  } else if (what == RT_FRAME_STATS) {
     const FrameParams fp = frame_pixel_params(mf->frames[0]);  // (rank is not read: the owner is the band's)
     hipLaunchKernelGGL(k_multi_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s0, fp, (const PixMoments* const*)mf->moment_ptrs.p, (double*)d_out, n);
   } else {

@@ -1268,6 +1268,7 @@ int rtxh_render(rtxh_scene* s, const rtxh_render_params* p, void* stream, float*
   rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
   return rt_render(s->dev, &cf.cam, &cf.film, &smp, &path, &shard, p->flags, stream, film_xyzw, stats);
 }
+static void sampler_path_of(const rtxh_render_params* p, const CamFilm& cf, rt_sampler_desc& smp, rt_path_desc& path);
 int rtxh_render_samples(rtxh_scene* s, const rtxh_render_params* p, void* stream, float* radiance, float* p_film, rt_stats* stats) {
   if (!s || !p || !radiance) return fail(RT_ERR_INVALID, "null argument");
   g_err.clear();
@@ -1288,6 +1289,21 @@ int rtxh_render_samples(rtxh_scene* s, const rtxh_render_params* p, void* stream
   }
   if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_render_samples(s->dev, &cf.cam, &cf.film, &smp, &path, p->flags, stream, radiance, p_film, stats);
+}
+int rtxh_render_sample_features(rtxh_scene* s, const rtxh_render_params* p, void* stream, float* features) {
+  if (!s || !p || !features) return fail(RT_ERR_INVALID, "rtxh_render_sample_features: null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp; rt_path_desc path; sampler_path_of(p, cf, smp, path);
+  {  // the size rt_render_sample_features refuses, before the scene is uploaded for it
+    const int* pb = path.pixel_bounds;
+    unsigned long long spp = 1; while (spp < (unsigned long long)std::max(p->spp, 1)) spp <<= 1;
+    if (pb[2] <= pb[0] || pb[3] <= pb[1]) return fail(RT_ERR_INVALID, "rtxh_render_sample_features: the pixel bounds hold no pixel");
+    if ((unsigned long long)(pb[2] - pb[0]) * (unsigned long long)(pb[3] - pb[1]) * spp > (unsigned long long)RT_FEATURE_SAMPLES_MAX)
+      return fail(RT_ERR_INVALID, "rtxh_render_sample_features: the window holds more than RT_FEATURE_SAMPLES_MAX (2^25) samples");
+  }
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_sample_features(s->dev, &cf.cam, &cf.film, &smp, &path, p->flags, stream, features);
 }
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
@@ -1323,7 +1339,7 @@ int rtxh_frame_advance_adaptive(rtxh_frame* f, int32_t n_samples, float threshol
   return rt_frame_advance_adaptive(f->f, n_samples, threshold, floor_y, min_samples, stream, stats);
 }
 int rtxh_frame_read(rtxh_frame* f, int32_t what, float scale, uint32_t flags, void* stream, void* out) {
-  if (!f || !out) return fail(RT_ERR_INVALID, "null argument");
+  if (!f || !out) return fail(RT_ERR_INVALID, "rtxh_frame_read: null argument");
   g_err.clear();
   return rt_frame_read(f->f, what, scale, flags, stream, out);
 }

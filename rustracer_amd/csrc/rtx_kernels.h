@@ -2583,6 +2583,94 @@ static __global__ void __launch_bounds__(256) k_sample_store(FrameParams fp, Pas
   if ((threadIdx.x & 63u) == 0u && scrubbed) atomicAdd(&ps.stats[ST_SCRUBBED], (unsigned long long)scrubbed);
 }
 
+// ================================================================================ first-hit features (rt_render_sample_features, RT_FLAG_FRAME_FEATURES)
+// What the camera ray's first hit tells a denoiser, per camera sample: the ray, the hit record, and of the SurfaceInteraction the production fill routines build at it the
+// depth length(p - o), the shading normal turned towards the ray origin, and the factor PathIntegrator::li multiplies beta by at the camera vertex (path.rs:172-196) - the
+// throughput record k_shade stores for the path's bounce-1 vertex, beta having entered as 1. Written right after bounce 0's shade launches by k_feature_hits
+// (rtx_shade_kernels.h: one lane per entry of bounce 0's queue) and k_feature_albedo (one lane per entry of bounce 1's queue), launched only by a frame or call that asked.
+// Two destinations: the 64-byte records of rt_render_sample_features at [window pixel][sample] of its output (RT_FEATURE_FLOATS floats: o.xyz, d.xyz, prim, b0, b1, depth,
+// normal.xyz, albedo.rgb), or - a feature frame - two float4 planes by path id, (normal.xyz | depth) and (albedo.rgb | 1.0 hit, 0.0 miss), which k_feature_accumulate
+// adds into the frame's plane once per pass.
+struct FeatureOut {
+  float4* samples;         // rt_render_sample_features: [window pixel][sample][4] float4, or NULL
+  int wx0, wy0, ww;        // ... its window: first pixel, width
+  float4* nd; float4* ah;  // a feature frame: [path id] (normal.xyz | depth), (albedo.rgb | hit)
+};
+// where sample `pid` of the pass sits in the output of rt_render_sample_features (k_sample_store's indexing), in float4 units
+RT_DEV size_t feature_sample_at(const FrameParams& fp, const PassState& ps, const FeatureOut& fo, unsigned pid) {
+  unsigned sl, pix; split_path_id(ps, pid, sl, pix);
+  int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+  return (((size_t)(y - fo.wy0) * (size_t)fo.ww + (size_t)(x - fo.wx0)) * ps.spp + ps.s0 + sl) * 4u;
+}
+// One lane per entry of the queue bounce 0's shade launches filled (ps.out / ps.cnt_out, queue 0): the continuing path's throughput is the camera vertex's albedo.
+// A 16-byte record read at consecutive slots of consecutive lanes, one scattered store per continuing path. Runs after k_feature_hits (which wrote zero albedo everywhere).
+template <bool SAMPLES>
+static __global__ void __launch_bounds__(256) k_feature_albedo(FrameParams fp, PassState ps, FeatureOut fo) {
+  QView qv; qv.init(nullptr, ps.cnt_out, ps.shard_cap);
+  const unsigned count = qv.total(), stride = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const unsigned slot = qv.get(i);
+    const float4 b4 = sraw(ps.out.beta)[slot]; const unsigned pid = sraw(ps.out.st)[slot].y;
+    if (SAMPLES) { float* o = (float*)(fo.samples + feature_sample_at(fp, ps, fo, pid)); o[13] = b4.x; o[14] = b4.y; o[15] = b4.z; }
+    else fo.ah[pid] = make_float4(b4.x, b4.y, b4.z, 1.0f);
+  }
+}
+// The plane of a frame begun with RT_FLAG_FRAME_FEATURES, 64 B per owned pixel, zero at rt_frame_begin: sums over the pixel's traced samples, in sample-index order.
+struct alignas(16) PixFeatures { double albedo[3], normal[3], depth; unsigned n, hits; };
+// Once per pass, after the feature kernels: one lane per batch pixel walks the pass's samples in order (the discipline of k_film_accumulate_frame_stats - one lane owns the
+// pixel's entry, no atomics, the sums are those of a sequential float64 loop). A sample that was not traced (outside pixel_bounds or the sample rows, or of a pixel an
+// adaptive step left out: RT_STATE_OUT_OF_BOUNDS in lacc.w) does not count. Unfiltered: a pixel's plane holds its own samples only.
+static __global__ void __launch_bounds__(256) k_feature_accumulate(FrameParams fp, PassState ps, const float4* __restrict__ nd, const float4* __restrict__ ah, PixFeatures* planes) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < ps.n_pixels; pix += stride) {
+    int x, y; unsigned long long pixel_index;
+    owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+    if (y >= fp.sb_y1) continue;
+    PixFeatures* const pf = &planes[fp.chunk_first + pix];
+    double a0 = pf->albedo[0], a1 = pf->albedo[1], a2 = pf->albedo[2], n0 = pf->normal[0], n1 = pf->normal[1], n2 = pf->normal[2], dp = pf->depth;
+    unsigned n = pf->n, hits = pf->hits;
+    for (unsigned sl = 0; sl < ps.n_samples; ++sl) {
+      const unsigned pid = sl * ps.n_pixels + pix;
+      if (__float_as_uint(ps.lacc[pid].w) & RT_STATE_OUT_OF_BOUNDS) continue;
+      const float4 v = nd[pid], a = ah[pid];
+      n += 1u; a0 += (double)a.x; a1 += (double)a.y; a2 += (double)a.z; n0 += (double)v.x; n1 += (double)v.y; n2 += (double)v.z;
+      if (a.w != 0.0f) { hits += 1u; dp += (double)v.w; }
+    }
+    pf->albedo[0] = a0; pf->albedo[1] = a1; pf->albedo[2] = a2; pf->normal[0] = n0; pf->normal[1] = n1; pf->normal[2] = n2; pf->depth = dp; pf->n = n; pf->hits = hits;
+  }
+}
+// RT_FRAME_FEATURES of one pixel: albedo.rgb and normal.xyz = (float)(sum / n), depth = (float)(sum / hits) or 0, coverage = (float)(hits / n); IEEE double divisions.
+// m == NULL (a pixel outside the sample bounds, a row of another rank) or n == 0: zeros.
+RT_DEV void feature_pixel_store(const PixFeatures* m, float* __restrict__ out, unsigned long long i) {
+  float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = lo;
+  if (m != nullptr && m->n != 0u) {
+    const double n = (double)m->n;
+    lo = make_float4((float)(m->albedo[0] / n), (float)(m->albedo[1] / n), (float)(m->albedo[2] / n), (float)(m->normal[0] / n));
+    hi = make_float4((float)(m->normal[1] / n), (float)(m->normal[2] / n), m->hits != 0u ? (float)(m->depth / (double)m->hits) : 0.0f, (float)((double)m->hits / n));
+  }
+  ((float4*)out)[2ull * i] = lo; ((float4*)out)[2ull * i + 1ull] = hi;
+}
+// rt_frame_read(RT_FRAME_FEATURES): one lane per cropped pixel (k_frame_stats_read's walk); rt_multi_frame_read: the pixel's entry from its owner's plane, nothing is added
+// (k_multi_frame_stats_read's walk). planes: one plane (MULTI = false: the frame's own, of rank fp.rank) or the workers' planes by rank.
+template <bool MULTI>
+static __global__ void __launch_bounds__(256) k_frame_features_read(FrameParams fp, const PixFeatures* const* __restrict__ planes, const PixFeatures* __restrict__ own, float* __restrict__ out,
+                                                                    unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  const PixFeatures* m = nullptr;
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel, as in k_frame_resolve
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    const unsigned long long owner = band % (unsigned long long)fp.world;
+    const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+    const unsigned long long k = j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0);
+    if (MULTI) m = &planes[owner][k];
+    else if (owner == (unsigned long long)fp.rank) m = &own[k];
+  }
+  feature_pixel_store(m, out, i);
+}
+
 // ================================================================================ per-triangle / per-light constants (rt_scene_create)
 // What Triangle::intersect computes of the triangle alone (dpdu, dpdv, the geometric normal and - without per-vertex normals or tangents - the whole shading
 // frame and the first axis of Bsdf::new's frame) is evaluated once here, by the functions the per-vertex path uses (tri_geo, tri_frame: IEEE + - * / sqrt

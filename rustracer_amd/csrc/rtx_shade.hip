@@ -102,5 +102,12 @@ void rtx_launch_bsdf_eval(int mode, bool const_tex, unsigned grid, hipStream_t s
   }
 #undef RT_BE
 }
+// k_feature_hits after bounce 0's shade launches of a frame or call that asked for first-hit features (general: the scene holds quadrics or object instances)
+void rtx_launch_feature_hits(bool samples, bool general, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const FeatureOut& fo) {
+#define RT_FH(S, G) hipLaunchKernelGGL((k_feature_hits<S, G>), dim3(grid), dim3(256), 0, stream, d, fp, p, fo)
+  if (samples) { if (general) RT_FH(true, true); else RT_FH(true, false); }
+  else { if (general) RT_FH(false, true); else RT_FH(false, false); }
+#undef RT_FH
+}
 void rtx_shade_set_ewa_lut(const float* lut128) { (void)hipMemcpyToSymbol(HIP_SYMBOL(kEwaLut), lut128, 128 * sizeof(float)); }
 }  // namespace rtx

@@ -235,19 +235,14 @@ struct SmallBsdfT {
 // (primitive_to_world), rc/interaction.rs:156-190. Returns the primitive's index in the scene's arrays (material, flags).
 // OBJ_GENERAL: the object may hold quadrics (DScene::obj_general) - an instantiation of its own, so that scenes of plain objects keep the function they had (instances-10k:
 // one function with both branches cost the generic shade launches 80 B of call frame and 12 %)
-template <bool OBJ_GENERAL>
-RT_DEVN int instance_fill_interaction(const DScene& sc, unsigned hit_id, float ox, float oy, float oz, float dx, float dy, float dz, float b0, float b1, float b2,
-                                      SurfaceInteraction& si) {
-  unsigned lo = 0, hi = sc.n_instances;  // the last instance whose id_base <= hit_id
+// The instance a hit id names (the last whose id_base <= hit_id)
+RT_DEV const DInstance& instance_of_hit(const DScene& sc, unsigned hit_id) {
+  unsigned lo = 0, hi = sc.n_instances;
   while (hi - lo > 1u) { const unsigned mid = (lo + hi) >> 1; if (sc.instances[mid].id_base <= hit_id) lo = mid; else hi = mid; }
-  const DInstance& in = sc.instances[lo];
-  const int gprim = (int)(in.prim_base + (hit_id - in.id_base));
-  const f3 d_obj = xf34_vector(in.w2o, mk3(dx, dy, dz));  // Transform * Ray: the direction as a vector (the origin does not enter a triangle's interaction)
-  TriHit th; th.t = 0.0f; th.b0 = b0; th.b1 = b1; th.b2 = b2;
-  SurfaceInteraction s;
-  if (OBJ_GENERAL && (tri_flags(sc.tri_p, gprim) & RT_FLAG_SPHERE)) {  // a quadric of the object (round 6): Sphere::intersect builds its interaction from the OBJECT-space ray, then SurfaceInteraction::transform
-    (void)sphere_fill_interaction(sc.spheres[prim_sphere_index(sc.tri_p, gprim)], xf34_point(in.w2o, mk3(ox, oy, oz)), d_obj, s);
-  } else tri_fill_interaction_inl(sc, gprim, d_obj, th, s);
+  return sc.instances[lo];
+}
+// SurfaceInteraction::transform(primitive_to_world) of the object-space interaction `s` of instance `in` (rc/interaction.rs:156-190)
+RT_DEV void instance_transform_interaction(const DInstance& in, const SurfaceInteraction& s, int gprim, SurfaceInteraction& si) {
   f3 perr;
   si.hit.p = xf34_point_with_error(in.o2w, s.hit.p, s.hit.p_error, perr); si.hit.p_error = perr;
   si.hit.wo = normalize(xf34_vector(in.o2w, s.hit.wo));
@@ -260,7 +255,35 @@ RT_DEVN int instance_fill_interaction(const DScene& sc, unsigned hit_id, float o
   si.sh_n = face_forward(si.sh_n, si.hit.n);
   si.ssb = normalize(si.sh_dpdu);
   si.prim = gprim;
+}
+template <bool OBJ_GENERAL>
+RT_DEVN int instance_fill_interaction(const DScene& sc, unsigned hit_id, float ox, float oy, float oz, float dx, float dy, float dz, float b0, float b1, float b2,
+                                      SurfaceInteraction& si) {
+  const DInstance& in = instance_of_hit(sc, hit_id);
+  const int gprim = (int)(in.prim_base + (hit_id - in.id_base));
+  const f3 d_obj = xf34_vector(in.w2o, mk3(dx, dy, dz));  // Transform * Ray: the direction as a vector (the origin does not enter a triangle's interaction)
+  TriHit th; th.t = 0.0f; th.b0 = b0; th.b1 = b1; th.b2 = b2;
+  SurfaceInteraction s;
+  if (OBJ_GENERAL && (tri_flags(sc.tri_p, gprim) & RT_FLAG_SPHERE)) {  // a quadric of the object (round 6): Sphere::intersect builds its interaction from the OBJECT-space ray, then SurfaceInteraction::transform
+    (void)sphere_fill_interaction(sc.spheres[prim_sphere_index(sc.tri_p, gprim)], xf34_point(in.w2o, mk3(ox, oy, oz)), d_obj, s);
+  } else tri_fill_interaction_inl(sc, gprim, d_obj, th, s);
+  instance_transform_interaction(in, s, gprim, si);
   return gprim;
+}
+// The same interaction handed to `f` instead of stored: every branch - a triangle of the object, each kind of quadric - builds an interaction of its own, transforms it
+// and returns f's value, all inline. For a kernel that reads a few fields (k_feature_hits): nothing is merged in a struct, so nothing of it lives in memory.
+template <bool OBJ_GENERAL, class F>
+RT_DEV auto instance_interaction_visit(const DScene& sc, unsigned hit_id, f3 o, f3 d, float b0, float b1, float b2, F f) {
+  const DInstance& in = instance_of_hit(sc, hit_id);
+  const int gprim = (int)(in.prim_base + (hit_id - in.id_base));
+  const f3 d_obj = xf34_vector(in.w2o, d);
+  if (OBJ_GENERAL && (tri_flags(sc.tri_p, gprim) & RT_FLAG_SPHERE))
+    return quadric_interaction_visit(sc.spheres[prim_sphere_index(sc.tri_p, gprim)], xf34_point(in.w2o, o), d_obj,
+                                     [&in, gprim, f](const SurfaceInteraction& s) { SurfaceInteraction w; instance_transform_interaction(in, s, gprim, w); return f(w); });
+  TriHit th; th.t = 0.0f; th.b0 = b0; th.b1 = b1; th.b2 = b2;
+  SurfaceInteraction s, w; tri_fill_interaction_inl(sc, gprim, d_obj, th, s);
+  instance_transform_interaction(in, s, gprim, w);
+  return f(w);
 }
 
 // MODE 0: any material / texture / light. MODE 1: every material is matte with constant Kd and
@@ -641,5 +664,50 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
 #endif
 }
 
+
+// ================================================================================ first-hit features (FeatureOut, rtx_kernels.h)
+// One lane per entry of bounce 0's queue, launched right after that bounce's shade launches and before bounce 1's trace overwrites ps.hit: the camera ray k_raygen wrote
+// (ps.in.o / .d), its closest hit (ps.hit) and the SurfaceInteraction the shade kernels built from the two - by the fill routines they call, inline here so that the
+// interaction stays in registers. The entry's path id is its slot where the pass traces every sample (ps.cnt_in == NULL: entry i is slot i is path i, and k_raygen left the
+// state record out), else the state record's. Reads: three or four 16-byte records at consecutive slots of consecutive lanes, then the gathers of the fill routine.
+// The normal is the interaction's shading normal BEFORE compute_scattering_functions (no bump map), negated where dot(n, d) > 0. A miss: prim = -1, every feature zero.
+// GENERAL: the scene holds quadrics or object instances.
+RT_DEV float4 feature_normal_depth(const SurfaceInteraction& si, f3 ray_o, f3 ray_d) {
+  const f3 n = dot(si.sh_n, ray_d) > 0.0f ? -si.sh_n : si.sh_n;
+  return make_float4(n.x, n.y, n.z, len(si.hit.p - ray_o));
+}
+template <bool SAMPLES, bool GENERAL>
+__global__ void __launch_bounds__(256) k_feature_hits(DScene sc, FrameParams fp, PassState ps, FeatureOut fo) {
+  QView qv; if (ps.cnt_in) qv.init(nullptr, ps.cnt_in, ps.shard_cap);
+  const unsigned count = ps.cnt_in ? qv.total() : ps.cap, stride = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const unsigned slot = ps.cnt_in ? qv.get(i) : i;
+    const float4 o4 = sraw(ps.in.o)[slot], d4 = sraw(ps.in.d)[slot], h4 = sraw(ps.hit)[slot];
+    const unsigned pid = ps.cnt_in ? sraw(ps.in.st)[slot].y : slot;
+    const f3 ray_o = mk3(o4.x, o4.y, o4.z), ray_d = mk3(d4.x, d4.y, d4.z);
+    const int prim = __float_as_int(h4.y);
+    float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (normal | depth); each branch takes it from an interaction of its own
+    if (prim >= 0) {
+      TriHit th; th.t = 0.0f; th.b0 = h4.z; th.b1 = h4.w; th.b2 = h4.x;  // the frame loop's hit record is (b2, prim, b0, b1)
+      const auto take = [ray_o, ray_d](const SurfaceInteraction& si) { return feature_normal_depth(si, ray_o, ray_d); };
+      if (GENERAL && sc.n_instances != 0u && (unsigned)prim >= sc.n_top_prims)
+        nd = sc.obj_general ? instance_interaction_visit<true>(sc, (unsigned)prim, ray_o, ray_d, th.b0, th.b1, th.b2, take)
+                            : instance_interaction_visit<false>(sc, (unsigned)prim, ray_o, ray_d, th.b0, th.b1, th.b2, take);
+      else if (GENERAL && (tri_flags(sc.tri_p, prim) & RT_FLAG_SPHERE)) nd = quadric_interaction_visit(sc.spheres[prim_sphere_index(sc.tri_p, prim)], ray_o, ray_d, take);
+      else { SurfaceInteraction si; tri_fill_interaction_inl<true>(sc, prim, ray_d, th, si); nd = feature_normal_depth(si, ray_o, ray_d); }  // (wo is not read)
+    }
+    const bool hit = prim >= 0;
+    if (SAMPLES) {
+      float4* o = fo.samples + feature_sample_at(fp, ps, fo, pid);
+      o[0] = make_float4(ray_o.x, ray_o.y, ray_o.z, ray_d.x);
+      o[1] = make_float4(ray_d.y, ray_d.z, __int_as_float(hit ? prim : -1), hit ? h4.z : 0.0f);
+      o[2] = make_float4(hit ? h4.w : 0.0f, nd.w, nd.x, nd.y);
+      o[3] = make_float4(nd.z, 0.0f, 0.0f, 0.0f);
+    } else {
+      fo.nd[pid] = nd;
+      fo.ah[pid] = make_float4(0.0f, 0.0f, 0.0f, hit ? 1.0f : 0.0f);
+    }
+  }
+}
 
 }  // namespace rtx

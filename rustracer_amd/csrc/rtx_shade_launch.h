@@ -7,6 +7,8 @@ namespace rtx {
 void rtx_launch_shade(int mode, bool general, bool lean, bool bounced, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, bool qlights, int lds);
 // k_shade<1> (constant matte, area lights): ldsrec 0 / 1 / 3
 void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p);
+// k_feature_hits (first-hit features: it builds the interaction with the shade kernels' fill routines, so it lives beside them)
+void rtx_launch_feature_hits(bool samples, bool general, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const FeatureOut& fo);
 void rtx_shade_set_ewa_lut(const float* lut128);  // kEwaLut of that translation unit
 // rt_bsdf_eval: one Bsdf front-end of k_shade - mode 0 GenericBsdf, 3 SingleLambertT, 5 SmallBsdfT<false>, 6 SmallBsdfT<true>; const_tex: the constant-texture form
 // k_shade<1> and the LEAN forms use - on n queries, one lane each. Device pointers; surface NULL = the canonical hit. d.tri_p: record k carries orientation flag k (0, 1).

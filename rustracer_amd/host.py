@@ -15,7 +15,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
-_BUILD = os.path.join(_CSRC, "_build")
+# RTX_LIB_DIR (measurement knob): load librtx_hip.so / librtx_host.so from this directory instead of csrc/_build - another build of the libraries, such as the parent
+# commit's in an A/B run (scripts/feature_cost.py) - as they are: build() then compiles nothing.
+_BUILD = os.environ.get("RTX_LIB_DIR") or os.path.join(_CSRC, "_build")
 HOST_LIB = os.path.join(_BUILD, "librtx_host.so")
 HIP_LIB = os.path.join(_BUILD, "librtx_hip.so")
 
@@ -25,12 +27,15 @@ RT_FLAG_TIME_KERNELS = 4
 RT_FLAG_COUNT_AS_RENDERED = 8
 RT_FLAG_REF_STREAM = 16
 RT_FLAG_FRAME_STATS = 32   # rt_frame_begin: per-pixel luminance moments, adaptive steps
+RT_FLAG_FRAME_FEATURES = 64  # rt_frame_begin: per-pixel sums of the samples' first-hit features (albedo, normal, depth, coverage)
+RT_FEATURE_FLOATS = 16
+RT_FEATURE_SAMPLES_MAX = 1 << 25
 RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
 RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
 RT_SAMPLES_MAX = 1 << 27
 RT_QUERY_BSDF_LAUNCHED = 5  # rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
-RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS = range(4)                                    # rt_frame_read: what
+RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS, RT_FRAME_FEATURES = range(5)                                   # rt_frame_read: what
 RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES, RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS = range(6)   # rt_frame_query: what
 BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
                        two_lobe_wide=RT_BSDF_FRONT_TWO_LOBE_WIDE)
@@ -58,6 +63,8 @@ def source_sha() -> str:
 def build(force: bool = False) -> None:
     """Compile both libraries for gfx950 (hipcc cross-compiles without a GPU). Whether the built libraries are current is decided by CONTENT: the sha256 of the
     sources is stamped beside them (csrc/_build/source.sha) - the libraries are untracked and travel to the GPU box by snapshot, where file times mean nothing."""
+    if os.environ.get("RTX_LIB_DIR"):
+        return
     sha = source_sha()
     stamped = open(STAMP).read().strip() if os.path.exists(STAMP) else None
     if force or stamped != sha or not (os.path.exists(HOST_LIB) and os.path.exists(HIP_LIB)):
@@ -366,18 +373,20 @@ class HostScene:
         _check(lib().rtxh_render(self.h, C.byref(p), C.c_void_p(stream), _p(film), C.byref(stats)), "render")
         return film, stats.as_dict()
 
-    def progressive(self, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+    def progressive(self, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False, features=False):
         """The frame of `render` in steps (rt_frame_*): a ProgressiveFrame whose film can be read after any number of samples per pixel. `table_budget`: bytes the
         frame may spend on sampler tables that stay resident between steps (None: the backend's default; too small: every step rebuilds them - same film).
-        `pixel_stats`: the frame keeps per-pixel luminance moments (RT_FLAG_FRAME_STATS) - `pixel_stats()`, `noise()` and `advance_adaptive()` need it."""
+        `pixel_stats`: the frame keeps per-pixel luminance moments (RT_FLAG_FRAME_STATS) - `pixel_stats()`, `noise()` and `advance_adaptive()` need it.
+        `features`: the frame keeps per-pixel sums of its samples' first-hit features (RT_FLAG_FRAME_FEATURES) - `features()` needs it."""
         return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels,
-                                pixel_stats=pixel_stats)
+                                pixel_stats=pixel_stats, features=features)
 
-    def progressive_multi(self, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+    def progressive_multi(self, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False, features=False):
         """The frame of `progressive` across several GPUs of this process (rt_multi_frame_*): a MultiProgressiveFrame with the methods and properties of
         ProgressiveFrame whose read-outs are the merged frame, formed on devices[0]. One worker per entry of `devices` (an entry may repeat), worker k owns the
         interleaved bands k of len(devices); `table_budget` is per worker. `advance*` return (total stats, [per-device stats])."""
-        return MultiProgressiveFrame(self, devices, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels, pixel_stats=pixel_stats)
+        return MultiProgressiveFrame(self, devices, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels, pixel_stats=pixel_stats,
+                                     features=features)
 
     def render_multi(self, devices, chunks_per_device=1, count_traversal=False, time_kernels=False, count_as_rendered=False, device_out=None):
         """The frame on several GPUs of this process (rt_multi_render): one host thread per entry of `devices`, chunks of tile rows pulled from a
@@ -484,6 +493,31 @@ class HostScene:
         _check(lib().rtxh_render_samples(self.h, C.byref(p), C.c_void_p(stream), _p(rad), _p(pf), C.byref(stats)), "render_samples")
         return rad, pf, stats.as_dict()
 
+    def sample_features(self, device_out=None, stream=0):
+        """The first-hit features of every sample of `samples_window()` (rt_render_sample_features): (h, w, spp, 16) float32 - camera ray o.xyz, d.xyz, then the
+        closest hit's prim (int bits - `out[..., 6].view(np.int32)` -, -1 = miss), b0, b1, then depth = |p - o|, the shading normal (world space, unit, facing the ray origin, no bump
+        map) and the albedo = the camera vertex's throughput factor f |wi.n| / pdf (zero at max_depth 0). A miss: prim -1, everything after the ray zero.
+        `device_out`: a contiguous torch CUDA float32 tensor of that shape that receives the records in HBM."""
+        x0, y0, x1, y1 = self.samples_window()
+        w, h = x1 - x0, y1 - y0
+        p = self.setup()["params"]
+        spp = 1
+        while spp < max(int(p.spp), 1):
+            spp *= 2
+        if w <= 0 or h <= 0 or w * h * spp > RT_FEATURE_SAMPLES_MAX:
+            raise BackendError(f"sample_features: a window of {max(w, 0)} x {max(h, 0)} pixels x {spp} samples is empty or holds more than RT_FEATURE_SAMPLES_MAX samples")
+        L = lib()
+        L.rtxh_render_sample_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if device_out is not None:
+            assert tuple(device_out.shape) == (h, w, spp, RT_FEATURE_FLOATS) and device_out.is_contiguous() and device_out.element_size() == 4
+            p.flags = RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_sample_features(self.h, C.byref(p), C.c_void_p(stream), C.c_void_p(device_out.data_ptr())), "sample_features")
+            return device_out
+        p.flags = 0
+        out = np.zeros((h, w, spp, RT_FEATURE_FLOATS), np.float32)
+        _check(L.rtxh_render_sample_features(self.h, C.byref(p), C.c_void_p(stream), out.ctypes.data_as(C.c_void_p)), "sample_features")
+        return out
+
     def texture_words(self, tex):
         """The word block of texture `tex` as the host holds it (float32), or an empty array for a texture that names none."""
         L = lib()
@@ -531,7 +565,7 @@ class ProgressiveFrame:
     """A frame rendered in steps (HostScene.progressive). `advance(n)` renders the next n samples of every pixel; `film()`, `rgb()` and `display()` read the film as
     it stands. A context manager; it keeps its scene alive and must be closed (or left) before the scene goes."""
 
-    def __init__(self, scene, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+    def __init__(self, scene, rank=0, world_size=1, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False, features=False):
         L = lib()
         L.rtxh_frame_end.argtypes = [C.c_void_p]
         self.scene = scene   # (the frame's device state belongs to the scene's device: the scene must outlive it)
@@ -540,7 +574,8 @@ class ProgressiveFrame:
         cr = st["cropped"]
         self.width, self.height = int(cr[2] - cr[0]), int(cr[3] - cr[1])
         p = st["params"]
-        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0)
+        p.flags = ((RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0) |
+                   (RT_FLAG_FRAME_FEATURES if features else 0))
         self.scale = float(p.film_scale)
         h = C.c_void_p()
         _check(L.rtxh_frame_begin(scene.h, C.byref(p), C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)), C.byref(h)), "frame_begin")
@@ -603,6 +638,12 @@ class ProgressiveFrame:
         a = self._read(RT_FRAME_STATS, 1.0, 3, np.float64, device_out, stream)
         return a[..., 0], a[..., 1], a[..., 2]
 
+    def features(self, device_out=None, stream=0):
+        """(H, W, 8) float32 over the cropped pixel bounds (RT_FRAME_FEATURES; the frame needs features=True): the means over each pixel's own samples of the first-hit
+        albedo rgb and shading normal xyz (not renormalised; misses add zero), the mean depth over the samples that hit, and coverage = hits / samples. Unfiltered;
+        zeros where a pixel has taken no sample. With `device_out`, a torch CUDA tensor (H, W, 8) float32, that tensor."""
+        return self._read(RT_FRAME_FEATURES, 1.0, 8, np.float32, device_out, stream)
+
     def noise(self):
         """(mean, se): each pixel's mean luminance and the standard error of that mean, from `pixel_stats()` with the arithmetic of the adaptive criterion
         (var = max(0, sum_y2 - sum_y * mean) / (n - 1), se = sqrt(var / n)); mean is 0 where n = 0, se is inf where n < 2."""
@@ -642,7 +683,7 @@ class MultiProgressiveFrame(ProgressiveFrame):
     `advance` / `advance_adaptive` return (total stats, [per-device stats]); `device_out` tensors live on devices[0]. Calls on one scene's multi frames and
     `render_multi` come from one thread at a time."""
 
-    def __init__(self, scene, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False):
+    def __init__(self, scene, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False, features=False):
         L = lib()
         L.rtxh_multi_frame_end.argtypes = [C.c_void_p]
         L.rtxh_multi_frame_end.restype = None
@@ -653,7 +694,8 @@ class MultiProgressiveFrame(ProgressiveFrame):
         cr = st["cropped"]
         self.width, self.height = int(cr[2] - cr[0]), int(cr[3] - cr[1])
         p = st["params"]
-        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0)
+        p.flags = ((RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0) |
+                   (RT_FLAG_FRAME_FEATURES if features else 0))
         self.scale = float(p.film_scale)
         dev = np.ascontiguousarray(self.devices, np.int32)
         h = C.c_void_p()

@@ -1,7 +1,7 @@
 """Render a pbrt-v3 scene file on the GPU.
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
-                                  [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...]
+                                  [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -15,7 +15,10 @@ the standard error of a pixel's mean luminance over max(mean, --noise-floor), ev
 reached; prints samples taken / samples of the full frame; --sample-map out.npy gets the per-pixel sample counts (float64 [height, width]). Such an image is no longer
 the one the run without the flag writes.
 --devices 0,1,...: with --preview-every or --adaptive, the frame lives on these GPUs of this process (rt_multi_frame_*; an index may repeat): every step runs on all
-of them at once and the image written is the merged frame; prints the slowest worker's share of each step."""
+of them at once and the image written is the merged frame; prints the slowest worker's share of each step.
+--features out.npy: beside the image, the guide images a denoiser takes (RT_FLAG_FRAME_FEATURES): float32 [height, width, 8] = per pixel the means over its own samples of
+the first-hit albedo rgb and shading normal xyz, the mean depth of the samples that hit, and the coverage hits / samples - unfiltered. The frame is then rendered through
+rt_frame_* (in one step unless --preview-every / --adaptive cut it; on --devices if given): the image is the one the run without the flag writes."""
 import argparse
 import os
 import sys
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--min-samples", type=int, default=8, metavar="M", help="with --adaptive: samples every pixel takes before it may stop")
     ap.add_argument("--noise-floor", type=float, default=1e-3, metavar="F", help="with --adaptive: the error is relative to max(mean luminance, F)")
     ap.add_argument("--sample-map", metavar="OUT.npy", default=None, help="with --adaptive: write the per-pixel sample counts")
+    ap.add_argument("--features", metavar="OUT.npy", default=None, help="write the per-pixel first-hit feature planes (albedo, normal, depth, coverage) beside the image")
     ap.add_argument("--devices", default=None, metavar="0,1,...", help="with --preview-every / --adaptive: render the frame on these GPUs of this process")
     a = ap.parse_args()
     host.build()
@@ -61,10 +65,12 @@ def main():
             write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
 
     devices = [int(v) for v in a.devices.split(",")] if a.devices else None
-    if devices and a.adaptive is None and a.preview_every <= 0:
-        raise SystemExit("--devices goes with --preview-every or --adaptive")
+    if devices and a.adaptive is None and a.preview_every <= 0 and not a.features:
+        raise SystemExit("--devices goes with --preview-every, --adaptive or --features")
 
     def begin(**kw):
+        if a.features:
+            kw["features"] = True
         return s.progressive_multi(devices, **kw) if devices else s.progressive(**kw)
 
     def step_ms(st):
@@ -75,6 +81,13 @@ def main():
         worst = max(p["ms_total"] for p in per)
         print(f"  step {total['ms_total']:.1f} ms on {len(per)} workers; slowest worker {worst:.1f} ms = {worst / max(total['ms_total'], 1e-9):.3f} of it", flush=True)
         return total["ms_total"]
+
+    def save_features(frame):
+        if a.features:
+            import numpy as np
+            f = frame.features()
+            np.save(a.features, f)
+            print(f"{a.features}: {f.shape[1]}x{f.shape[0]} x (albedo rgb, normal xyz, depth, coverage), mean coverage {float(f[..., 7].mean()):.3f}")
 
     if a.adaptive is not None:
         import numpy as np
@@ -96,15 +109,17 @@ def main():
             print(f"{out}: {frame.samples_taken} samples taken / {full} of the full frame ({frame.samples_taken / max(full, 1):.3f}), stopped after {frame.samples_done} of {spp} indices")
             if a.sample_map:
                 np.save(a.sample_map, counts)
-    elif a.preview_every > 0:
+            save_features(frame)
+    elif a.preview_every > 0 or a.features:
         stats = {"ms_total": 0.0}
         with begin() as frame:
             spp = frame.spp
             while frame.samples_done < spp:
-                stats["ms_total"] += step_ms(frame.advance(a.preview_every))
+                stats["ms_total"] += step_ms(frame.advance(a.preview_every if a.preview_every > 0 else spp))
                 film = frame.film()
                 write(film)
                 print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
+            save_features(frame)
     else:
         film, stats = s.render()
         write(film)
