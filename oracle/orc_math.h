@@ -75,6 +75,14 @@ inline int32_t f2i_sat(float f) {
   if (f <= -2147483648.0f) return INT32_MIN;
   return (int32_t)f;
 }
+// Rust `f32 as isize` (64-bit), saturating: MIPMap's texel indices (mipmap.rs:289-290, 336-339)
+inline int64_t f2l_sat(float f) {
+  if (f != f) return 0;
+  if (f >= 9223372036854775808.0f) return INT64_MAX;
+  if (f <= -9223372036854775808.0f) return INT64_MIN;
+  return (int64_t)f;
+}
+inline int64_t wrapping_inc(int64_t v) { return (int64_t)((uint64_t)v + 1u); }  // `v + 1` as a release build computes it: the reference's `t0..(t1 + 1)` is empty at the 64-bit limit
 // Rust `f32 as usize` (64-bit): saturating at 0 below.
 inline uint64_t f2u_sat(float f) {
   if (f != f || f <= 0.0f) return 0;

@@ -114,10 +114,11 @@ struct MipMap {
     level = clamp_t(level, 0, levels() - 1);
     float s = st.x * (float)pyramid[level].u - 0.5f;
     float t = st.y * (float)pyramid[level].v - 0.5f;
-    long s0 = (long)f2i_sat(floorf(s)), t0 = (long)f2i_sat(floorf(t));
+    long s0 = f2l_sat(floorf(s)), t0 = f2l_sat(floorf(t));  // `as isize`: 64-bit
     float ds = s - (float)s0, dt = t - (float)t0;
-    return texel(level, s0, t0) * (1.0f - ds) * (1.0f - dt) + texel(level, s0, t0 + 1) * (1.0f - ds) * dt +
-           texel(level, s0 + 1, t0) * ds * (1.0f - dt) + texel(level, s0 + 1, t0 + 1) * ds * dt;
+    long s1 = wrapping_inc(s0), t1 = wrapping_inc(t0);
+    return texel(level, s0, t0) * (1.0f - ds) * (1.0f - dt) + texel(level, s0, t1) * (1.0f - ds) * dt +
+           texel(level, s1, t0) * ds * (1.0f - dt) + texel(level, s1, t1) * ds * dt;
   }
   static RGB lerp_rgb(float t, RGB a, RGB b) { return a * (1.0f - t) + b * t; }  // lib.rs:107-117
   RGB lookup(P2 st, float width) const {  // :227-245
@@ -141,12 +142,12 @@ struct MipMap {
     float det = -B * B + 4.0f * A * C;
     float invDet = 1.0f / det;
     float uSqrt = sqrtf(det * C), vSqrt = sqrtf(A * det);
-    long s0 = f2i_sat(ceilf(st.x - 2.0f * invDet * uSqrt)), s1 = f2i_sat(floorf(st.x + 2.0f * invDet * uSqrt));
-    long t0 = f2i_sat(ceilf(st.y - 2.0f * invDet * vSqrt)), t1 = f2i_sat(floorf(st.y + 2.0f * invDet * vSqrt));
+    long s0 = f2l_sat(ceilf(st.x - 2.0f * invDet * uSqrt)), s1 = f2l_sat(floorf(st.x + 2.0f * invDet * uSqrt));
+    long t0 = f2l_sat(ceilf(st.y - 2.0f * invDet * vSqrt)), t1 = f2l_sat(floorf(st.y + 2.0f * invDet * vSqrt));
     RGB sum = rgb(0, 0, 0); float sumWts = 0.0f;
-    for (long it = t0; it < t1 + 1; ++it) {
+    for (long it = t0, te = wrapping_inc(t1), se = wrapping_inc(s1); it < te; ++it) {
       float tt = (float)it - st.y;
-      for (long is = s0; is < s1 + 1; ++is) {
+      for (long is = s0; is < se; ++is) {
         float ss = (float)is - st.x;
         float r2 = A * ss * ss + B * ss * tt + C * tt * tt;
         if (r2 < 1.0f) {

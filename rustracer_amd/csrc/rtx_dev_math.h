@@ -50,6 +50,14 @@ RT_DEV int f2i_sat(float f) {
   if (f <= -2147483648.0f) return -2147483647 - 1;
   return (int)f;
 }
+// Rust `as isize` (64-bit, saturating, NaN -> 0): MIPMap's texel indices (rc/mipmap.rs:289-290, 336-339)
+RT_DEV long f2l_sat(float f) {
+  if (f != f) return 0;
+  if (f >= 9223372036854775808.0f) return 0x7fffffffffffffffL;
+  if (f <= -9223372036854775808.0f) return -0x7fffffffffffffffL - 1;
+  return (long)f;
+}
+RT_DEV long wrapping_inc(long v) { return (long)((unsigned long)v + 1ul); }  // `v + 1` as a release build computes it: the reference's `t0..(t1 + 1)` is empty at the 64-bit limit
 RT_DEV uint32_t f2u_sat(float f) {
   if (f != f || f <= 0.0f) return 0u;
   if (f >= 4294967296.0f) return 0xffffffffu;

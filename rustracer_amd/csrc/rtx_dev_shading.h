@@ -26,10 +26,11 @@ RT_DEV rgb3 mip_triangle(const DImage& im, int level, f2 st) {  // :285-308
   level = clampi(level, 0, im.n_levels - 1);
   float s = st.x * (float)im.w[level] - 0.5f;
   float t = st.y * (float)im.h[level] - 0.5f;
-  long s0 = f2i_sat(floorf(s)), t0 = f2i_sat(floorf(t));
+  long s0 = f2l_sat(floorf(s)), t0 = f2l_sat(floorf(t));  // `as isize`: 64-bit
   float ds = s - (float)s0, dt = t - (float)t0;
-  return mip_texel(im, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(im, level, s0, t0 + 1) * (1.0f - ds) * dt +
-         mip_texel(im, level, s0 + 1, t0) * ds * (1.0f - dt) + mip_texel(im, level, s0 + 1, t0 + 1) * ds * dt;
+  long s1 = wrapping_inc(s0), t1 = wrapping_inc(t0);
+  return mip_texel(im, level, s0, t0) * (1.0f - ds) * (1.0f - dt) + mip_texel(im, level, s0, t1) * (1.0f - ds) * dt +
+         mip_texel(im, level, s1, t0) * ds * (1.0f - dt) + mip_texel(im, level, s1, t1) * ds * dt;
 }
 RT_DEV rgb3 lerp_rgb(float t, rgb3 a, rgb3 b) { return a * (1.0f - t) + b * t; }
 RT_DEV rgb3 mip_lookup(const DImage& im, f2 st, float width) {  // :227-245
@@ -56,12 +57,13 @@ RT_DEV rgb3 mip_ewa(const DImage& im, int level, f2 st, f2 dst0, f2 dst1) {  // 
   float det = -B * B + 4.0f * A * C;
   float invDet = 1.0f / det;
   float uSqrt = sqrtf(det * C), vSqrt = sqrtf(A * det);
-  long s0 = f2i_sat(ceilf(st.x - 2.0f * invDet * uSqrt)), s1 = f2i_sat(floorf(st.x + 2.0f * invDet * uSqrt));
-  long t0 = f2i_sat(ceilf(st.y - 2.0f * invDet * vSqrt)), t1 = f2i_sat(floorf(st.y + 2.0f * invDet * vSqrt));
+  long s0 = f2l_sat(ceilf(st.x - 2.0f * invDet * uSqrt)), s1 = f2l_sat(floorf(st.x + 2.0f * invDet * uSqrt));
+  long t0 = f2l_sat(ceilf(st.y - 2.0f * invDet * vSqrt)), t1 = f2l_sat(floorf(st.y + 2.0f * invDet * vSqrt));
   rgb3 sum = mkc(0, 0, 0); float sumWts = 0.0f;
-  for (long it = t0; it < t1 + 1; ++it) {
+  const long se = wrapping_inc(s1), te = wrapping_inc(t1);
+  for (long it = t0; it < te; ++it) {
     float tt = (float)it - st.y;
-    for (long is = s0; is < s1 + 1; ++is) {
+    for (long is = s0; is < se; ++is) {
       float ss = (float)is - st.x;
       float r2 = A * ss * ss + B * ss * tt + C * tt * tt;
       if (r2 < 1.0f) {

@@ -53,6 +53,13 @@ inline int f2i(float f) {                                                       
   if (f <= -2147483648.0f) return -2147483647 - 1;
   return (int)f;
 }
+inline long f2l(float f) {                                                                          // Rust `as isize` (64-bit): MIPMap's texel indices
+  if (f != f) return 0;
+  if (f >= 9223372036854775808.0f) return 0x7fffffffffffffffL;
+  if (f <= -9223372036854775808.0f) return -0x7fffffffffffffffL - 1;
+  return (long)f;
+}
+inline long wrapping_inc(long v) { return (long)((unsigned long)v + 1ul); }  // `v + 1` as a release build computes it
 
 // ------------------------------------------------------------------ 4x4 matrices (rc/geometry/matrix.rs, rc/transform.rs)
 struct Mat { float a[4][4]; };
@@ -162,10 +169,10 @@ void mip_triangle(const MipLevels& m, int level, float sx, float sy, float out[3
   int nl = (int)m.w.size();
   level = level < 0 ? 0 : (level > nl - 1 ? nl - 1 : level);
   float s = sx * (float)m.w[level] - 0.5f, t = sy * (float)m.h[level] - 0.5f;
-  long s0 = f2i(std::floor(s)), t0 = f2i(std::floor(t));
+  long s0 = f2l(std::floor(s)), t0 = f2l(std::floor(t)), s1 = wrapping_inc(s0), t1 = wrapping_inc(t0);  // `as isize`: 64-bit
   float ds = s - (float)s0, dt = t - (float)t0;
   float a[3], b[3], c[3], d[3];
-  mip_texel(m, level, s0, t0, a); mip_texel(m, level, s0, t0 + 1, b); mip_texel(m, level, s0 + 1, t0, c); mip_texel(m, level, s0 + 1, t0 + 1, d);
+  mip_texel(m, level, s0, t0, a); mip_texel(m, level, s0, t1, b); mip_texel(m, level, s1, t0, c); mip_texel(m, level, s1, t1, d);
   for (int k = 0; k < 3; ++k) out[k] = a[k] * (1.0f - ds) * (1.0f - dt) + b[k] * (1.0f - ds) * dt + c[k] * ds * (1.0f - dt) + d[k] * ds * dt;
 }
 void mip_lookup(const MipLevels& m, float sx, float sy, float width, float out[3]) {  // mipmap.rs:227-245

@@ -59,12 +59,12 @@ struct IngestPyramid { const float* texels; int n_levels; int w[RT_MAX_MIP_LEVEL
 RT_DEV void ingest_triangle(const IngestPyramid& m, int level, float sx, float sy, float out[3]) {  // MIPMap::triangle, mipmap.rs:285-308
   level = level < 0 ? 0 : (level > m.n_levels - 1 ? m.n_levels - 1 : level);
   const float s = sx * (float)m.w[level] - 0.5f, t = sy * (float)m.h[level] - 0.5f;
-  const long s0 = (long)f2i_sat(floorf(s)), t0 = (long)f2i_sat(floorf(t));
+  const long s0 = f2l_sat(floorf(s)), t0 = f2l_sat(floorf(t)), s1 = wrapping_inc(s0), t1 = wrapping_inc(t0);  // `as isize`: 64-bit
   const float ds = s - (float)s0, dt = t - (float)t0;
   const float* lvl = m.texels + 3 * m.off[level];
   float a[3], b[3], c[3], d[3];
-  ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0, t0, a); ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0, t0 + 1, b);
-  ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0 + 1, t0, c); ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0 + 1, t0 + 1, d);
+  ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0, t0, a); ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s0, t1, b);
+  ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s1, t0, c); ingest_texel(lvl, m.w[level], m.h[level], m.wrap, s1, t1, d);
   for (int k = 0; k < 3; ++k) out[k] = a[k] * (1.0f - ds) * (1.0f - dt) + b[k] * (1.0f - ds) * dt + c[k] * ds * (1.0f - dt) + d[k] * ds * dt;
 }
 
