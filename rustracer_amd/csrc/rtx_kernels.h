@@ -126,6 +126,9 @@ struct PassState {
 #define RT_FRESH_RECORDS_LDS 2  // ... a frame of k_shade<1, .., LDSREC = 1> (S1): the state record only. One box, interleaved, three rounds (profiles/r06_ab_fresh_records.txt):
 #endif                          // S1 0 / 1 / 2 / 3 = 2003 / 1978 / 2020 / 1977 Msamples/s (a constant throughput costs that kernel 12 ms of shade); the other forms
                                 // 0 / 1 / 2 / 3: S2 1509 / 1533 / 1523 / 1556, S3 1816 / 1825 / 1828 / 1842, S4 447.0 / 445.3 / 448.2 / 446.6
+                                // Round 8: where such a frame's closest hits come from k_trace, bounce 0 of a fully traced pass is shaded by k_shade_split<1>, which has the
+                                // constant throughput and state at compile time (no select) - rt_render then leaves BOTH records out (fresh_planes = 3) whatever this says;
+                                // it still holds for k_shade<1, .., 1> itself (RTX_SHADE_SPLIT=0, counting frames of scenes with general primitives).
 #define RT_FRESH_BETA(ps) (((ps).fresh & 1) != 0)
 #define RT_FRESH_ST(ps) (((ps).fresh & 2) != 0)
   int shadow_sets;    // k_shade: a shadow segment whose voxel / light pair is EMPTY (ld_rows8 r0.w / r1.w, rtx_shadow_sets.h) is answered without a walk (off on frames that count node visits)
@@ -986,6 +989,9 @@ struct TraceIO {
   // the launch's rays are the entries of a sharded queue whose records sit at their slots (the path rays of a bounce, PassState::in): entry i -> slot by the
   // shard counts alone, `queue` is then only a non-NULL marker
   int queue_is_slots;
+  // closest hit, k_trace only: bit (i & 63) of hit_mask[i >> 6] = entry i of the launch's queue found a hit (one store per wave; NULL: not written). A wave holds 64
+  // consecutive, 64-aligned entries, here and in the shade scan that reads the words (k_shade_split<1> / k_shade_split<2>) instead of the hit records.
+  unsigned long long* hit_mask;
 };
 template <class AddPtr>
 RT_DEV void trace_write_any(float4* __restrict__ lacc, size_t ls, const AddPtr direct_add, size_t as, unsigned* __restrict__ occluded, size_t os,
@@ -1095,8 +1101,14 @@ __global__ void __launch_bounds__(BLOCK, MID ? 4 : ((GENERAL == 0 && !COUNT) ? (
     n_rays += 1;
     if (ANY) trace_write_any(lacc, ls, direct_add, as, occluded, os, pid, d4.w, found);
     else hits[pid * hs] = make_float4(hit_b2 ? h.b2 : (found ? h.t : kInf), __int_as_float(found ? prim : -1), h.b0, h.b1);
+    return found;
   };
-  for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < count; i += stride) trace_one(queue ? qv.get(i) : i);
+  for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < count; i += stride) {
+    const bool found = trace_one(queue ? qv.get(i) : i);
+    if constexpr (!ANY) {  // TraceIO::hit_mask: the wave's 64 entries (lanes past the queue's end are not here: their bits are zero), stored by its first lane
+      if (io.hit_mask != nullptr) { const unsigned long long m = __ballot(found); if ((threadIdx.x & 63u) == 0u) io.hit_mask[i >> 6] = m; }
+    } else (void)found;
+  }
   if (stats) {
     // one atomic per wave and counter
     for (int off = 32; off > 0; off >>= 1) { n_rays += __shfl_down(n_rays, off); if (COUNT) { n_nodes += __shfl_down(n_nodes, off); n_tris += __shfl_down(n_tris, off); } }

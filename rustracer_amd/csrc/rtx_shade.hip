@@ -52,6 +52,10 @@ void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream
   else if (ldsrec == 3) hipLaunchKernelGGL((k_shade<1, false, false, false, false, 3>), dim3(grid), dim3(block), 0, stream, d, fp, p);
   else hipLaunchKernelGGL(k_shade<1>, dim3(grid), dim3(block), 0, stream, d, fp, p);
 }
+void rtx_launch_shade_split(bool camera, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const unsigned long long* hit_mask) {
+  if (camera) hipLaunchKernelGGL(k_shade_split<RT_SPLIT_CAMERA>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
+  else hipLaunchKernelGGL(k_shade_split<RT_SPLIT_BOUNCED>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
+}
 // ---- rt_bsdf_eval (rtx_hip.h): the front-end structs above on hand-made surface records. One lane per query builds the Bsdf of the material at its record the way
 // shade_vertex does (the generic front-end takes the scene record in device memory, the others the kernel argument) and evaluates f, pdf and sample_f over all lobes.
 RT_DEV int front_end_lobes(const GenericBsdf& b) { return b.b.n; }

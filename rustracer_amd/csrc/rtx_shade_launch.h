@@ -7,6 +7,9 @@ namespace rtx {
 void rtx_launch_shade(int mode, bool general, bool lean, bool bounced, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, bool qlights, int lds);
 // k_shade<1> (constant matte, area lights): ldsrec 0 / 1 / 3
 void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p);
+// the frames of k_shade<1, .., LDSREC = 1> whose closest hits come from k_trace: k_shade_split<1> (bounce 0 of a pass that traces every sample) or k_shade_split<2>
+// (bounces >= 1), workgroups of 256 lanes; hit_mask: the words that bounce's k_trace launch wrote (TraceIO::hit_mask)
+void rtx_launch_shade_split(bool camera, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const unsigned long long* hit_mask);
 // k_feature_hits (first-hit features: it builds the interaction with the shade kernels' fill routines, so it lives beside them)
 void rtx_launch_feature_hits(bool samples, bool general, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const FeatureOut& fo);
 void rtx_shade_set_ewa_lut(const float* lut128);  // kEwaLut of that translation unit
