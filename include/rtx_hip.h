@@ -434,6 +434,30 @@ int rt_render_samples(rt_scene* scene, const rt_camera* camera, const rt_film_de
 int rt_render_sample_features(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
                               uint32_t flags, void* stream, float* features);
 
+/* Path-traced radiance along caller-supplied rays: PathIntegrator::li(ray, ..) on a batch, with rt_render's kernels, queues and sampler - for the cameras this backend
+ * has no struct for (orthographic, environment, fisheye, a realistic lens), light probes, lightmap texels, sensor positions.
+ *   rays      [height][width][n_samples][8] floats: o.xyz, t_max, d.xyz, unused - rt_trace_closest's record. d is used as given (not normalised), as Ray::d is.
+ *   radiance  [height][width][n_samples][4] floats: L rgb exactly as PathIntegrator::li returns it (rt_render_samples' record), and a fourth float: 0.0 a normal sample,
+ *             1.0 where renderer.rs:115-126 would scrub it, 2.0 a ray that was not traced.
+ * The batch is a VIRTUAL FILM whose sample bounds are [0, width) x [0, height): ray (x, y, sl) is sample s = sample0 + sl of the pixel with pixel_index = y * width + x. It
+ * draws from that pixel's sampler tables at index s and from the keyed RNG stream pixel_index * spp + s + 2^32, the dimension counters starting where get_camera_sample
+ * leaves them (cur_1d = 1, cur_2d = 2: what a camera would have consumed is unused). sampler->spp, rounded up to a power of two, sizes the tables, and
+ * [sample0, sample0 + n_samples) must lie inside [0, spp): a job of more than RT_RAYS_MAX rays is cut by sample range, and the calls together are the one call, bit for bit.
+ * So the camera rays rt_render_sample_features reports of a film with a box filter of radius 0.5, fed back in with t_max = inf, give the radiance rt_render_samples reports.
+ * The rays carry no differentials (Ray { differential: None }): every derivative of the first vertex is zero, as at every later vertex (interaction.rs:245-314), and image
+ * maps are looked up at zero filter width.
+ * A ray whose t_max is not > 0 (zero, negative, NaN) is SKIPPED: radiance (0, 0, 0, 2.0), nothing consumed, not counted in stats->camera_rays. One scan of the rays on the
+ * device decides the route of the call: none skipped - the route of a frame whose pixel_bounds crop nothing, else that of a cropped one. Same radiance either way.
+ * path: max_depth, rr_threshold and light_strategy as in rt_render (the light distribution is built by the first call that needs it); pixel_bounds is ignored.
+ * flags: RT_FLAG_FILM_ON_DEVICE - rays AND radiance are device pointers; RT_FLAG_COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED as in rt_render_samples (ms_raygen: the
+ * scan and the kernel that reads the rays). Refused with RT_ERR_INVALID before any device work: a NULL scene, rays, sampler, path or radiance; width, height or
+ * n_samples <= 0; sample0 < 0 or sample0 + n_samples > the rounded spp; width * height * n_samples > RT_RAYS_MAX; spp > 16384; dimensions outside [2, 8];
+ * RT_FLAG_REF_STREAM. Single device. */
+#define RT_RAYS_MAX 134217728   /* 2^27 rays per call: 4 GiB of rays, 2 GiB of radiance */
+int rt_render_rays(rt_scene* scene, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples,
+                   const rt_sampler_desc* sampler, const rt_path_desc* path, uint32_t flags, void* stream,
+                   float* radiance, rt_stats* stats /* may be NULL */);
+
 /* Progressive frames: the frame of rt_render rendered in steps, with the film readable between them. The reference's CLI offers "display image as it is
  * rendered" (-p / --display); it has no checkpoint or resume. The pixel-keyed sampler makes sample s of pixel p the same whichever call renders it, so a frame
  * can stop after any number of samples per pixel and go on later.
@@ -549,7 +573,9 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
        RT_QUERY_SHADOW_PAIRS = 3 /* shadow sets (rt_shadow_sets): voxel / light pairs of the voxels a surface reaches; 0 where the scene has none */,
        RT_QUERY_SHADOW_EMPTY = 4 /* ... of them EMPTY: no shadow segment of the pair can be occluded */,
        RT_QUERY_BSDF_LAUNCHED = 5 /* the kernel the scene's last rt_bsdf_eval launched: 1 + 2 * mode + const_tex (mode 0 generic, 3 Lambert, 5 two-lobe, 6 two-lobe wide;
-                                     const_tex 1: its constant-texture form), 0 before the first call */ };
+                                     const_tex 1: its constant-texture form), 0 before the first call */,
+       RT_QUERY_NEEDS_DIFFERENTIALS = 6 /* 1 if some texture or bump map of the scene reads ray differentials (image maps, closed-form checkerboards, fbm): the shade kernels
+                                           then regenerate the camera ray's at bounce 0 - in the frames of a camera, never in rt_render_rays' */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

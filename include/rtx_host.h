@@ -148,6 +148,12 @@ int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream
 /* The first-hit features of the same window's samples (rt_render_sample_features in rtx_hip.h): features: pixels x spp x RT_FEATURE_FLOATS floats; a host pointer, or a
  * device pointer with RT_FLAG_FILM_ON_DEVICE. Window and set-up as for rtxh_render_samples; more than RT_FEATURE_SAMPLES_MAX samples are refused. */
 int rtxh_render_sample_features(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* features);
+/* Path-traced radiance along the caller's rays (rt_render_rays in rtx_hip.h): rays height x width x n_samples x 8 floats (o.xyz, t_max, d.xyz, unused), radiance
+ * height x width x n_samples x 4; host pointers, or both device pointers with RT_FLAG_FILM_ON_DEVICE. Of the parameters only the sampler (spp, sampler_dims), the
+ * integrator (max_depth, rr_threshold, light_strategy) and the flags are read: no camera or film is set up. Sizes rt_render_rays refuses are refused before the scene
+ * is uploaded for it. */
+int rtxh_render_rays(rtxh_scene*, const rtxh_render_params*, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, void* hip_stream,
+                     float* radiance, rt_stats* stats);
 /* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
  * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
  * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */

@@ -19,6 +19,7 @@
 #include "rtx_kernels.h"
 #include "rtx_shade_launch.h"
 #include "rtx_ref_launch.h"
+#include "rtx_rays_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -99,6 +100,7 @@ struct rt_scene {
   DevBuf ws[32];
   DevBuf film_acc, own_acc, film_out, counters, stats, filter_table, ref_samples, ref_stack;
   DevBuf samples_rad, samples_pf;  // rt_render_samples with host outputs: [window pixel][sample] radiance (float4) and film position (float2)
+  DevBuf rays_in, rays_skipped;    // rt_render_rays: the caller's host rays in device memory ([pixel][sample] 32 B), and the word k_rays_scan leaves (1: some ray is skipped)
   DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
   DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
   DevBuf bsdf_self, bsdf_tris;     // rt_bsdf_eval: a copy of `d` whose tri_p names two primitive records that carry nothing but the orientation flag (0, 1) - what a bump map reads of si.prim
@@ -368,6 +370,7 @@ extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (what == RT_QUERY_SHADOW_PAIRS) return s->shadow_sets ? (int)s->shadow.pairs : 0;
   if (what == RT_QUERY_SHADOW_EMPTY) return s->shadow_sets ? (int)s->shadow.empty : 0;
   if (what == RT_QUERY_BSDF_LAUNCHED) return s->bsdf_launched < 0 ? 0 : s->bsdf_launched + 1;
+  if (what == RT_QUERY_NEEDS_DIFFERENTIALS) return s->d.needs_differentials ? 1 : 0;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -1040,16 +1043,24 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // bounce 0's shade launches. Either launches k_feature_hits and k_feature_albedo right after those launches, before bounce 1's trace overwrites the hit records, and casts
 // the continuation rays of a max_depth == 1 frame (nothing reads them: PassState::skip_dead_tail is cleared for bounce 0, whose throughput record is the albedo). No other
 // frame launches either kernel.
+// Caller-supplied rays: ray_src != NULL - the frame of rt_render_rays, a samples frame (samples_rad is its radiance, [pixel][sample of the call]) over the virtual film
+// `film` whose bounce 0 comes from k_raygen_rays instead of k_raygen: samples [sample0, sample0 + n_samples) of every pixel, no camera, and no differentials - every
+// launch gets the scene record with needs_differentials = 0. One scan of the rays (k_rays_scan) before the first pass decides the route of all passes: no ray skipped -
+// all_in_bounds, as a frame whose pixel_bounds crop nothing; else the sharded bounce-0 queue of a cropped one. Everything after ray generation is the samples frame's.
+struct RaySource { const float* rays; unsigned sample0, n_samples; };
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
-                        rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr) {
+                        rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr,
+                        const RaySource* ray_src = nullptr) {
+  const bool rays = ray_src != nullptr;
   const bool samples = samples_rad != nullptr;
   const bool fsamples = samples_feat != nullptr, features = fsamples || (fr && fr->features);
   // the window of rt_render_samples: pixel_bounds inside the sample bounds, and its size - checked before any device work
   const int wx0 = std::max(path->pixel_bounds[0], film->sample_bounds[0]), wy0 = std::max(path->pixel_bounds[1], film->sample_bounds[1]);
   const int wx1 = std::min(path->pixel_bounds[2], film->sample_bounds[2]), wy1 = std::min(path->pixel_bounds[3], film->sample_bounds[3]);
   unsigned long long n_window_samples = 0;
-  if (samples) {
+  if (rays) n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * ray_src->n_samples;  // (rt_render_rays checked the size: the call's samples, not spp)
+  else if (samples) {
     if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_samples: the reference-stream frame has no per-sample output");
     if (wx1 <= wx0 || wy1 <= wy0) return fail(RT_ERR_INVALID, "rt_render_samples: pixel_bounds and the film's sample bounds share no pixel");
     const unsigned long long spp_r = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
@@ -1139,8 +1150,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     return RT_OK;
   }
   // pixel_bounds (path.rs:30) that do not crop the sample bounds: every generated sample is traced
-  const bool all_in_bounds = !active_mask && path->pixel_bounds[0] <= film->sample_bounds[0] && path->pixel_bounds[2] >= film->sample_bounds[2] &&
-                             path->pixel_bounds[1] <= film->sample_bounds[1] && path->pixel_bounds[3] >= film->sample_bounds[3];
+  bool all_in_bounds = !active_mask && path->pixel_bounds[0] <= film->sample_bounds[0] && path->pixel_bounds[2] >= film->sample_bounds[2] &&
+                       path->pixel_bounds[1] <= film->sample_bounds[1] && path->pixel_bounds[3] >= film->sample_bounds[3];  // (a ray frame: cleared below if k_rays_scan finds a skipped ray)
   // batch / pass sizing. A batch is a range of owned pixels whose sampler tables (2*dims u16 per sample) are built
   // at once; it is rendered in passes of n_samples consecutive samples of all its pixels, ~2^29 paths (211 GB of path state) per pass.
   // measurement knobs; 2^23 -> 2^26 paths per pass: -9 % (S1), -32 % (S2); 2^26 -> 2^28 with 2^19-pixel batches: -1 % (S1), -7 % (S2), -1 % (S3):
@@ -1175,7 +1186,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
 
   const bool resident = fr && fr->resident;                   // the sampler tables of every batch live in the frame ...
   const bool build_tables = !(resident && fr->tables_built);  // ... and are built by its first step only
-  const unsigned s_begin = fr ? fr->done : 0u, s_end = fr ? step_end : spp;  // the samples this call renders
+  const unsigned s_begin = fr ? fr->done : (rays ? ray_src->sample0 : 0u), s_end = fr ? step_end : (rays ? ray_src->sample0 + ray_src->n_samples : spp);  // the samples this call renders
   unsigned long long batch_pixels = 0, chunk_pixels = 0, cap = 0, lead_pixels = 0; unsigned pass_samples = 0, shard_cap = 0; bool multi_batch = false; size_t n_slots = 0;
   static const char* lead_env = getenv("RTX_LEAD_BATCH");  // measurement knob (round 4), see lead_pixels below: 1 always, 0 never, unset: at 1024 spp
   const bool lead_on = lead_env ? lead_env[0] == '1' : spp == 1024u;
@@ -1213,7 +1224,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         {&s->ws[B_SH], cap * 48}, {&s->ws[B_MI], cap * 100}, {&s->ws[B_OCCSH], cap}, {&s->ws[B_OCCMI], cap}, {&s->ws[B_HITMASK], shade_split ? (size_t)((cap + 63) / 64) * 8 : 16},
         {&s->ws[B_QSH], szq}, {&s->ws[B_QMI], szq}, {&s->ws[B_QMA], has_infinite ? szq : 16},
         {&s->counters, counter_words * 4}, {&s->stats, (size_t)ST_COUNT * 8}};
-    if (!fr && !fsamples) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
+    if (!fr && !fsamples && !rays) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
     if (!resident) { want.push_back({&s->scrambles[0], (size_t)chunk_pixels * 3 * dims * 4}); want.push_back({&s->perms[0], (size_t)(chunk_pixels * table_bytes_per_pixel)}); }
     if (build_tables) want.push_back({&s->sampler_plan.partners, (size_t)(chunk_pixels * table_bytes_per_pixel)});
     if (use_bins) { want.push_back({&s->bin_words, (size_t)(fp.max_depth + 1) * bin_stride * 4}); want.push_back({&s->bin_sorted, (size_t)cap * 4}); want.push_back({&s->bin_at, (size_t)cap * 2}); }
@@ -1223,7 +1234,9 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       if (fsamples) want.push_back({&s->samples_feat, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4});
       else if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
       else { want.push_back({&s->samples_rad, (size_t)n_window_samples * 16}); if (samples_pf) want.push_back({&s->samples_pf, (size_t)n_window_samples * 8}); }
+      if (rays) want.push_back({&s->rays_in, (size_t)n_window_samples * 32});
     }
+    if (rays) want.push_back({&s->rays_skipped, 16});
     size_t grow = 0;  // bytes the buffers have to grow by (a buffer that is too small is freed and allocated anew)
     for (const Want& w : want) if (!w.buf->p || w.buf->bytes < w.bytes) grow += w.bytes;
     size_t held = 0;
@@ -1253,6 +1266,26 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)cw * ch * 16, stream));
   }
   HIP_TRY(hipMemsetAsync(s->stats.p, 0, ST_COUNT * 8, stream));
+  // A ray frame: the caller's rays in device memory, and the one scan that picks the route of its passes (timed with ray generation). Its launches take the scene
+  // record with needs_differentials cleared (DScene travels by value): the rays are Ray { differential: None }, every derivative stays zero (interaction.rs:245-314).
+  const float4* d_rays = nullptr;
+  DScene dsc_rays;
+  if (rays) {
+    dsc_rays = s->d; dsc_rays.needs_differentials = 0;
+    if (flags & RT_FLAG_FILM_ON_DEVICE) d_rays = (const float4*)ray_src->rays;
+    else { HIP_TRY(hipMemcpyAsync(s->rays_in.p, ray_src->rays, (size_t)n_window_samples * 32, hipMemcpyHostToDevice, stream)); d_rays = s->rays_in.as<float4>(); }
+    HIP_TRY(hipMemsetAsync(s->rays_skipped.p, 0, 4, stream));
+    tm.begin(&stats.ms_raygen);
+    rtx_launch_rays_scan((unsigned)std::min<unsigned long long>((n_window_samples + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, (const float*)d_rays, n_window_samples,
+                         s->rays_skipped.as<unsigned>());
+    tm.end();
+    HIP_TRY(hipGetLastError());
+    unsigned any_skipped = 0;
+    HIP_TRY(hipMemcpyAsync(&any_skipped, s->rays_skipped.p, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (any_skipped) all_in_bounds = false;
+  }
+  const DScene& dsc = rays ? dsc_rays : s->d;  // the scene record of the frame's shade launches
 
   PassState ps{};
   ps.spp = spp; ps.spp_log2 = spp_log2; ps.dims = dims;
@@ -1355,6 +1388,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       const int skip_dead_tail = ps.skip_dead_tail;
       tm.begin(&stats.ms_raygen);
       if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
+      else if (rays) {  // tiles of 2^(8 - ts) pixels x 2^ts samples, ts = log2(min(16, the pass's samples rounded up))
+        unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
+        rtx_launch_raygen_rays(pgrid, stream, fp, ps, d_rays, ray_src->sample0, ray_src->n_samples, ts_log2, d_samples_rad);
+      }
       else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
       tm.end();
       for (int bounce = 0; bounce <= fp.max_depth; ++bounce) {
@@ -1371,11 +1408,11 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         launch_trace<false>(s, count, io_path, ps.cnt_in, ps.cnt_in, ps.shard_cap, ps.cap, dstats, ST_RAYS_CLOSEST, ST_NODES_CLOSEST, ST_TRIS_CLOSEST, stream);
         tm.end();
         if (bounce <= 1 && build_tables) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][bounce + 1], 0));  // table groups 1 / 2: first read by the shade launches of bounce 0 / 1
-#define RT_SHADE(MODE, P) stats.launches_shade += 1, launch_shade<MODE>(gshade, lean_shade, bounce >= 1, sgrid, sblock, stream, s->d, fp, P, qlights, lds_shade)
+#define RT_SHADE(MODE, P) stats.launches_shade += 1, launch_shade<MODE>(gshade, lean_shade, bounce >= 1, sgrid, sblock, stream, dsc, fp, P, qlights, lds_shade)
         if (s->lambert_only) {
           tm.begin(&stats.ms_shade_lambert_const);
-          if (split_launch) rtx_launch_shade_split(bounce == 0, sgrid, stream, s->d, fp, ps, io_path.hit_mask);
-          else rtx_launch_shade_const(s->lds_records ? 1 : (s->lds_tables ? 3 : 0), sgrid, sblock, stream, s->d, fp, ps);  // LDSREC 3: a large mesh with few lights / materials (S2)
+          if (split_launch) rtx_launch_shade_split(bounce == 0, sgrid, stream, dsc, fp, ps, io_path.hit_mask);
+          else rtx_launch_shade_const(s->lds_records ? 1 : (s->lds_tables ? 3 : 0), sgrid, sblock, stream, dsc, fp, ps);  // LDSREC 3: a large mesh with few lights / materials (S2)
           tm.end(); stats.launches_shade += 1;
         }
         else if (s->lambert_materials) { tm.begin(&stats.ms_shade_lambert); RT_SHADE(3, ps); tm.end(); }
@@ -1427,6 +1464,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       }
       tm.begin(&stats.ms_film);
       if (fsamples) { }  // (the feature kernels wrote the output)
+      else if (rays) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
+        PassState po = ps; po.spp = ray_src->n_samples; po.s0 = ps.s0 - ray_src->sample0;
+        hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, po, wx0, wy0, wx1 - wx0, d_samples_rad, (float2*)nullptr);
+      }
       else if (samples) hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, ps, wx0, wy0, wx1 - wx0, d_samples_rad, d_samples_pf);
       else if (fr && fr->stats) hipLaunchKernelGGL(k_film_accumulate_frame_stats, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), fr->moments.as<PixMoments>());
       else if (fr) hipLaunchKernelGGL(k_film_accumulate_frame, dim3(pgrid), dim3(256), 0, stream, fp, ps, fr->filter_table.as<float>(), fr->film_acc.as<float4>(), fr->own_acc.as<float4>());
@@ -1494,6 +1535,31 @@ extern "C" int rt_render_sample_features(rt_scene* s, const rt_camera* cam, cons
                                          uint32_t flags, void* stream_, float* features) {
   if (!s || !cam || !film || !smp || !path || !features) return fail(RT_ERR_INVALID, "rt_render_sample_features: null argument");
   return render_frame(s, cam, film, smp, path, nullptr, flags & ~(uint32_t)RT_FLAG_FRAME_FEATURES, stream_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, features);
+}
+// PathIntegrator::li along the caller's rays. The batch is a virtual film: sample bounds = pixel bounds = [0, width) x [0, height) (a box filter of radius 0.5), so the
+// frame's FrameParams key every consumer - K0's tables, the shade kernels' RNG rebuild, split_path_id - by pixel_index = y * width + x without a change to any of them.
+extern "C" int rt_render_rays(rt_scene* s, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, const rt_sampler_desc* smp,
+                              const rt_path_desc* path, uint32_t flags, void* stream_, float* radiance, rt_stats* stats_out) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  if (!s || !rays || !smp || !path || !radiance) return fail(RT_ERR_INVALID, "rt_render_rays: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_rays: the reference-stream frame has no per-sample output");
+  if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rt_render_rays: width, height and n_samples must be positive");
+  if (smp->spp > 16384) return fail(RT_ERR_INVALID, "rt_render_rays: spp > 16384 unsupported");
+  if (smp->dimensions < 2 || smp->dimensions > 8) return fail(RT_ERR_INVALID, "rt_render_rays: sampler dimensions must be in [2, 8]");
+  const long long spp_r = (long long)next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
+  if (sample0 < 0 || (long long)sample0 + (long long)n_samples > spp_r) return fail(RT_ERR_INVALID, "rt_render_rays: [sample0, sample0 + n_samples) must lie inside [0, spp)");
+  // (64 bits: width * height < 2^62, and n_samples <= 2^14 multiplies a product already known to be <= 2^27)
+  if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX ||
+      (unsigned long long)width * (unsigned long long)height * (unsigned long long)n_samples > (unsigned long long)RT_RAYS_MAX)
+    return fail(RT_ERR_INVALID, "rt_render_rays: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+  rt_camera cam{};  // no camera: k_raygen_rays reads none, and the shade launches regenerate no differentials
+  rt_film_desc film{};
+  film.cropped_pixel_bounds[2] = film.sample_bounds[2] = width; film.cropped_pixel_bounds[3] = film.sample_bounds[3] = height;
+  film.filter_radius[0] = film.filter_radius[1] = 0.5f; film.max_sample_luminance = std::numeric_limits<float>::infinity();
+  rt_path_desc p = *path;  // pixel_bounds is ignored: every ray with t_max > 0 is traced
+  p.pixel_bounds[0] = p.pixel_bounds[1] = 0; p.pixel_bounds[2] = width; p.pixel_bounds[3] = height;
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples};
+  return render_frame(s, &cam, &film, smp, &p, nullptr, flags, stream_, nullptr, stats_out, radiance, nullptr, nullptr, 0, nullptr, false, nullptr, &src);
 }
 
 // ---------------------------------------------------------------------------------------------- progressive frames

@@ -1312,6 +1312,22 @@ int rtxh_render_sample_features(rtxh_scene* s, const rtxh_render_params* p, void
   if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_render_sample_features(s->dev, &cf.cam, &cf.film, &smp, &path, p->flags, stream, features);
 }
+int rtxh_render_rays(rtxh_scene* s, const rtxh_render_params* p, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, void* stream,
+                     float* radiance, rt_stats* stats) {
+  if (!s || !p || !rays || !radiance) return fail(RT_ERR_INVALID, "rtxh_render_rays: null argument");
+  g_err.clear();
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  {  // the sizes rt_render_rays refuses, before the scene is uploaded for it
+    long long spp = 1; while (spp < (long long)std::max(p->spp, 1)) spp <<= 1;
+    if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rtxh_render_rays: width, height and n_samples must be positive");
+    if (sample0 < 0 || (long long)sample0 + (long long)n_samples > spp) return fail(RT_ERR_INVALID, "rtxh_render_rays: [sample0, sample0 + n_samples) must lie inside [0, spp)");
+    if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX / (unsigned long long)n_samples)
+      return fail(RT_ERR_INVALID, "rtxh_render_rays: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+  }
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_rays(s->dev, rays, width, height, sample0, n_samples, &smp, &path, p->flags, stream, radiance, stats);
+}
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
 int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {

@@ -1,0 +1,82 @@
+// rtx_raygen_rays.h — bounce 0 from caller-supplied rays (rt_render_rays): the producer that stands where k_raygen stands when a frame's first rays do not come
+// from the perspective camera. Included by rtx_rays.hip alone (launchers: rtx_rays_launch.h); k_raygen / k_raygen_masked (rtx_raygen_body.inl) are not touched.
+#pragma once
+#include "rtx_kernels.h"
+
+namespace rtx {
+
+// Does any ray of the call carry a t_max that is not > 0 (zero, negative, NaN: the ray is skipped)? One scan of the rays before the first pass, one word read back:
+// the answer picks the route of every pass - none skipped: PassState::all_in_bounds with the fresh records, else the sharded bounce-0 queue of a cropped frame.
+static __global__ void __launch_bounds__(256) k_rays_scan(const float* __restrict__ rays, unsigned long long n_rays, unsigned* __restrict__ any_skipped) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  bool skip = false;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_rays; i += stride) skip |= !(rays[i * 8ull + 3ull] > 0.0f);
+  if (__ballot(skip) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(any_skipped, 1u);
+}
+
+// One lane per ray of the pass. The caller's records are [pixel][sample of the call][8 floats] - pixel-major - and the pass's path ids are sample-major (local sample *
+// n_pixels + batch pixel), so a workgroup takes a TILE of 2^tp_log2 pixels x 2^ts_log2 samples (256 rays): it reads the tile's records as 512 float4 - lane after lane,
+// runs of 2 * TS float4 per pixel, contiguous over the tile where the pass holds all the call's samples; once-through, so with the non-temporal hint of the other streams -
+// into LDS, and after a barrier every lane takes the ray of ITS path id, so that the record stores of a wave are the runs of neighbouring slots k_raygen's are.
+// ts_log2 = log2(min(16, the pass's samples rounded up to a power of two)), tp_log2 = 8 - ts_log2.
+// What it writes per ray is what rtx_raygen_body.inl writes per camera sample: lacc (zero | RT_STATE_OUT_OF_BOUNDS for a skipped ray), pfilm (the pixel centre: nothing
+// reads it, a ray frame shades with DScene::needs_differentials = 0), the ray at its slot with the caller's t_max in o.w, the throughput and state records unless the pass
+// leaves them out (PassState::fresh), the shard push where rays are skipped, and ST_CAMERA. A skipped ray (t_max not > 0) gets no slot and its answer right here:
+// rad[ray] = (0, 0, 0, 2.0) - k_sample_store passes over samples marked out of bounds.
+// ray_s0 / ray_ns: first sample and samples per pixel of the CALL (the pass renders [ps.s0, ps.s0 + ps.n_samples) of them).
+static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, unsigned ray_s0, unsigned ray_ns, unsigned ts_log2,
+                                                            float4* __restrict__ rad) {
+  __shared__ float4 s_ray[512 + 256];  // [tile pixel][2 * TS + 1]: one float4 of padding per pixel row
+  const unsigned tp_log2 = 8u - ts_log2, TS = 1u << ts_log2, TP = 1u << tp_log2, row = 2u * TS + 1u;
+  const unsigned n_ptiles = (ps.n_pixels + TP - 1u) >> tp_log2, n_stiles = (ps.n_samples + TS - 1u) >> ts_log2, n_tiles = n_ptiles * n_stiles;
+  unsigned n_camera = 0;
+  for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // (uniform per workgroup: barriers inside)
+    const unsigned stile = tile / n_ptiles, ptile = tile - stile * n_ptiles;
+    const unsigned pix0 = ptile << tp_log2, sl0 = stile << ts_log2;
+#pragma unroll
+    for (unsigned k = 0; k < 2u; ++k) {  // the tile's records, pixel-major as the caller laid them out
+      const unsigned idx = threadIdx.x + 256u * k, lp = idx >> (ts_log2 + 1u), within = idx & (2u * TS - 1u);
+      const unsigned pix = pix0 + lp, sl = sl0 + (within >> 1);
+      if (pix < ps.n_pixels && sl < ps.n_samples) {
+        int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+        s_ray[lp * row + within] = rays[(size_t)((pixel_index * ray_ns + (ps.s0 + sl - ray_s0)) * 2ull + (within & 1u))];
+      }
+    }
+    __syncthreads();
+    const unsigned lp = threadIdx.x & (TP - 1u), ls = threadIdx.x >> tp_log2;
+    const unsigned pix = pix0 + lp, sl = sl0 + ls;
+    const bool live = pix < ps.n_pixels && sl < ps.n_samples;
+    const unsigned pid = sl * ps.n_pixels + pix;
+    bool traced = false;
+    float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d4 = o4; unsigned long long rng_state = 0ull;
+    if (live) {
+      o4 = s_ray[lp * row + 2u * ls]; d4 = s_ray[lp * row + 2u * ls + 1u];
+      traced = o4.w > 0.0f;  // (false for NaN)
+      const unsigned s = ps.s0 + sl;
+      int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+      Pcg32 rng; rng.set_sequence(pixel_index * (unsigned long long)ps.spp + s + (1ull << 32));  // keyed per-sample stream, as k_raygen
+      rng_state = rng.state;
+      ps.lacc[pid] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(traced ? 0u : RT_STATE_OUT_OF_BOUNDS));
+      ps.pfilm[pid] = make_float2((float)x + 0.5f, (float)y + 0.5f);
+      if (!traced) rad[(size_t)(pixel_index * ray_ns + (s - ray_s0))] = make_float4(0.0f, 0.0f, 0.0f, 2.0f);
+    }
+    n_camera += traced ? 1u : 0u;
+    unsigned slot = pid;  // every ray traced: path i is entry i is slot i
+    if (!ps.all_in_bounds) {
+      const int ci[1] = {0}; const bool pr[1] = {traced}; unsigned sl_[1];
+      block_push<1>(ps.cnt_out, ps.shard_cap, ci, pr, sl_);
+      slot = sl_[0];
+    }
+    if (traced) {
+      ps.out.o[slot] = o4;
+      ps.out.d[slot] = make_float4(d4.x, d4.y, d4.z, 0.0f);
+      if (!RT_FRESH_BETA(ps)) ps.out.beta[slot] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+      if (!RT_FRESH_ST(ps)) ps.out.st[slot] = make_uint4(pack_state(0, false, 1, 2), pid, (unsigned)rng_state, (unsigned)(rng_state >> 32));  // counters where get_camera_sample leaves them
+    }
+    __syncthreads();  // (the next tile's records overwrite s_ray)
+  }
+  for (int off = 32; off > 0; off >>= 1) n_camera += __shfl_down(n_camera, off);
+  if ((threadIdx.x & 63u) == 0u && n_camera) atomicAdd(&ps.stats[ST_CAMERA], (unsigned long long)n_camera);
+}
+
+}  // namespace rtx

@@ -34,7 +34,9 @@ RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_
 RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
 RT_SAMPLES_MAX = 1 << 27
-RT_QUERY_BSDF_LAUNCHED = 5  # rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
+RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
+RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
+RT_QUERY_BSDF_LAUNCHED = 5# rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
 RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS, RT_FRAME_FEATURES = range(5)                                   # rt_frame_read: what
 RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES, RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS = range(6)   # rt_frame_query: what
 BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
@@ -517,6 +519,42 @@ class HostScene:
         out = np.zeros((h, w, spp, RT_FEATURE_FLOATS), np.float32)
         _check(L.rtxh_render_sample_features(self.h, C.byref(p), C.c_void_p(stream), out.ctypes.data_as(C.c_void_p)), "sample_features")
         return out
+
+    def render_rays(self, rays, sample0=0, spp=None, max_depth=None, device_out=None, stream=0, count_traversal=False, time_kernels=False):
+        """Path-traced radiance along caller-supplied rays (rt_render_rays): `rays` (H, W, ns, 8) float32 - o.xyz, t_max, d.xyz, unused; d is used as given -, returns
+        (radiance (H, W, ns, 4), stats dict): L rgb as PathIntegrator::li returns it and a fourth float 0.0 / 1.0 (the renderer would scrub the sample) / 2.0 (t_max not
+        > 0: the ray was not traced). Ray (x, y, sl) is sample sample0 + sl of pixel y * W + x of a virtual W x H film: `spp` (default: the scene's sampler's) sizes
+        the sampler tables and [sample0, sample0 + ns) must lie inside it - a job of more than RT_RAYS_MAX rays is cut by sample range. `max_depth` defaults to the
+        scene's integrator's; rr_threshold, light strategy and sampler dimensions are the scene's. `rays` may be a contiguous torch CUDA float32 tensor: `device_out`
+        must then be one of shape (H, W, ns, 4) (RT_FLAG_FILM_ON_DEVICE: both stay in HBM) and is returned."""
+        p = self._render_params()
+        if spp is not None:
+            p.spp = int(spp)
+        if max_depth is not None:
+            p.max_depth = int(max_depth)
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        on_device = hasattr(rays, "data_ptr")
+        if not on_device:
+            rays = np.ascontiguousarray(rays, np.float32)
+        if len(rays.shape) != 4 or rays.shape[3] != 8:
+            raise BackendError(f"render_rays: rays must have shape (H, W, ns, 8), not {tuple(rays.shape)}")
+        h, w, ns = (int(v) for v in rays.shape[:3])
+        if h * w * ns > RT_RAYS_MAX:
+            raise BackendError(f"render_rays: {h} x {w} x {ns} rays are more than RT_RAYS_MAX - cut the job by sample range")
+        L = lib()
+        L.rtxh_render_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if on_device:
+            if device_out is None or tuple(device_out.shape) != (h, w, ns, 4) or not (rays.is_contiguous() and device_out.is_contiguous()) or rays.element_size() != 4 or device_out.element_size() != 4:
+                raise BackendError("render_rays: device rays need a contiguous float32 device_out of shape (H, W, ns, 4)")
+            p.flags |= RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_rays(self.h, C.byref(p), C.c_void_p(rays.data_ptr()), w, h, int(sample0), ns, C.c_void_p(stream), C.c_void_p(device_out.data_ptr()), C.byref(stats)), "render_rays")
+            return device_out, stats.as_dict()
+        if device_out is not None:
+            raise BackendError("render_rays: device_out needs device rays (RT_FLAG_FILM_ON_DEVICE names both pointers)")
+        rad = np.zeros((h, w, ns, 4), np.float32)
+        _check(L.rtxh_render_rays(self.h, C.byref(p), rays.ctypes.data_as(C.c_void_p), w, h, int(sample0), ns, C.c_void_p(stream), rad.ctypes.data_as(C.c_void_p), C.byref(stats)), "render_rays")
+        return rad, stats.as_dict()
 
     def texture_words(self, tex):
         """The word block of texture `tex` as the host holds it (float32), or an empty array for a texture that names none."""

@@ -2,6 +2,7 @@
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
+                                  [--camera-model orthographic|environment [--seed N]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -18,7 +19,11 @@ the one the run without the flag writes.
 of them at once and the image written is the merged frame; prints the slowest worker's share of each step.
 --features out.npy: beside the image, the guide images a denoiser takes (RT_FLAG_FRAME_FEATURES): float32 [height, width, 8] = per pixel the means over its own samples of
 the first-hit albedo rgb and shading normal xyz, the mean depth of the samples that hit, and the coverage hits / samples - unfiltered. The frame is then rendered through
-rt_frame_* (in one step unless --preview-every / --adaptive cut it; on --devices if given): the image is the one the run without the flag writes."""
+rt_frame_* (in one step unless --preview-every / --adaptive cut it; on --devices if given): the image is the one the run without the flag writes.
+--camera-model orthographic|environment [--seed N]: the scene along the rays of a camera the reference does not have (rustracer_amd/cameras.py, pbrt-v3's definitions)
+through rt_render_rays, in place of the file's perspective camera - whose camera-to-world and screen window it keeps -: film positions pixel + 0.5 + a seeded jitter of
+the script's own, sample ranges of at most RT_RAYS_MAX rays, the radiance box-filtered (each pixel the mean of its own samples, scrubbed samples black). A choice of
+this command line, not a file directive: the loader refuses Camera "orthographic" / "environment" as the reference does."""
 import argparse
 import os
 import sys
@@ -26,10 +31,48 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def render_camera_model(s, model, seed=0):
+    """The scene through `HostScene.render_rays` with a camera of rustracer_amd/cameras.py in place of the file's: returns (rgb [yres, xres, 3] float32 - the box-filtered
+    radiance, each pixel the mean of its own samples, scrubbed samples black as in the renderer -, stats summed over the calls). The camera takes the file's
+    camera-to-world and, orthographic, its "screenwindow" (pbrt's default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5)
+    from numpy's default_rng(seed); the samples go through in sample ranges of at most RT_RAYS_MAX rays."""
+    import numpy as np
+    from rustracer_amd import cameras, host
+    p = s._render_params()
+    w, h = int(p.xres), int(p.yres)
+    spp = 1
+    while spp < max(int(p.spp), 1):
+        spp *= 2
+    if w * h > host.RT_RAYS_MAX:
+        raise SystemExit(f"--camera-model: a film of {w} x {h} pixels holds more than RT_RAYS_MAX rays per sample")
+    c2w = np.float32(list(p.cam_to_world)).reshape(4, 4)
+    win = tuple(float(v) for v in p.screen_window)
+    if win == (0.0, 0.0, 0.0, 0.0):
+        aspect = w / h
+        win = (-aspect, aspect, -1.0, 1.0) if aspect > 1.0 else (-1.0, 1.0, -1.0 / aspect, 1.0 / aspect)
+    rng = np.random.default_rng(seed)
+    total = np.zeros((h, w, 3), np.float64)
+    stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
+    step = max(1, min(spp, host.RT_RAYS_MAX // (w * h)))
+    for s0 in range(0, spp, step):
+        ns = min(step, spp - s0)
+        p_film = cameras.pixel_centres(w, h, ns) + rng.uniform(-0.5, 0.5, (h, w, ns, 2))
+        rays = cameras.orthographic(c2w, win, w, h, p_film) if model == "orthographic" else cameras.environment(c2w, w, h, p_film)
+        rad, st = s.render_rays(rays, sample0=s0, spp=spp)
+        ok = rad[..., 3:4] == 0.0
+        total += np.where(ok, rad[..., :3], 0.0).sum(axis=2, dtype=np.float64)
+        for k in stats:
+            stats[k] += st[k]
+    return (total / spp * float(p.film_scale)).astype(np.float32), stats
+
+
 def main():
     from rustracer_amd import host
     from rustracer_amd.ingest import write_pfm, write_png
     ap = argparse.ArgumentParser()
+    ap.add_argument("--camera-model", choices=["orthographic", "environment"], default=None,
+                    help="render along the rays of this camera (rt_render_rays) instead of the file's perspective camera; box-filtered")
+    ap.add_argument("--seed", type=int, default=0, help="with --camera-model: seed of the film-position jitter")
     ap.add_argument("scene")
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
@@ -56,6 +99,14 @@ def main():
     out = a.out or s.film_filename
     if not out.endswith((".pfm", ".png")):
         raise SystemExit("Unsupported file format")   # rc/imageio.rs:47-49 (EXR output is not written here)
+    if a.camera_model:
+        rgb, stats = render_camera_model(s, a.camera_model, a.seed)
+        if out.endswith(".pfm"):
+            write_pfm(out, rgb)
+        else:
+            write_png(out, host.rgb_to_png8(rgb), 2, 8, filters=(1,))
+        print(f"{out}: {rgb.shape[1]}x{rgb.shape[0]}, {a.camera_model} camera, {stats['camera_rays']} rays, {stats['paths_scrubbed']} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
+        return
 
     def write(film):
         rgb = host.film_to_rgb(film, s.params.film_scale)
