@@ -513,8 +513,13 @@ int rt_render_rays(rt_scene* scene, const float* rays, int32_t width, int32_t he
  *   rays_tail_not_cast and the rays actually cast differ there, as they do under RTX_DEAD_TAIL=0, and the film does not.
  * rt_frame_read(RT_FRAME_FEATURES): W*H*8 float32 over the cropped pixel bounds - albedo.rgb = (float)(sum / n), normal.xyz = (float)(sum / n) (not renormalised: misses
  *   add zero), depth = (float)(sum / hits) or 0 when hits == 0, coverage = (float)((double)hits / n); IEEE double divisions. Zeros where n == 0, in rows of other ranks and
- *   before the first step; scale ignored; RT_ERR_INVALID on a frame begun without the flag. */
-enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2, RT_FRAME_STATS = 3, RT_FRAME_FEATURES = 4 };
+ *   before the first step; scale ignored; RT_ERR_INVALID on a frame begun without the flag.
+ *
+ * rt_frame_read(RT_FRAME_SUMS): W*H float4 over the cropped pixel bounds - the frame's sums as it holds them, before any colour arithmetic: (sum of w * L).rgb and the filter
+ *   weight sum, film sum + the pixel's own sum as in every other read-out (RT_FRAME_XYZW is these through the float32 RGB -> XYZ matrix, with the same fourth value). For a
+ *   caller that wants sum / weight in the radiance's own RGB - RT_FRAME_RGB is Film::write_image's pixel and goes RGB -> XYZ -> RGB, two float32 matrices that multiply to the
+ *   identity only within 1e-6. scale ignored. rt_frame_read only: rt_multi_frame_read refuses it as an unknown read-out. */
+enum { RT_FRAME_XYZW = 0, RT_FRAME_RGB = 1, RT_FRAME_RGB8 = 2, RT_FRAME_STATS = 3, RT_FRAME_FEATURES = 4, RT_FRAME_SUMS = 5 };
 enum { RT_FRAME_SAMPLES_DONE = 0, RT_FRAME_SPP = 1, RT_FRAME_TABLES_RESIDENT = 2, RT_FRAME_STATE_BYTES = 3, RT_FRAME_SAMPLES_TAKEN = 4, RT_FRAME_ACTIVE_PIXELS = 5 };
 typedef struct rt_frame rt_frame;
 int rt_frame_begin(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
@@ -524,6 +529,36 @@ int rt_frame_advance_adaptive(rt_frame* frame, int32_t n_samples, float threshol
 int rt_frame_read(rt_frame* frame, int32_t what, float scale, uint32_t flags, void* stream, void* out);
 int rt_frame_query(rt_frame* frame, int32_t what, uint64_t* value);
 void rt_frame_end(rt_frame* frame);
+
+/* Ray frames: a progressive frame whose steps take their rays, and the film positions their samples are splatted at, from the caller - the film stage of rt_frame_* for
+ * the cameras rt_render_rays serves (orthographic, environment, fisheye, a realistic lens), lightmap bakes and light probes. Nothing per sample travels back to the host.
+ * rt_frame_begin_rays opens a frame over rt_render_rays' VIRTUAL FILM: sample bounds = cropped pixel bounds = [0, width) x [0, height), pixel_index = y * width + x, so a
+ *   ray frame and rt_render_rays draw the same sampler values for the same ray. Of `film` only filter_radius, filter_table and max_sample_luminance are read (both bounds
+ *   arrays are ignored); NULL: a box filter of radius 0.5, a table of ones, no clamp. path->pixel_bounds is ignored, as in rt_render_rays. rt_shard is honoured: rays of
+ *   rows a rank does not own are never read. flags: RT_FLAG_FRAME_STATS / _FRAME_FEATURES as in rt_frame_begin; RT_FLAG_COUNT_TRAVERSAL / _TIME_KERNELS /
+ *   _COUNT_AS_RENDERED act per step. Refused with RT_ERR_INVALID before any device work: a NULL out, scene, sampler or path; width or height <= 0; width * height >
+ *   RT_RAYS_MAX; spp > 16384; dimensions outside [2, 8]; a bad shard; a filter radius > 8 or not > 0; RT_FLAG_REF_STREAM.
+ * rt_frame_advance_rays renders samples [done, done + n_samples) of every owned pixel:
+ *   rays    [height][width][n_samples][8] floats, rt_render_rays' record, for exactly those samples;
+ *   p_film  [height][width][n_samples][2] floats: the raster position each sample is splatted at (FilmTile::add_sample), or NULL: the pixel centre (x + 0.5, y + 0.5).
+ *   The position is used as given. A sample whose position lies in its own pixel goes into the pixel's own sum in sample-index order, as in rt_frame_advance: with the
+ *   camera's rays and positions the film is the camera frame's, bit for bit. A position elsewhere is legal; what it adds to other pixels - like every tap of a wide
+ *   filter outside the sample's pixel - reaches the film through float atomics, so those sums are fixed only up to the order of the additions.
+ *   A ray whose t_max is not > 0 (zero, negative, NaN) is SKIPPED, as in rt_render_rays: not traced, not splatted, not counted in the moments' n, the feature plane's n or
+ *   camera_rays - the way to mask pixels (outside a fisheye circle, say). The one scan of the step's rays that picks the route of its passes is rt_render_rays'.
+ *   flags: RT_FLAG_FILM_ON_DEVICE - rays and p_film are device pointers; any other bit is RT_ERR_INVALID. RT_ERR_INVALID before any device work: a NULL frame or rays;
+ *   a frame begun with rt_frame_begin; n_samples <= 0; done + n_samples > spp (rounded) - the caller's array fixes the count, so it is refused, not clamped;
+ *   width * height * n_samples > RT_RAYS_MAX. A finished frame: RT_OK, zeroed stats. rt_frame_advance / _advance_adaptive on a ray frame are RT_ERR_INVALID as well.
+ * rt_frame_advance_rays_adaptive: rt_frame_advance_adaptive's decision - per pixel, from the moments plane as it stands, before any path work - with the caller's rays:
+ *   the rays of an inactive pixel are passed over like skipped rays (and not read). Needs RT_FLAG_FRAME_STATS; threshold, floor_y and min_samples as there.
+ *   RT_FRAME_ACTIVE_PIXELS and RT_FRAME_SAMPLES_TAKEN behave as for a camera frame.
+ * rt_frame_read, rt_frame_query and rt_frame_end work unchanged on a ray frame. The rays carry no differentials (see rt_render_rays). Single device per frame. */
+int rt_frame_begin_rays(rt_scene* scene, int32_t width, int32_t height, const rt_film_desc* film /* may be NULL */, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                        const rt_shard* shard /* may be NULL */, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out);
+int rt_frame_advance_rays(rt_frame* frame, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, uint32_t flags, void* stream,
+                          rt_stats* stats /* of this step, may be NULL */);
+int rt_frame_advance_rays_adaptive(rt_frame* frame, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, float threshold, float floor_y,
+                                   int32_t min_samples, uint32_t flags, void* stream, rt_stats* stats /* of this step, may be NULL */);
 
 /* Progressive and adaptive frames across the workers of an rt_multi: the frame of rt_frame_* spread over the devices of rt_multi_create, read as ONE film.
  * rt_multi_frame_begin opens one rt_frame per worker k on the multi's replica k with rt_shard{k, n_devices} - the static split into interleaved bands of

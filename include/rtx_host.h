@@ -166,6 +166,16 @@ int rtxh_frame_advance_adaptive(rtxh_frame*, int32_t n_samples, float threshold,
 int rtxh_frame_read(rtxh_frame*, int32_t what, float scale, uint32_t flags, void* hip_stream, void* out);
 int rtxh_frame_query(rtxh_frame*, int32_t what, uint64_t* value);
 void rtxh_frame_end(rtxh_frame*);
+/* A ray frame of the scene (rt_frame_begin_rays / rt_frame_advance_rays* in rtx_hip.h): a progressive frame over a width x height film whose steps take their rays
+ * (height x width x n_samples x 8 floats) and film positions (height x width x n_samples x 2, or NULL: pixel centres) from the caller. Of the parameters the sampler, the
+ * integrator, the pixel filter (filter_kind, filter_params), max_sample_luminance, rank / world_size and the flags are read: no camera is set up, and xres / yres, crop
+ * and pixel bounds are ignored. Sizes rt_frame_begin_rays refuses are refused before the scene is uploaded for it. flags of a step: RT_FLAG_FILM_ON_DEVICE - rays and
+ * p_film are device pointers. The frame is read, queried and ended with rtxh_frame_read / _query / _end. */
+int rtxh_frame_begin_rays(rtxh_scene*, const rtxh_render_params*, int32_t width, int32_t height, uint64_t table_budget_bytes, rtxh_frame** out);
+int rtxh_frame_advance_rays(rtxh_frame*, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, uint32_t flags, void* hip_stream,
+                            rt_stats* stats /* of this step, may be NULL */);
+int rtxh_frame_advance_rays_adaptive(rtxh_frame*, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, float threshold, float floor_y,
+                                     int32_t min_samples, uint32_t flags, void* hip_stream, rt_stats* stats /* of this step, may be NULL */);
 /* The same frame on several GPUs of this process (rt_multi_* in rtx_hip.h): the scene is replicated on `devices` (kept for later calls with the
  * same list), host threads pull chunks of tile rows, the film is gathered on devices[0] and returned in host memory (or in memory of devices[0]
  * with RT_FLAG_FILM_ON_DEVICE). rank / world_size of the parameters are ignored. */

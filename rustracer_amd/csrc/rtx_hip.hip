@@ -100,6 +100,7 @@ struct rt_scene {
   DevBuf ws[32];
   DevBuf film_acc, own_acc, film_out, counters, stats, filter_table, ref_samples, ref_stack;
   DevBuf samples_rad, samples_pf;  // rt_render_samples with host outputs: [window pixel][sample] radiance (float4) and film position (float2)
+  DevBuf pfilm_in;                 // rt_frame_advance_rays*: the caller's host film positions in device memory ([pixel][sample of the step] 8 B)
   DevBuf rays_in, rays_skipped;    // rt_render_rays: the caller's host rays in device memory ([pixel][sample] 32 B), and the word k_rays_scan leaves (1: some ray is skipped)
   DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
   DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
@@ -1029,6 +1030,8 @@ struct rt_frame {
   // RT_FLAG_FRAME_FEATURES: [owned pixel] sums of the first-hit features of the pixel's own samples (PixFeatures, 64 B, zero at begin)
   bool features = false;
   DevBuf feature_plane;
+  // rt_frame_begin_rays: every step takes its rays and film positions from the caller (rt_frame_advance_rays*); `cam` is unused
+  bool ray_frame = false;
   size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes + feature_plane.bytes; }
 };
 static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u * (size_t)(owned_pixels / 4096u + 4u); }  // alignment room: a batch holds >= 4096 pixels, plus a leading and a last one
@@ -1047,7 +1050,11 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // `film` whose bounce 0 comes from k_raygen_rays instead of k_raygen: samples [sample0, sample0 + n_samples) of every pixel, no camera, and no differentials - every
 // launch gets the scene record with needs_differentials = 0. One scan of the rays (k_rays_scan) before the first pass decides the route of all passes: no ray skipped -
 // all_in_bounds, as a frame whose pixel_bounds crop nothing; else the sharded bounce-0 queue of a cropped one. Everything after ray generation is the samples frame's.
-struct RaySource { const float* rays; unsigned sample0, n_samples; };
+// ray_src != NULL together with fr != NULL: the step of a RAY FRAME (rt_frame_advance_rays*) - samples [fr->done, step_end) of every owned pixel, sample0 = fr->done and
+// n_samples = step_end - fr->done, bounce 0 from k_raygen_rays_film (k_raygen_rays_film_masked under active_mask), which also hands each sample's film position
+// (ray_src->p_film, or the pixel centre) to ps.pfilm; everything after ray generation is the frame step's - its film kernel, its feature kernels, its resident tables.
+// A shard stages and scans the rays of its own rows only. on_device: rays and p_film are device pointers (rt_render_rays: RT_FLAG_FILM_ON_DEVICE of the call).
+struct RaySource { const float* rays; unsigned sample0, n_samples; const float* p_film; bool on_device; };
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
                         rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr,
@@ -1234,7 +1241,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       if (fsamples) want.push_back({&s->samples_feat, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4});
       else if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
       else { want.push_back({&s->samples_rad, (size_t)n_window_samples * 16}); if (samples_pf) want.push_back({&s->samples_pf, (size_t)n_window_samples * 8}); }
-      if (rays) want.push_back({&s->rays_in, (size_t)n_window_samples * 32});
+    }
+    if (rays && !ray_src->on_device) {
+      want.push_back({&s->rays_in, (size_t)n_window_samples * 32});
+      if (fr && ray_src->p_film) want.push_back({&s->pfilm_in, (size_t)n_window_samples * 8});
     }
     if (rays) want.push_back({&s->rays_skipped, 16});
     size_t grow = 0;  // bytes the buffers have to grow by (a buffer that is too small is freed and allocated anew)
@@ -1269,21 +1279,38 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   // A ray frame: the caller's rays in device memory, and the one scan that picks the route of its passes (timed with ray generation). Its launches take the scene
   // record with needs_differentials cleared (DScene travels by value): the rays are Ray { differential: None }, every derivative stays zero (interaction.rs:245-314).
   const float4* d_rays = nullptr;
+  const float2* d_pfilm = nullptr;  // (a ray frame's film positions; NULL: pixel centres)
   DScene dsc_rays;
   if (rays) {
     dsc_rays = s->d; dsc_rays.needs_differentials = 0;
-    if (flags & RT_FLAG_FILM_ON_DEVICE) d_rays = (const float4*)ray_src->rays;
-    else { HIP_TRY(hipMemcpyAsync(s->rays_in.p, ray_src->rays, (size_t)n_window_samples * 32, hipMemcpyHostToDevice, stream)); d_rays = s->rays_in.as<float4>(); }
-    HIP_TRY(hipMemsetAsync(s->rays_skipped.p, 0, 4, stream));
-    tm.begin(&stats.ms_raygen);
-    rtx_launch_rays_scan((unsigned)std::min<unsigned long long>((n_window_samples + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, (const float*)d_rays, n_window_samples,
-                         s->rays_skipped.as<unsigned>());
-    tm.end();
-    HIP_TRY(hipGetLastError());
-    unsigned any_skipped = 0;
-    HIP_TRY(hipMemcpyAsync(&any_skipped, s->rays_skipped.p, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (any_skipped) all_in_bounds = false;
+    if (ray_src->on_device) { d_rays = (const float4*)ray_src->rays; d_pfilm = fr ? (const float2*)ray_src->p_film : nullptr; }
+    else if (!fr) { HIP_TRY(hipMemcpyAsync(s->rays_in.p, ray_src->rays, (size_t)n_window_samples * 32, hipMemcpyHostToDevice, stream)); d_rays = s->rays_in.as<float4>(); }
+    else {  // a ray frame: the rows the rank owns (bands of `band` rows, every world-th one), at their place in the whole array
+      const size_t row_rays = (size_t)W * ray_src->n_samples;
+      for (int r0 = rank * band; r0 < H; r0 += world * band) {
+        const size_t first = (size_t)r0 * row_rays, n = (size_t)(std::min(r0 + band, H) - r0) * row_rays;
+        HIP_TRY(hipMemcpyAsync((char*)s->rays_in.p + first * 32, (const char*)ray_src->rays + first * 32, n * 32, hipMemcpyHostToDevice, stream));
+        if (ray_src->p_film) HIP_TRY(hipMemcpyAsync((char*)s->pfilm_in.p + first * 8, (const char*)ray_src->p_film + first * 8, n * 8, hipMemcpyHostToDevice, stream));
+      }
+      d_rays = s->rays_in.as<float4>(); d_pfilm = ray_src->p_film ? s->pfilm_in.as<float2>() : nullptr;
+    }
+    if (all_in_bounds && owned_pixels > 0) {  // (the step of rt_frame_advance_rays_adaptive takes the queued route whatever the rays hold: nothing to decide)
+      HIP_TRY(hipMemsetAsync(s->rays_skipped.p, 0, 4, stream));
+      tm.begin(&stats.ms_raygen);
+      if (fr && world > 1) {
+        const unsigned long long n_owned = owned_pixels * ray_src->n_samples;
+        rtx_launch_rays_scan_owned((unsigned)std::min<unsigned long long>((n_owned + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, fp, (const float*)d_rays, owned_pixels,
+                                   ray_src->n_samples, s->rays_skipped.as<unsigned>());
+      } else
+        rtx_launch_rays_scan((unsigned)std::min<unsigned long long>((n_window_samples + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, (const float*)d_rays, n_window_samples,
+                             s->rays_skipped.as<unsigned>());
+      tm.end();
+      HIP_TRY(hipGetLastError());
+      unsigned any_skipped = 0;
+      HIP_TRY(hipMemcpyAsync(&any_skipped, s->rays_skipped.p, 4, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      if (any_skipped) all_in_bounds = false;
+    }
   }
   const DScene& dsc = rays ? dsc_rays : s->d;  // the scene record of the frame's shade launches
 
@@ -1387,7 +1414,11 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       ps.skip_dead_tail = (!tail_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
       const int skip_dead_tail = ps.skip_dead_tail;
       tm.begin(&stats.ms_raygen);
-      if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
+      if (rays && fr) {  // the step of a ray frame: k_raygen_rays' tiles, and the film positions (masked in an adaptive step)
+        unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
+        rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, d_rays, d_pfilm, ray_src->sample0, ray_src->n_samples, ts_log2, active_mask);
+      }
+      else if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
       else if (rays) {  // tiles of 2^(8 - ts) pixels x 2^ts samples, ts = log2(min(16, the pass's samples rounded up))
         unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
         rtx_launch_raygen_rays(pgrid, stream, fp, ps, d_rays, ray_src->sample0, ray_src->n_samples, ts_log2, d_samples_rad);
@@ -1464,7 +1495,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       }
       tm.begin(&stats.ms_film);
       if (fsamples) { }  // (the feature kernels wrote the output)
-      else if (rays) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
+      else if (rays && !fr) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
         PassState po = ps; po.spp = ray_src->n_samples; po.s0 = ps.s0 - ray_src->sample0;
         hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, po, wx0, wy0, wx1 - wx0, d_samples_rad, (float2*)nullptr);
       }
@@ -1558,7 +1589,7 @@ extern "C" int rt_render_rays(rt_scene* s, const float* rays, int32_t width, int
   film.filter_radius[0] = film.filter_radius[1] = 0.5f; film.max_sample_luminance = std::numeric_limits<float>::infinity();
   rt_path_desc p = *path;  // pixel_bounds is ignored: every ray with t_max > 0 is traced
   p.pixel_bounds[0] = p.pixel_bounds[1] = 0; p.pixel_bounds[2] = width; p.pixel_bounds[3] = height;
-  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples};
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
   return render_frame(s, &cam, &film, smp, &p, nullptr, flags, stream_, nullptr, stats_out, radiance, nullptr, nullptr, 0, nullptr, false, nullptr, &src);
 }
 
@@ -1628,6 +1659,7 @@ extern "C" int rt_frame_begin(rt_scene* s, const rt_camera* cam, const rt_film_d
 }
 extern "C" int rt_frame_advance(rt_frame* fr, int32_t n_samples, void* stream, rt_stats* stats_out) {
   if (!fr) return fail(RT_ERR_INVALID, "rt_frame_advance: null frame");
+  if (fr->ray_frame) return fail(RT_ERR_INVALID, "rt_frame_advance: a ray frame takes its steps from rt_frame_advance_rays");
   if (n_samples <= 0) return fail(RT_ERR_INVALID, "rt_frame_advance: n_samples must be positive");
   if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
   const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
@@ -1652,15 +1684,9 @@ static FrameParams frame_pixel_params(const rt_frame* fr) {
 }
 // One adaptive step: k_frame_active decides every owned pixel from its moments as they stand, then the step of rt_frame_advance runs with that mask in front of its
 // ray generation. The scene's mutex is held from the mask to the last film kernel, so no other step of the frame can move the moments in between.
-extern "C" int rt_frame_advance_adaptive(rt_frame* fr, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* stream_, rt_stats* stats_out) {
-  if (!fr) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: null frame");
-  if (!fr->stats) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: the frame was begun without RT_FLAG_FRAME_STATS");
-  if (n_samples <= 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: n_samples must be positive");
-  if (min_samples < 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: min_samples must not be negative");
-  if (!(threshold >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: threshold must be a number >= 0 (+inf: no pixel past min_samples)");
-  if (!(floor_y >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: floor_y must be a number >= 0");
-  if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
-  const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
+// (shared by rt_frame_advance_adaptive and rt_frame_advance_rays_adaptive, after their refusals: the mask, then the step to sample index `end` - with the caller's rays
+// where ray_src is not NULL)
+static int frame_adaptive_step(rt_frame* fr, unsigned end, float threshold, float floor_y, int32_t min_samples, void* stream_, rt_stats* stats_out, const RaySource* ray_src) {
   rt_scene* s = fr->scene;
   std::lock_guard<std::mutex> render_lock(s->render_mutex);
   HIP_TRY(hipSetDevice(s->device));
@@ -1679,19 +1705,111 @@ extern "C" int rt_frame_advance_adaptive(rt_frame* fr, int32_t n_samples, float 
   rt_stats st{};
   if (n_active > 0) {  // (no active pixel: no path kernel, no film kernel - the step only moves `done`)
     const int rc = render_frame(s, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, &st, nullptr, nullptr, fr, end,
-                                fr->active.as<unsigned char>(), true);
+                                fr->active.as<unsigned char>(), true, nullptr, ray_src);
     if (rc != RT_OK) return rc;
   }
   fr->done = end; fr->samples_taken += st.camera_rays;
   if (stats_out) *stats_out = st;
   return RT_OK;
 }
+extern "C" int rt_frame_advance_adaptive(rt_frame* fr, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, void* stream_, rt_stats* stats_out) {
+  if (!fr) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: null frame");
+  if (fr->ray_frame) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: a ray frame takes its steps from rt_frame_advance_rays_adaptive");
+  if (!fr->stats) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: the frame was begun without RT_FLAG_FRAME_STATS");
+  if (n_samples <= 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: n_samples must be positive");
+  if (min_samples < 0) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: min_samples must not be negative");
+  if (!(threshold >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: threshold must be a number >= 0 (+inf: no pixel past min_samples)");
+  if (!(floor_y >= 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_advance_adaptive: floor_y must be a number >= 0");
+  if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
+  const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
+  return frame_adaptive_step(fr, end, threshold, floor_y, min_samples, stream_, stats_out, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- ray frames
+// A progressive frame over rt_render_rays' virtual film - sample bounds = cropped pixel bounds = [0, width) x [0, height), pixel_index = y * width + x - whose steps take
+// their rays and film positions from the caller. The frame is rt_frame_begin's with that film and a camera nothing reads; rt_frame_read / _query / _end do not know the
+// difference.
+extern "C" int rt_frame_begin_rays(rt_scene* s, int32_t width, int32_t height, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path, const rt_shard* shard,
+                                   uint32_t flags, uint64_t table_budget_bytes, rt_frame** out) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  if (!out) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: NULL out");
+  *out = nullptr;
+  if (!s || !smp || !path) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: the reference-stream frame cannot be rendered in steps");
+  if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: width and height must be positive");
+  if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX)
+    return fail(RT_ERR_INVALID, "rt_frame_begin_rays: the film holds more than RT_RAYS_MAX (2^27) pixels");
+  if (smp->spp > 16384) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: spp > 16384 unsupported");
+  if (smp->dimensions < 2 || smp->dimensions > 8) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: sampler dimensions must be in [2, 8]");
+  if (shard && (shard->world_size < 1 || shard->rank < 0 || shard->rank >= shard->world_size)) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: bad shard");
+  if (film && (film->filter_radius[0] > 8.0f || film->filter_radius[1] > 8.0f)) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: filter radius > 8");
+  if (film && !(film->filter_radius[0] > 0.0f && film->filter_radius[1] > 0.0f)) return fail(RT_ERR_INVALID, "rt_frame_begin_rays: the filter radius must be a number > 0");
+  rt_camera cam{};  // no camera: k_raygen_rays_film reads none, and the shade launches regenerate no differentials
+  rt_film_desc f{};  // of `film`: the filter's radius and table, and the clamp; NULL: a box of radius 0.5 and no clamp
+  f.cropped_pixel_bounds[2] = f.sample_bounds[2] = width; f.cropped_pixel_bounds[3] = f.sample_bounds[3] = height;
+  if (film) { memcpy(f.filter_radius, film->filter_radius, sizeof(f.filter_radius)); memcpy(f.filter_table, film->filter_table, sizeof(f.filter_table)); f.max_sample_luminance = film->max_sample_luminance; }
+  else { f.filter_radius[0] = f.filter_radius[1] = 0.5f; for (float& w : f.filter_table) w = 1.0f; f.max_sample_luminance = std::numeric_limits<float>::infinity(); }
+  rt_path_desc p = *path;  // pixel_bounds is ignored: every ray with t_max > 0 is traced
+  p.pixel_bounds[0] = p.pixel_bounds[1] = 0; p.pixel_bounds[2] = width; p.pixel_bounds[3] = height;
+  const int rc = rt_frame_begin(s, &cam, &f, smp, &p, shard, flags, table_budget_bytes, out);
+  if (rc == RT_OK) (*out)->ray_frame = true;
+  return rc;
+}
+// What both advance calls refuse, in two halves: the pointers, the flags and the kind of frame ...
+static int frame_rays_kind_check(const char* who, rt_frame* fr, const float* rays, uint32_t flags) {
+  if (!fr || !rays) return fail(RT_ERR_INVALID, std::string(who) + ": null frame or rays");
+  if (flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE) return fail(RT_ERR_INVALID, std::string(who) + ": the only flag of a step is RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers)");
+  if (!fr->ray_frame) return fail(RT_ERR_INVALID, std::string(who) + ": the frame was begun with a camera (rt_frame_begin): it takes its steps from rt_frame_advance / _adaptive");
+  return RT_OK;
+}
+// ... and the step's sample count (*finished: the frame holds all its samples - RT_OK with zeroed stats)
+static int frame_rays_count_check(const char* who, rt_frame* fr, int32_t n_samples, bool* finished) {
+  *finished = false;
+  if (n_samples <= 0) return fail(RT_ERR_INVALID, std::string(who) + ": n_samples must be positive");
+  if (fr->done >= fr->spp) { *finished = true; return RT_OK; }
+  if ((unsigned long long)fr->done + (unsigned long long)n_samples > (unsigned long long)fr->spp)
+    return fail(RT_ERR_INVALID, std::string(who) + ": done + n_samples exceeds the frame's spp (the rays array fixes the count: it is not clamped)");
+  const unsigned long long px = (unsigned long long)fr->film.sample_bounds[2] * (unsigned long long)fr->film.sample_bounds[3];
+  if (px * (unsigned long long)n_samples > (unsigned long long)RT_RAYS_MAX) return fail(RT_ERR_INVALID, std::string(who) + ": the step holds more than RT_RAYS_MAX (2^27) rays - take fewer samples per step");
+  return RT_OK;
+}
+extern "C" int rt_frame_advance_rays(rt_frame* fr, const float* rays, const float* p_film, int32_t n_samples, uint32_t flags, void* stream, rt_stats* stats_out) {
+  bool finished = false;
+  int rc = frame_rays_kind_check("rt_frame_advance_rays", fr, rays, flags);
+  if (rc == RT_OK) rc = frame_rays_count_check("rt_frame_advance_rays", fr, n_samples, &finished);
+  if (rc != RT_OK) return rc;
+  if (finished) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }
+  const unsigned end = fr->done + (unsigned)n_samples;
+  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
+  rt_stats st{};
+  rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, &st, nullptr, nullptr, fr, end, nullptr,
+                    false, nullptr, &src);
+  if (rc == RT_OK) { fr->done = end; fr->samples_taken += st.camera_rays; if (stats_out) *stats_out = st; }
+  return rc;
+}
+extern "C" int rt_frame_advance_rays_adaptive(rt_frame* fr, const float* rays, const float* p_film, int32_t n_samples, float threshold, float floor_y, int32_t min_samples,
+                                              uint32_t flags, void* stream, rt_stats* stats_out) {
+  bool finished = false;
+  const char* who = "rt_frame_advance_rays_adaptive";
+  // (the frame-free refusals and the kind of frame first, then what rt_frame_advance_adaptive refuses, in its order)
+  int rc = frame_rays_kind_check(who, fr, rays, flags);
+  if (rc != RT_OK) return rc;
+  if (!fr->stats) return fail(RT_ERR_INVALID, std::string(who) + ": the frame was begun without RT_FLAG_FRAME_STATS");
+  if (min_samples < 0) return fail(RT_ERR_INVALID, std::string(who) + ": min_samples must not be negative");
+  if (!(threshold >= 0.0f)) return fail(RT_ERR_INVALID, std::string(who) + ": threshold must be a number >= 0 (+inf: no pixel past min_samples)");
+  if (!(floor_y >= 0.0f)) return fail(RT_ERR_INVALID, std::string(who) + ": floor_y must be a number >= 0");
+  rc = frame_rays_count_check(who, fr, n_samples, &finished);
+  if (rc != RT_OK) return rc;
+  if (finished) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }
+  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
+  return frame_adaptive_step(fr, fr->done + (unsigned)n_samples, threshold, floor_y, min_samples, stream, stats_out, &src);
+}
 static size_t frame_read_bytes(int32_t what) {  // bytes per cropped pixel of a read-out
-  return what == RT_FRAME_FEATURES ? 32 : (what == RT_FRAME_STATS ? 24 : (what == RT_FRAME_XYZW ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
+  return what == RT_FRAME_FEATURES ? 32 : (what == RT_FRAME_STATS ? 24 : ((what == RT_FRAME_XYZW || what == RT_FRAME_SUMS) ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));
 }
 extern "C" int rt_frame_read(rt_frame* fr, int32_t what, float scale, uint32_t flags, void* stream_, void* out) {
   if (!fr || !out) return fail(RT_ERR_INVALID, "rt_frame_read: null argument");
-  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS && what != RT_FRAME_FEATURES) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
+  if (what != RT_FRAME_XYZW && what != RT_FRAME_RGB && what != RT_FRAME_RGB8 && what != RT_FRAME_STATS && what != RT_FRAME_FEATURES && what != RT_FRAME_SUMS) return fail(RT_ERR_INVALID, "rt_frame_read: unknown read-out");
   if (what == RT_FRAME_STATS && !fr->stats) return fail(RT_ERR_INVALID, "rt_frame_read: RT_FRAME_STATS needs a frame begun with RT_FLAG_FRAME_STATS");
   if (what == RT_FRAME_FEATURES && !fr->features) return fail(RT_ERR_INVALID, "rt_frame_read: RT_FRAME_FEATURES needs a frame begun with RT_FLAG_FRAME_FEATURES");
   rt_scene* s = fr->scene;
@@ -1706,6 +1824,7 @@ extern "C" int rt_frame_read(rt_frame* fr, int32_t what, float scale, uint32_t f
   void* const d_out = on_device ? out : fr->out.p;
   if (what == RT_FRAME_FEATURES) hipLaunchKernelGGL(k_frame_features_read<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, (const PixFeatures* const*)nullptr, fr->feature_plane.as<PixFeatures>(), (float*)d_out, n);
   else if (what == RT_FRAME_STATS) hipLaunchKernelGGL(k_frame_stats_read, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->moments.as<PixMoments>(), (double*)d_out, n);
+  else if (what == RT_FRAME_SUMS) rtx_launch_frame_sums_read(stream, fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), (float4*)d_out, n);
   else hipLaunchKernelGGL(k_frame_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fp, fr->film_acc.as<float4>(), fr->own_acc.as<float4>(), (int)what, scale, d_out, n);
   HIP_TRY(hipGetLastError());
   if (!on_device) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, stream));

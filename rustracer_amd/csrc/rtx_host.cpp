@@ -1376,6 +1376,45 @@ void rtxh_frame_end(rtxh_frame* f) {
   rt_frame_end(f->f);
   delete f;
 }
+// A ray frame of the scene (rt_frame_begin_rays): the film is width x height with the parameters' pixel filter and clamp, tabulated as setup_camera_film tabulates them.
+int rtxh_frame_begin_rays(rtxh_scene* s, const rtxh_render_params* p, int32_t width, int32_t height, uint64_t table_budget_bytes, rtxh_frame** out) {
+  if (!s || !p || !out) return fail(RT_ERR_INVALID, "rtxh_frame_begin_rays: null argument");
+  g_err.clear();
+  *out = nullptr;
+  // the sizes rt_frame_begin_rays refuses, before the scene is uploaded for it
+  if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "rtxh_frame_begin_rays: width and height must be positive");
+  if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX) return fail(RT_ERR_INVALID, "rtxh_frame_begin_rays: the film holds more than RT_RAYS_MAX (2^27) pixels");
+  if (p->spp > 16384) return fail(RT_ERR_INVALID, "rtxh_frame_begin_rays: spp > 16384 unsupported");
+  rt_film_desc film{};
+  const float xw = p->filter_params[0], yw = p->filter_params[1];
+  if (!(xw > 0.0f && yw > 0.0f) || xw > 8.0f || yw > 8.0f) return fail(RT_ERR_INVALID, "rtxh_frame_begin_rays: the filter radius must lie in (0, 8]");
+  film.filter_radius[0] = xw; film.filter_radius[1] = yw;
+  for (int y = 0; y < 16; ++y) {
+    float fy = ((float)y + 0.5f) * (yw / 16.0f);
+    for (int x = 0; x < 16; ++x) { float fx = ((float)x + 0.5f) * (xw / 16.0f); film.filter_table[y * 16 + x] = filter_eval(p->filter_kind, p->filter_params, fx, fy); }
+  }
+  film.max_sample_luminance = p->max_sample_luminance;
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  rt_frame* f = nullptr;
+  const int rc = rt_frame_begin_rays(s->dev, width, height, &film, &smp, &path, &shard, p->flags, table_budget_bytes, &f);
+  if (rc != RT_OK) return rc;
+  *out = new rtxh_frame{f};
+  return RT_OK;
+}
+int rtxh_frame_advance_rays(rtxh_frame* f, const float* rays, const float* p_film, int32_t n_samples, uint32_t flags, void* stream, rt_stats* stats) {
+  if (!f || !rays) return fail(RT_ERR_INVALID, "rtxh_frame_advance_rays: null frame or rays");
+  g_err.clear();
+  return rt_frame_advance_rays(f->f, rays, p_film, n_samples, flags, stream, stats);
+}
+int rtxh_frame_advance_rays_adaptive(rtxh_frame* f, const float* rays, const float* p_film, int32_t n_samples, float threshold, float floor_y, int32_t min_samples, uint32_t flags,
+                                     void* stream, rt_stats* stats) {
+  if (!f || !rays) return fail(RT_ERR_INVALID, "rtxh_frame_advance_rays_adaptive: null frame or rays");
+  g_err.clear();
+  return rt_frame_advance_rays_adaptive(f->f, rays, p_film, n_samples, threshold, floor_y, min_samples, flags, stream, stats);
+}
 // The replicas of the scene on `devices`: made on first use, kept while the device list and the commit stay the same.
 static int ensure_multi(rtxh_scene* s, const int32_t* devices, int32_t n_devices) {
   const std::vector<int32_t> want(devices, devices + n_devices);

@@ -1,5 +1,6 @@
 // rtx_raygen_rays.h — bounce 0 from caller-supplied rays (rt_render_rays): the producer that stands where k_raygen stands when a frame's first rays do not come
-// from the perspective camera. Included by rtx_rays.hip alone (launchers: rtx_rays_launch.h); k_raygen / k_raygen_masked (rtx_raygen_body.inl) are not touched.
+// from the perspective camera - and from the caller's rays AND film positions for the step of a ray frame (k_raygen_rays_film, at the end of the file).
+// Included by rtx_rays.hip alone (launchers: rtx_rays_launch.h); k_raygen / k_raygen_masked (rtx_raygen_body.inl) are not touched.
 #pragma once
 #include "rtx_kernels.h"
 
@@ -77,6 +78,54 @@ static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, Pass
   }
   for (int off = 32; off > 0; off >>= 1) n_camera += __shfl_down(n_camera, off);
   if ((threadIdx.x & 63u) == 0u && n_camera) atomicAdd(&ps.stats[ST_CAMERA], (unsigned long long)n_camera);
+}
+
+// ---- ray frames (rt_frame_begin_rays / rt_frame_advance_rays*): the step of a progressive frame whose rays and film positions come from the caller.
+// k_rays_scan for the step of a SHARDED ray frame: the same question asked of the rays of the rank's own rows only - the rows of other ranks are never read. One lane per
+// (owned pixel, sample of the step); fp.chunk_first is 0.
+static __global__ void __launch_bounds__(256) k_rays_scan_owned(FrameParams fp, const float* __restrict__ rays, unsigned long long owned_pixels, unsigned ray_ns,
+                                                                unsigned* __restrict__ any_skipped) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, n = owned_pixels * ray_ns;
+  bool skip = false;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned long long k = i / ray_ns;
+    int x, y; unsigned long long pixel_index; owned_pixel(fp, k, x, y, pixel_index);
+    skip |= !(rays[(pixel_index * ray_ns + (i - k * ray_ns)) * 8ull + 3ull] > 0.0f);
+  }
+  if (__ballot(skip) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(any_skipped, 1u);
+}
+// Bounce 0 of a ray frame's step (rtx_raygen_rays_film.inl): k_raygen_rays with the film position of every sample, and no per-sample output. ray_s0 / ray_ns: first
+// sample and samples per pixel of the STEP - rays and p_film hold [pixel_index][ray_ns] records.
+static __global__ void __launch_bounds__(256) k_raygen_rays_film(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, RT_SPTR_R(const float2) p_film, unsigned ray_s0,
+                                                                 unsigned ray_ns, unsigned ts_log2) {
+#include "rtx_raygen_rays_film.inl"
+}
+// ... of an adaptive step: a pixel whose byte is 0 takes none of the step's samples, and its rays are not read.
+static __global__ void __launch_bounds__(256) k_raygen_rays_film_masked(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, RT_SPTR_R(const float2) p_film,
+                                                                        unsigned ray_s0, unsigned ray_ns, unsigned ts_log2, const unsigned char* __restrict__ active) {
+#define RT_RAYGEN_RAYS_MASKED
+#include "rtx_raygen_rays_film.inl"
+#undef RT_RAYGEN_RAYS_MASKED
+}
+// rt_frame_read(RT_FRAME_SUMS): k_frame_resolve's walk - one lane per cropped pixel, film sum + the pixel's own sum where this shard owns its row - with the sums stored as
+// they are, (sum w L).rgb and the weight sum: no colour matrix, no division. A kernel of this translation unit, not a branch of frame_resolve_store, so that the code
+// object of rtx_hip.hip stays what it was.
+static __global__ void __launch_bounds__(256) k_frame_sums_read(FrameParams fp, const float4* __restrict__ film_acc, const float4* __restrict__ own_plane, float4* __restrict__ out,
+                                                                unsigned long long n) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned cw = (unsigned)(fp.crop_x1 - fp.crop_x0);
+  const int x = fp.crop_x0 + (int)(i % cw), y = fp.crop_y0 + (int)(i / cw);
+  float4 a = film_acc[i];
+  if (x >= fp.sb_x0 && x < fp.sb_x1 && y >= fp.sb_y0 && y < fp.sb_y1) {  // the inverse of owned_pixel
+    const unsigned long long row = (unsigned long long)(y - fp.sb_y0), band = row >> fp.shard_log2;
+    if (band % (unsigned long long)fp.world == (unsigned long long)fp.rank) {
+      const unsigned long long j = ((band / (unsigned long long)fp.world) << fp.shard_log2) + (row & ((1ull << fp.shard_log2) - 1ull));
+      const float4 o = own_plane[j * (unsigned long long)(fp.sb_x1 - fp.sb_x0) + (unsigned long long)(x - fp.sb_x0)];
+      a = make_float4(a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w);
+    }
+  }
+  out[i] = a;
 }
 
 }  // namespace rtx

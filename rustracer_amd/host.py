@@ -37,7 +37,7 @@ RT_SAMPLES_MAX = 1 << 27
 RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
 RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
 RT_QUERY_BSDF_LAUNCHED = 5# rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
-RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS, RT_FRAME_FEATURES = range(5)                                   # rt_frame_read: what
+RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS, RT_FRAME_FEATURES, RT_FRAME_SUMS = range(6)                    # rt_frame_read: what
 RT_FRAME_SAMPLES_DONE, RT_FRAME_SPP, RT_FRAME_TABLES_RESIDENT, RT_FRAME_STATE_BYTES, RT_FRAME_SAMPLES_TAKEN, RT_FRAME_ACTIVE_PIXELS = range(6)   # rt_frame_query: what
 BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, lambert=RT_BSDF_FRONT_LAMBERT, two_lobe=RT_BSDF_FRONT_TWO_LOBE,
                        two_lobe_wide=RT_BSDF_FRONT_TWO_LOBE_WIDE)
@@ -383,6 +383,15 @@ class HostScene:
         return ProgressiveFrame(self, rank=rank, world_size=world_size, table_budget=table_budget, count_traversal=count_traversal, time_kernels=time_kernels,
                                 pixel_stats=pixel_stats, features=features)
 
+    def progressive_rays(self, width, height, spp=None, max_depth=None, rank=0, world_size=1, table_budget=None, pixel_stats=False, features=False, count_traversal=False,
+                         time_kernels=False):
+        """A progressive frame over a `width` x `height` film whose steps take their rays and film positions from the caller (rt_frame_begin_rays): a RayFrame. The film
+        is `render_rays`' virtual film - pixel (x, y) draws the sampler values of pixel_index y * width + x - with the scene's pixel filter, max_sample_luminance and film
+        scale; no camera is set up. `spp` (default: the scene's sampler's) is the frame's sample count, `max_depth` defaults to the scene's integrator's. rank /
+        world_size, table_budget, pixel_stats and features as in `progressive`."""
+        return RayFrame(self, width, height, spp=spp, max_depth=max_depth, rank=rank, world_size=world_size, table_budget=table_budget, pixel_stats=pixel_stats,
+                        features=features, count_traversal=count_traversal, time_kernels=time_kernels)
+
     def progressive_multi(self, devices, table_budget=None, count_traversal=False, time_kernels=False, pixel_stats=False, features=False):
         """The frame of `progressive` across several GPUs of this process (rt_multi_frame_*): a MultiProgressiveFrame with the methods and properties of
         ProgressiveFrame whose read-outs are the merged frame, formed on devices[0]. One worker per entry of `devices` (an entry may repeat), worker k owns the
@@ -711,9 +720,85 @@ class ProgressiveFrame:
         """(H, W, 3) float32: Film::write_image's pixels (film_to_rgb of `film()`); `scale` defaults to the film's own."""
         return self._read(RT_FRAME_RGB, self.scale if scale is None else float(scale), 3, np.float32, device_out, stream)
 
+    def sums(self, device_out=None, stream=0):
+        """(H, W, 4) float32: the frame's sums as it holds them (RT_FRAME_SUMS) - (sum of w * L) rgb and the filter weight sum, before any colour arithmetic; `film()` is
+        these through the float32 RGB -> XYZ matrix. A frame on one device only."""
+        return self._read(RT_FRAME_SUMS, 1.0, 4, np.float32, device_out, stream)
+
     def display(self, scale=None, device_out=None, stream=0):
         """(H, W, 3) uint8: the pixels of `rgb()` through the PNG writer's sRGB quantisation (rgb_to_png8)."""
         return self._read(RT_FRAME_RGB8, self.scale if scale is None else float(scale), 3, np.uint8, device_out, stream)
+
+
+class RayFrame(ProgressiveFrame):
+    """A progressive frame whose steps take their rays and film positions from the caller (HostScene.progressive_rays; rt_frame_begin_rays / rt_frame_advance_rays*):
+    the film stage - pixel filter, clamp, read-outs, statistics, features, shards - for rays of any camera. `advance(rays, p_film=None)` renders the next n samples of
+    every pixel from `rays` (H, W, n, 8) float32 and splats each at `p_film` (H, W, n, 2) (None: the pixel centre); a ray whose t_max is not > 0 is skipped. Both may be
+    numpy arrays or contiguous torch device tensors (then both of them). Every read-out method and property is ProgressiveFrame's."""
+
+    def __init__(self, scene, width, height, spp=None, max_depth=None, rank=0, world_size=1, table_budget=None, pixel_stats=False, features=False, count_traversal=False,
+                 time_kernels=False):
+        L = lib()
+        L.rtxh_frame_end.argtypes = [C.c_void_p]
+        L.rtxh_frame_begin_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]
+        L.rtxh_frame_advance_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rtxh_frame_advance_rays_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        self.scene = scene   # (the frame's device state belongs to the scene's device: the scene must outlive it)
+        self.h = None
+        self.width, self.height = int(width), int(height)
+        p = scene._render_params(rank=rank, world_size=world_size)
+        if spp is not None:
+            p.spp = int(spp)
+        if max_depth is not None:
+            p.max_depth = int(max_depth)
+        p.flags = ((RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0) |
+                   (RT_FLAG_FRAME_FEATURES if features else 0))
+        self.scale = float(p.film_scale)
+        h = C.c_void_p()
+        _check(L.rtxh_frame_begin_rays(scene.h, C.byref(p), self.width, self.height, C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)), C.byref(h)),
+               "frame_begin_rays")
+        self.h = h
+
+    def _step_args(self, rays, p_film):
+        """(rays pointer, p_film pointer or None, n, flags, the arrays to keep alive over the call)"""
+        if self.h is None:
+            raise BackendError("the progressive frame is closed")
+        on_device = hasattr(rays, "data_ptr")
+        if p_film is not None and hasattr(p_film, "data_ptr") != on_device:
+            raise BackendError("ray frame: rays and p_film must both be numpy arrays or both be device tensors (RT_FLAG_FILM_ON_DEVICE names both pointers)")
+        if not on_device:
+            rays = np.ascontiguousarray(rays, np.float32)
+            if p_film is not None:
+                p_film = np.ascontiguousarray(p_film, np.float32)
+        if len(rays.shape) != 4 or tuple(rays.shape[:2]) != (self.height, self.width) or rays.shape[3] != 8:
+            raise BackendError(f"ray frame: rays must have shape ({self.height}, {self.width}, n, 8), not {tuple(rays.shape)}")
+        n = int(rays.shape[2])
+        if p_film is not None and tuple(p_film.shape) != (self.height, self.width, n, 2):
+            raise BackendError(f"ray frame: p_film must have shape ({self.height}, {self.width}, {n}, 2), not {tuple(p_film.shape)}")
+        if on_device:
+            for t in (rays,) + (() if p_film is None else (p_film,)):
+                if not t.is_contiguous() or t.element_size() != 4:
+                    raise BackendError("ray frame: device rays and p_film must be contiguous float32 tensors")
+            return C.c_void_p(rays.data_ptr()), (None if p_film is None else C.c_void_p(p_film.data_ptr())), n, RT_FLAG_FILM_ON_DEVICE, (rays, p_film)
+        return rays.ctypes.data_as(C.c_void_p), (None if p_film is None else p_film.ctypes.data_as(C.c_void_p)), n, 0, (rays, p_film)
+
+    def advance(self, rays, p_film=None, stream=0):
+        """Renders samples [samples_done, samples_done + n) of every pixel from `rays` (H, W, n, 8); returns the step's stats dict. n past the frame's spp is refused."""
+        pr, pp, n, flags, keep = RayFrame._step_args(self, rays, p_film)
+        stats = Stats()
+        _check(lib().rtxh_frame_advance_rays(self.h, pr, pp, C.c_int32(n), C.c_uint32(flags), C.c_void_p(stream), C.byref(stats)), "frame_advance_rays")
+        del keep
+        return stats.as_dict()
+
+    def advance_adaptive(self, rays, p_film, threshold, floor_y=0.0, min_samples=4, stream=0):
+        """ProgressiveFrame.advance_adaptive with the caller's rays (the frame needs pixel_stats=True): the rays of a pixel that is not active are passed over like
+        skipped rays. Returns the step's stats dict (camera_rays = samples taken)."""
+        pr, pp, n, flags, keep = RayFrame._step_args(self, rays, p_film)
+        stats = Stats()
+        _check(lib().rtxh_frame_advance_rays_adaptive(self.h, pr, pp, C.c_int32(n), C.c_float(threshold), C.c_float(floor_y), C.c_int32(int(min_samples)), C.c_uint32(flags),
+                                                      C.c_void_p(stream), C.byref(stats)), "frame_advance_rays_adaptive")
+        del keep
+        return stats.as_dict()
 
 
 class MultiProgressiveFrame(ProgressiveFrame):

@@ -1,6 +1,6 @@
 """What a ray frame costs beside the camera's frame (MEASUREMENTS "Ray frames").
 
-    python scripts/ray_frame_cost.py [--res N] [--spp N] [--rounds N] [--out results/ray_frame_cost.json]
+    python scripts/ray_frame_cost.py [--film] [--res N] [--spp N] [--rounds N] [--out results/ray_frame_cost.json]
 
 The benchmark's Cornell box cut to one RT_RAYS_MAX call (1024 x 1024 pixels x 128 samples = 2^27 rays by default). The camera's own rays are collected on the device
 (rt_render_sample_features, window by window, RT_FLAG_FILM_ON_DEVICE) and laid out as rt_render_rays takes them; then, interleaved for --rounds rounds after a warm-up
@@ -20,8 +20,62 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def film_mode(a, h, rays, out):
+    """--film: one step of a ray frame over all the call's samples (rt_frame_advance_rays, device-resident rays; p_film NULL, and an explicit device-resident p_film of
+    pixel centres) beside rt_render_rays over the same rays, interleaved for --rounds rounds after a warm-up of each: ms_total of the call, and - in rounds of their own
+    under RT_FLAG_TIME_KERNELS - ms_film and ms_raygen, medians. Every step is the first of a fresh frame begun with table_budget=1: its sampler tables are not resident,
+    so the step builds them inside the timed call as rt_render_rays does; rt_frame_begin_rays itself (allocation, zeroing) is outside it. With RTX_LIB_DIR naming a library from before ray frames (MEASUREMENTS "Ray frames with a film": the parent commit's), only
+    rt_render_rays is measured - run the two builds in alternating processes."""
+    import torch
+    from rustracer_amd import host
+    n, spp = a.res, a.spp
+    have_frames = hasattr(host.lib(), "rtxh_frame_begin_rays")
+    pf = None
+    if have_frames:
+        ys, xs = torch.meshgrid(torch.arange(n, dtype=torch.float32, device="cuda") + 0.5, torch.arange(n, dtype=torch.float32, device="cuda") + 0.5, indexing="ij")
+        pf = torch.stack([xs, ys], dim=-1)[:, :, None, :].expand(n, n, spp, 2).contiguous()
+
+    def rays_call(timed):
+        return h.render_rays(rays, device_out=out, time_kernels=timed)[1]
+
+    def step(p_film, timed):
+        with h.progressive_rays(n, n, spp=spp, table_budget=1, time_kernels=timed) as fr:
+            st = fr.advance(rays, p_film)
+            torch.cuda.synchronize()
+            return st
+
+    kinds = {"render_rays": rays_call}
+    if have_frames:
+        kinds["step"] = lambda timed: step(None, timed)
+        kinds["step_p_film"] = lambda timed: step(pf, timed)
+    for f in kinds.values():
+        f(False)
+    total = {k: [] for k in kinds}
+    film = {k: [] for k in kinds}
+    raygen = {k: [] for k in kinds}
+    for _ in range(a.rounds):
+        for k, f in kinds.items():
+            total[k].append(f(False)["ms_total"])
+    for _ in range(a.rounds):
+        for k, f in kinds.items():
+            st = f(True)
+            film[k].append(st["ms_film"]), raygen[k].append(st["ms_raygen"])
+    med = lambda v: float(np.median(v))
+    res = dict(mode="film", lib_dir=os.environ.get("RTX_LIB_DIR") or "", res=n, spp=spp, rays=n * n * spp, rounds=a.rounds,
+               ms_total={k: med(v) for k, v in total.items()}, ms_film={k: med(v) for k, v in film.items()}, ms_raygen={k: med(v) for k, v in raygen.items()},
+               all=dict(ms_total=total, ms_film=film, ms_raygen=raygen))
+    print(f"cornell {n}x{n}x{spp} = {n * n * spp} device-resident rays, medians of {a.rounds}: " +
+          "; ".join(f"{k} {res['ms_total'][k]:.2f} ms (ms_film {res['ms_film'][k]:.3f}, ms_raygen {res['ms_raygen'][k]:.3f})" for k in kinds))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--film", action="store_true", help="measure one ray-frame step (rt_frame_advance_rays, with and without p_film) beside rt_render_rays")
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=3)
@@ -54,6 +108,8 @@ def main():
     d.integrator.pixel_bounds = None
     torch.cuda.synchronize()
     out = torch.empty((n, n, spp, 4), dtype=torch.float32, device="cuda")
+    if a.film:
+        return film_mode(a, h, rays, out)
 
     def ray_frame(timed):
         t0 = time.perf_counter()

@@ -2,7 +2,7 @@
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
-                                  [--camera-model orthographic|environment [--seed N]]
+                                  [--camera-model orthographic|environment [--seed N] [--ray-frame]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -23,7 +23,10 @@ rt_frame_* (in one step unless --preview-every / --adaptive cut it; on --devices
 --camera-model orthographic|environment [--seed N]: the scene along the rays of a camera the reference does not have (rustracer_amd/cameras.py, pbrt-v3's definitions)
 through rt_render_rays, in place of the file's perspective camera - whose camera-to-world and screen window it keeps -: film positions pixel + 0.5 + a seeded jitter of
 the script's own, sample ranges of at most RT_RAYS_MAX rays, the radiance box-filtered (each pixel the mean of its own samples, scrubbed samples black). A choice of
-this command line, not a file directive: the loader refuses Camera "orthographic" / "environment" as the reference does."""
+this command line, not a file directive: the loader refuses Camera "orthographic" / "environment" as the reference does.
+--ray-frame (with --camera-model): the same rays and film positions through a ray frame (rt_frame_begin_rays / rt_frame_advance_rays*) - filtered on the device with the
+file's PixelFilter, clamp and film scale, no sample travels back. Honours --preview-every N (steps of N samples, the image rewritten after each), --adaptive T with
+--min-samples / --noise-floor / --sample-map, and --features; the PNG is RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights (RT_FRAME_SUMS). Without the flag --camera-model renders as before."""
 import argparse
 import os
 import sys
@@ -31,11 +34,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def render_camera_model(s, model, seed=0):
-    """The scene through `HostScene.render_rays` with a camera of rustracer_amd/cameras.py in place of the file's: returns (rgb [yres, xres, 3] float32 - the box-filtered
-    radiance, each pixel the mean of its own samples, scrubbed samples black as in the renderer -, stats summed over the calls). The camera takes the file's
-    camera-to-world and, orthographic, its "screenwindow" (pbrt's default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5)
-    from numpy's default_rng(seed); the samples go through in sample ranges of at most RT_RAYS_MAX rays."""
+def camera_model_samples(s, model, seed=0):
+    """The generator behind --camera-model: (w, h, spp, chunks) where `chunks` yields (s0, p_film [h, w, ns, 2] float64, rays [h, w, ns, 8] float32) for sample ranges
+    [s0, s0 + ns) of at most RT_RAYS_MAX rays that together are [0, spp). The camera takes the file's camera-to-world and, orthographic, its "screenwindow" (pbrt's
+    default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5) from numpy's default_rng(seed), drawn range after range."""
     import numpy as np
     from rustracer_amd import cameras, host
     p = s._render_params()
@@ -50,20 +52,76 @@ def render_camera_model(s, model, seed=0):
     if win == (0.0, 0.0, 0.0, 0.0):
         aspect = w / h
         win = (-aspect, aspect, -1.0, 1.0) if aspect > 1.0 else (-1.0, 1.0, -1.0 / aspect, 1.0 / aspect)
-    rng = np.random.default_rng(seed)
+
+    def chunks():
+        rng = np.random.default_rng(seed)
+        step = max(1, min(spp, host.RT_RAYS_MAX // (w * h)))
+        for s0 in range(0, spp, step):
+            ns = min(step, spp - s0)
+            p_film = cameras.pixel_centres(w, h, ns) + rng.uniform(-0.5, 0.5, (h, w, ns, 2))
+            rays = cameras.orthographic(c2w, win, w, h, p_film) if model == "orthographic" else cameras.environment(c2w, w, h, p_film)
+            yield s0, p_film, rays
+
+    return w, h, spp, chunks()
+
+
+def render_camera_model(s, model, seed=0):
+    """The scene through `HostScene.render_rays` with a camera of rustracer_amd/cameras.py in place of the file's: returns (rgb [yres, xres, 3] float32 - the box-filtered
+    radiance, each pixel the mean of its own samples, scrubbed samples black as in the renderer -, stats summed over the calls). The camera takes the file's
+    camera-to-world and, orthographic, its "screenwindow" (pbrt's default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5)
+    from numpy's default_rng(seed); the samples go through in sample ranges of at most RT_RAYS_MAX rays."""
+    import numpy as np
+    w, h, spp, chunks = camera_model_samples(s, model, seed)
     total = np.zeros((h, w, 3), np.float64)
     stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
-    step = max(1, min(spp, host.RT_RAYS_MAX // (w * h)))
-    for s0 in range(0, spp, step):
-        ns = min(step, spp - s0)
-        p_film = cameras.pixel_centres(w, h, ns) + rng.uniform(-0.5, 0.5, (h, w, ns, 2))
-        rays = cameras.orthographic(c2w, win, w, h, p_film) if model == "orthographic" else cameras.environment(c2w, w, h, p_film)
+    for s0, _, rays in chunks:
         rad, st = s.render_rays(rays, sample0=s0, spp=spp)
         ok = rad[..., 3:4] == 0.0
         total += np.where(ok, rad[..., :3], 0.0).sum(axis=2, dtype=np.float64)
         for k in stats:
             stats[k] += st[k]
-    return (total / spp * float(p.film_scale)).astype(np.float32), stats
+    return (total / spp * float(s._render_params().film_scale)).astype(np.float32), stats
+
+
+def frame_rgb(frame):
+    """The linear image of a frame from its own sums (RT_FRAME_SUMS): per pixel (sum of w * L) / (sum of w) in the radiance's RGB where the weight is not zero, max(0, .),
+    times the film scale - Film::write_image's pixel without the detour through XYZ that RT_FRAME_RGB takes (two float32 matrices, inverse to each other within 1e-6): the
+    box-filtered image is then the mean of a pixel's samples to float32 rounding, which is what `render_camera_model` returns."""
+    import numpy as np
+    a = frame.sums()
+    w = a[..., 3:4]
+    q = np.where(w != 0, np.maximum(a[..., :3] / np.where(w != 0, w, np.float32(1)), np.float32(0)), a[..., :3])
+    return (q * np.float32(frame.scale)).astype(np.float32)
+
+
+def render_camera_model_frame(s, model, seed=0, preview_every=0, adaptive=None, noise_floor=1e-3, min_samples=8, features=False, on_step=None):
+    """--camera-model --ray-frame: the same rays and film positions as `render_camera_model` draws for `seed`, through a ray frame (`HostScene.progressive_rays`) - the
+    film stage on the device, with the file's PixelFilter, max_sample_luminance and film scale instead of the numpy box filter. Steps of `preview_every` samples (0: a
+    whole sample range each; 4 under `adaptive`); `on_step(frame)` is called after each. `adaptive` = T: the steps are `advance_adaptive(.., T, noise_floor,
+    min_samples)` and end when no pixel is active. Returns dict(rgb [yres, xres, 3] float32 - `frame_rgb` -, png8 [yres, xres, 3] uint8 - RT_FRAME_RGB8 -, stats,
+    samples_done, samples_taken, spp, counts - the per-pixel sample counts, adaptive only -, features - [yres, xres, 8] where asked for)."""
+    import numpy as np
+    w, h, spp, chunks = camera_model_samples(s, model, seed)
+    stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
+    with s.progressive_rays(w, h, spp=spp, pixel_stats=adaptive is not None, features=features) as frame:
+        stopped = False
+        for s0, p_film, rays in chunks:
+            ns = rays.shape[2]
+            step = preview_every if preview_every > 0 else (4 if adaptive is not None else ns)
+            for a in range(0, ns, step):
+                r, pf = np.ascontiguousarray(rays[:, :, a:a + step]), np.ascontiguousarray(p_film[:, :, a:a + step], np.float32)
+                st = frame.advance(r, pf) if adaptive is None else frame.advance_adaptive(r, pf, adaptive, noise_floor, min_samples)
+                for k in stats:
+                    stats[k] += st[k]
+                if adaptive is not None and frame.active_pixels == 0:
+                    stopped = True
+                    break
+                if on_step is not None:
+                    on_step(frame)
+            if stopped:
+                break
+        return dict(rgb=frame_rgb(frame), png8=frame.display(), stats=stats, samples_done=frame.samples_done, samples_taken=frame.samples_taken, spp=spp,
+                    counts=frame.pixel_stats()[0] if adaptive is not None else None, features=frame.features() if features else None)
 
 
 def main():
@@ -73,6 +131,8 @@ def main():
     ap.add_argument("--camera-model", choices=["orthographic", "environment"], default=None,
                     help="render along the rays of this camera (rt_render_rays) instead of the file's perspective camera; box-filtered")
     ap.add_argument("--seed", type=int, default=0, help="with --camera-model: seed of the film-position jitter")
+    ap.add_argument("--ray-frame", action="store_true",
+                    help="with --camera-model: filter the samples on the device through a ray frame (rt_frame_advance_rays) with the file's PixelFilter, in steps")
     ap.add_argument("scene")
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
@@ -99,6 +159,37 @@ def main():
     out = a.out or s.film_filename
     if not out.endswith((".pfm", ".png")):
         raise SystemExit("Unsupported file format")   # rc/imageio.rs:47-49 (EXR output is not written here)
+    if a.ray_frame and not a.camera_model:
+        raise SystemExit("--ray-frame goes with --camera-model")
+    if a.camera_model and a.ray_frame:
+        import numpy as np
+        if a.devices:
+            raise SystemExit("--ray-frame renders on one device")
+
+        def put(rgb, png8):
+            if out.endswith(".pfm"):
+                write_pfm(out, rgb)
+            else:
+                write_png(out, png8, 2, 8, filters=(1,))
+
+        def preview(frame):
+            put(frame_rgb(frame), frame.display())
+            print(f"{out}: {frame.samples_done} / {frame.spp} samples per pixel" + (f", {frame.active_pixels} pixels active" if a.adaptive is not None else ""), flush=True)
+
+        r = render_camera_model_frame(s, a.camera_model, a.seed, preview_every=a.preview_every, adaptive=a.adaptive, noise_floor=a.noise_floor, min_samples=a.min_samples,
+                                      features=bool(a.features), on_step=preview if a.preview_every > 0 else None)
+        put(r["rgb"], r["png8"])
+        if a.adaptive is not None:
+            full = int(np.count_nonzero(r["counts"])) * r["spp"]
+            print(f"{out}: {r['samples_taken']} samples taken / {full} of the full frame ({r['samples_taken'] / max(full, 1):.3f}), stopped after {r['samples_done']} of {r['spp']} indices")
+            if a.sample_map:
+                np.save(a.sample_map, r["counts"])
+        if a.features:
+            np.save(a.features, r["features"])
+            print(f"{a.features}: {r['features'].shape[1]}x{r['features'].shape[0]} x (albedo rgb, normal xyz, depth, coverage), mean coverage {float(r['features'][..., 7].mean()):.3f}")
+        stats = r["stats"]
+        print(f"{out}: {r['rgb'].shape[1]}x{r['rgb'].shape[0]}, {a.camera_model} camera through a ray frame, {stats['camera_rays']} rays, {stats['paths_scrubbed']} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
+        return
     if a.camera_model:
         rgb, stats = render_camera_model(s, a.camera_model, a.seed)
         if out.endswith(".pfm"):
