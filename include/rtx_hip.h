@@ -285,6 +285,8 @@ typedef struct rt_stats {
 #define RT_FLAG_FRAME_STATS 32u /* rt_frame_begin only (other entry points ignore it): the frame keeps per-pixel luminance moments and accepts rt_frame_advance_adaptive */
 #define RT_FLAG_FRAME_FEATURES 64u /* rt_frame_begin / rt_multi_frame_begin only (other entry points ignore it): the frame keeps per-pixel sums of its samples' first-hit features
                                       (albedo, normal, depth, coverage), read with RT_FRAME_FEATURES */
+#define RT_FLAG_RAY_DIFFERENTIALS 128u /* rt_render_rays, rt_frame_advance_rays, rt_frame_advance_rays_adaptive, rt_camera_rays (other entry points ignore it): a ray record is
+                                          RT_RAY_DIFF_FLOATS floats - the eight of rt_render_rays, then the ray's differentials rx_o.xyz, ry_o.xyz, rx_d.xyz, ry_d.xyz */
 
 typedef struct rt_scene rt_scene;
 
@@ -444,12 +446,19 @@ int rt_render_sample_features(rt_scene* scene, const rt_camera* camera, const rt
  * leaves them (cur_1d = 1, cur_2d = 2: what a camera would have consumed is unused). sampler->spp, rounded up to a power of two, sizes the tables, and
  * [sample0, sample0 + n_samples) must lie inside [0, spp): a job of more than RT_RAYS_MAX rays is cut by sample range, and the calls together are the one call, bit for bit.
  * So the camera rays rt_render_sample_features reports of a film with a box filter of radius 0.5, fed back in with t_max = inf, give the radiance rt_render_samples reports.
- * The rays carry no differentials (Ray { differential: None }): every derivative of the first vertex is zero, as at every later vertex (interaction.rs:245-314), and image
- * maps are looked up at zero filter width.
+ * Without RT_FLAG_RAY_DIFFERENTIALS the rays carry no differentials (Ray { differential: None }): every derivative of the first vertex is zero, as at every later vertex
+ * (interaction.rs:245-314), and image maps are looked up at zero filter width.
+ * RT_FLAG_RAY_DIFFERENTIALS: a record is RT_RAY_DIFF_FLOATS (20) floats - the eight above, then rx_o.xyz, ry_o.xyz, rx_d.xyz, ry_d.xyz: Ray::differential's rx_origin,
+ * ry_origin, rx_direction, ry_direction (ray.rs) in world space, USED AS GIVEN - the caller applies scale_differentials (1 / sqrt(spp) in the reference's renderer) itself.
+ * They enter compute_differential (interaction.rs:245-314) at the first vertex only; later vertices have none, as in PathIntegrator::li. So MIP maps are filtered,
+ * closed-form checkerboards antialiased, fbm octaves clamped and bump maps given footprints as in a camera frame: rt_camera_rays' records of a film with a box filter of
+ * radius 0.5 give the radiance rt_render_samples reports on a textured scene too. A record whose twelve differential floats are zero behaves exactly as a ray without
+ * differentials (compute_differential returns early on the division by zero), and on a scene that reads none (RT_QUERY_NEEDS_DIFFERENTIALS == 0) the fields are never read:
+ * the result is the unflagged call's, bit for bit. The flag costs 48 more bytes per ray of upload and three 16-byte loads per camera vertex.
  * A ray whose t_max is not > 0 (zero, negative, NaN) is SKIPPED: radiance (0, 0, 0, 2.0), nothing consumed, not counted in stats->camera_rays. One scan of the rays on the
  * device decides the route of the call: none skipped - the route of a frame whose pixel_bounds crop nothing, else that of a cropped one. Same radiance either way.
  * path: max_depth, rr_threshold and light_strategy as in rt_render (the light distribution is built by the first call that needs it); pixel_bounds is ignored.
- * flags: RT_FLAG_FILM_ON_DEVICE - rays AND radiance are device pointers; RT_FLAG_COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED as in rt_render_samples (ms_raygen: the
+ * flags: RT_FLAG_FILM_ON_DEVICE - rays AND radiance are device pointers; RT_FLAG_RAY_DIFFERENTIALS - records of 20 floats; RT_FLAG_COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED as in rt_render_samples (ms_raygen: the
  * scan and the kernel that reads the rays). Refused with RT_ERR_INVALID before any device work: a NULL scene, rays, sampler, path or radiance; width, height or
  * n_samples <= 0; sample0 < 0 or sample0 + n_samples > the rounded spp; width * height * n_samples > RT_RAYS_MAX; spp > 16384; dimensions outside [2, 8];
  * RT_FLAG_REF_STREAM. Single device. */
@@ -457,6 +466,20 @@ int rt_render_sample_features(rt_scene* scene, const rt_camera* camera, const rt
 int rt_render_rays(rt_scene* scene, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples,
                    const rt_sampler_desc* sampler, const rt_path_desc* path, uint32_t flags, void* stream,
                    float* radiance, rt_stats* stats /* may be NULL */);
+
+/* The perspective camera's rays, as a camera frame generates them - what k_raygen and bounce 0's shade kernels compute - for samples [sample0, sample0 + n_samples) of every
+ * pixel of the film's sample bounds (W x H pixels, pixel_index = row * W + column): for a caller who bends them (lens distortion, a stereo offset, a rolling shutter) and
+ * feeds them to rt_render_rays or a ray frame, and as the exact source of the camera's differentials.
+ *   rays    [H][W][n_samples][8] floats - o.xyz, t_max = inf, d.xyz, 0 - or [..][RT_RAY_DIFF_FLOATS] with RT_FLAG_RAY_DIFFERENTIALS: then rx_o, ry_o, rx_d, ry_d as
+ *           PerspectiveCamera::generate_ray_differential leaves them after scale_differentials(1 / sqrt(spp)), spp rounded up to a power of two;
+ *   p_film  [H][W][n_samples][2] floats, or NULL: the film position of each sample (pixel + the pixel-keyed sampler's 2D#0; the lens sample is 2D#1).
+ * The first 8 floats of a record are the same with and without the flag, and calls over sample ranges that add up to a range give that range's call. With
+ * RT_FLAG_FILM_ON_DEVICE both outputs are device pointers; any other flag bit is refused. Refused with RT_ERR_INVALID and a message before any device work: a NULL scene,
+ * camera, film, sampler or rays; an empty film; n_samples <= 0, sample0 < 0 or sample0 + n_samples > the rounded spp; more than RT_RAYS_MAX rays; spp > 16384;
+ * dimensions outside [2, 8]. Single device. */
+#define RT_RAY_DIFF_FLOATS 20
+int rt_camera_rays(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler,
+                   int32_t sample0, int32_t n_samples, uint32_t flags, void* stream, float* rays, float* p_film /* may be NULL */);
 
 /* Progressive frames: the frame of rt_render rendered in steps, with the film readable between them. The reference's CLI offers "display image as it is
  * rendered" (-p / --display); it has no checkpoint or resume. The pixel-keyed sampler makes sample s of pixel p the same whichever call renders it, so a frame
@@ -539,20 +562,22 @@ void rt_frame_end(rt_frame* frame);
  *   _COUNT_AS_RENDERED act per step. Refused with RT_ERR_INVALID before any device work: a NULL out, scene, sampler or path; width or height <= 0; width * height >
  *   RT_RAYS_MAX; spp > 16384; dimensions outside [2, 8]; a bad shard; a filter radius > 8 or not > 0; RT_FLAG_REF_STREAM.
  * rt_frame_advance_rays renders samples [done, done + n_samples) of every owned pixel:
- *   rays    [height][width][n_samples][8] floats, rt_render_rays' record, for exactly those samples;
+ *   rays    [height][width][n_samples][8] floats, rt_render_rays' record, for exactly those samples - [..][RT_RAY_DIFF_FLOATS] with RT_FLAG_RAY_DIFFERENTIALS;
  *   p_film  [height][width][n_samples][2] floats: the raster position each sample is splatted at (FilmTile::add_sample), or NULL: the pixel centre (x + 0.5, y + 0.5).
  *   The position is used as given. A sample whose position lies in its own pixel goes into the pixel's own sum in sample-index order, as in rt_frame_advance: with the
  *   camera's rays and positions the film is the camera frame's, bit for bit. A position elsewhere is legal; what it adds to other pixels - like every tap of a wide
  *   filter outside the sample's pixel - reaches the film through float atomics, so those sums are fixed only up to the order of the additions.
  *   A ray whose t_max is not > 0 (zero, negative, NaN) is SKIPPED, as in rt_render_rays: not traced, not splatted, not counted in the moments' n, the feature plane's n or
  *   camera_rays - the way to mask pixels (outside a fisheye circle, say). The one scan of the step's rays that picks the route of its passes is rt_render_rays'.
- *   flags: RT_FLAG_FILM_ON_DEVICE - rays and p_film are device pointers; any other bit is RT_ERR_INVALID. RT_ERR_INVALID before any device work: a NULL frame or rays;
+ *   flags: RT_FLAG_FILM_ON_DEVICE - rays and p_film are device pointers; RT_FLAG_RAY_DIFFERENTIALS - the records carry the rays' differentials, with rt_render_rays'
+ *   semantics: with rt_camera_rays' records and positions a textured scene's film, statistics and feature planes are the camera frame's, bit for bit; any other bit is RT_ERR_INVALID. RT_ERR_INVALID before any device work: a NULL frame or rays;
  *   a frame begun with rt_frame_begin; n_samples <= 0; done + n_samples > spp (rounded) - the caller's array fixes the count, so it is refused, not clamped;
  *   width * height * n_samples > RT_RAYS_MAX. A finished frame: RT_OK, zeroed stats. rt_frame_advance / _advance_adaptive on a ray frame are RT_ERR_INVALID as well.
  * rt_frame_advance_rays_adaptive: rt_frame_advance_adaptive's decision - per pixel, from the moments plane as it stands, before any path work - with the caller's rays:
  *   the rays of an inactive pixel are passed over like skipped rays (and not read). Needs RT_FLAG_FRAME_STATS; threshold, floor_y and min_samples as there.
  *   RT_FRAME_ACTIVE_PIXELS and RT_FRAME_SAMPLES_TAKEN behave as for a camera frame.
- * rt_frame_read, rt_frame_query and rt_frame_end work unchanged on a ray frame. The rays carry no differentials (see rt_render_rays). Single device per frame. */
+ * rt_frame_read, rt_frame_query and rt_frame_end work unchanged on a ray frame. The rays of a step without RT_FLAG_RAY_DIFFERENTIALS carry no differentials (see
+ * rt_render_rays); the flag is per step. Single device per frame. */
 int rt_frame_begin_rays(rt_scene* scene, int32_t width, int32_t height, const rt_film_desc* film /* may be NULL */, const rt_sampler_desc* sampler, const rt_path_desc* path,
                         const rt_shard* shard /* may be NULL */, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out);
 int rt_frame_advance_rays(rt_frame* frame, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, uint32_t flags, void* stream,
@@ -610,7 +635,8 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
        RT_QUERY_BSDF_LAUNCHED = 5 /* the kernel the scene's last rt_bsdf_eval launched: 1 + 2 * mode + const_tex (mode 0 generic, 3 Lambert, 5 two-lobe, 6 two-lobe wide;
                                      const_tex 1: its constant-texture form), 0 before the first call */,
        RT_QUERY_NEEDS_DIFFERENTIALS = 6 /* 1 if some texture or bump map of the scene reads ray differentials (image maps, closed-form checkerboards, fbm): the shade kernels
-                                           then regenerate the camera ray's at bounce 0 - in the frames of a camera, never in rt_render_rays' */ };
+                                           then regenerate the camera ray's at bounce 0 in the frames of a camera, and load the caller's from the ray records in a call or ray-frame step with
+                                           RT_FLAG_RAY_DIFFERENTIALS; without the flag caller-supplied rays have none */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

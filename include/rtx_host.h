@@ -148,12 +148,18 @@ int rtxh_render_samples(rtxh_scene*, const rtxh_render_params*, void* hip_stream
 /* The first-hit features of the same window's samples (rt_render_sample_features in rtx_hip.h): features: pixels x spp x RT_FEATURE_FLOATS floats; a host pointer, or a
  * device pointer with RT_FLAG_FILM_ON_DEVICE. Window and set-up as for rtxh_render_samples; more than RT_FEATURE_SAMPLES_MAX samples are refused. */
 int rtxh_render_sample_features(rtxh_scene*, const rtxh_render_params*, void* hip_stream, float* features);
-/* Path-traced radiance along the caller's rays (rt_render_rays in rtx_hip.h): rays height x width x n_samples x 8 floats (o.xyz, t_max, d.xyz, unused), radiance
+/* Path-traced radiance along the caller's rays (rt_render_rays in rtx_hip.h): rays height x width x n_samples x 8 floats (o.xyz, t_max, d.xyz, unused) - x
+ * RT_RAY_DIFF_FLOATS (then rx_o, ry_o, rx_d, ry_d) with RT_FLAG_RAY_DIFFERENTIALS among the parameters' flags -, radiance
  * height x width x n_samples x 4; host pointers, or both device pointers with RT_FLAG_FILM_ON_DEVICE. Of the parameters only the sampler (spp, sampler_dims), the
  * integrator (max_depth, rr_threshold, light_strategy) and the flags are read: no camera or film is set up. Sizes rt_render_rays refuses are refused before the scene
  * is uploaded for it. */
 int rtxh_render_rays(rtxh_scene*, const rtxh_render_params*, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, void* hip_stream,
                      float* radiance, rt_stats* stats);
+/* The camera's rays of the frame rtxh_render would render (rt_camera_rays in rtx_hip.h): camera and film are set up as for rtxh_render; samples [sample0, sample0 +
+ * n_samples) of every pixel of the film's sample bounds (H x W pixels). rays: H x W x n_samples x 8 floats, or x RT_RAY_DIFF_FLOATS with RT_FLAG_RAY_DIFFERENTIALS in
+ * `flags`; p_film: H x W x n_samples x 2 or NULL; device pointers with RT_FLAG_FILM_ON_DEVICE. Of the parameters' own flags none is read. Sizes rt_camera_rays refuses are
+ * refused before the scene is uploaded for it. */
+int rtxh_camera_rays(rtxh_scene*, const rtxh_render_params*, int32_t sample0, int32_t n_samples, uint32_t flags, void* hip_stream, float* rays, float* p_film /* may be NULL */);
 /* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
  * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
  * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */
@@ -170,7 +176,7 @@ void rtxh_frame_end(rtxh_frame*);
  * (height x width x n_samples x 8 floats) and film positions (height x width x n_samples x 2, or NULL: pixel centres) from the caller. Of the parameters the sampler, the
  * integrator, the pixel filter (filter_kind, filter_params), max_sample_luminance, rank / world_size and the flags are read: no camera is set up, and xres / yres, crop
  * and pixel bounds are ignored. Sizes rt_frame_begin_rays refuses are refused before the scene is uploaded for it. flags of a step: RT_FLAG_FILM_ON_DEVICE - rays and
- * p_film are device pointers. The frame is read, queried and ended with rtxh_frame_read / _query / _end. */
+ * p_film are device pointers. RT_FLAG_RAY_DIFFERENTIALS - records of RT_RAY_DIFF_FLOATS floats. The frame is read, queried and ended with rtxh_frame_read / _query / _end. */
 int rtxh_frame_begin_rays(rtxh_scene*, const rtxh_render_params*, int32_t width, int32_t height, uint64_t table_budget_bytes, rtxh_frame** out);
 int rtxh_frame_advance_rays(rtxh_frame*, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, uint32_t flags, void* hip_stream,
                             rt_stats* stats /* of this step, may be NULL */);

@@ -154,6 +154,7 @@ static void fill_ewa_lut() {
   }
   (void)hipMemcpyToSymbol(HIP_SYMBOL(kEwaLut), lut, sizeof(lut));
   rtx_shade_set_ewa_lut(lut);  // the shade kernels' translation unit has a copy of its own
+  rtx_shade_rays_set_ewa_lut(lut);  // ... and so has k_shade_rays'
   rtx_ref_set_ewa_lut(lut);    // ... and the reference-stream kernel's
 }
 
@@ -1048,18 +1049,24 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // frame launches either kernel.
 // Caller-supplied rays: ray_src != NULL - the frame of rt_render_rays, a samples frame (samples_rad is its radiance, [pixel][sample of the call]) over the virtual film
 // `film` whose bounce 0 comes from k_raygen_rays instead of k_raygen: samples [sample0, sample0 + n_samples) of every pixel, no camera, and no differentials - every
-// launch gets the scene record with needs_differentials = 0. One scan of the rays (k_rays_scan) before the first pass decides the route of all passes: no ray skipped -
+// launch gets the scene record with needs_differentials = 0 - unless the records carry them (RaySource::rec_floats, below). One scan of the rays (k_rays_scan) before the first pass decides the route of all passes: no ray skipped -
 // all_in_bounds, as a frame whose pixel_bounds crop nothing; else the sharded bounce-0 queue of a cropped one. Everything after ray generation is the samples frame's.
 // ray_src != NULL together with fr != NULL: the step of a RAY FRAME (rt_frame_advance_rays*) - samples [fr->done, step_end) of every owned pixel, sample0 = fr->done and
 // n_samples = step_end - fr->done, bounce 0 from k_raygen_rays_film (k_raygen_rays_film_masked under active_mask), which also hands each sample's film position
 // (ray_src->p_film, or the pixel centre) to ps.pfilm; everything after ray generation is the frame step's - its film kernel, its feature kernels, its resident tables.
 // A shard stages and scans the rays of its own rows only. on_device: rays and p_film are device pointers (rt_render_rays: RT_FLAG_FILM_ON_DEVICE of the call).
-struct RaySource { const float* rays; unsigned sample0, n_samples; const float* p_film; bool on_device; };
+// rec_floats: floats per ray record - 8, or RT_RAY_DIFF_FLOATS (RT_FLAG_RAY_DIFFERENTIALS of the call or step): the record's last twelve floats are the ray's differentials
+// rx_o, ry_o, rx_d, ry_d. On a scene that reads differentials the launches then KEEP the scene's needs_differentials, and bounce 0's shade launches go through
+// k_shade_rays (rtx_shade_rays.hip), whose camera vertices load the differentials of their ray's record; every later bounce launches what it launches without the flag.
+// cam_out != NULL: rt_camera_rays - no path work at all: the batches, passes and sampler tables of a samples frame over the film's sample bounds, each pass handing the
+// camera's rays of samples [sample0, sample0 + n_samples) to k_camera_rays ([pixel][sample of the call] records of rec_floats floats, film positions where asked for).
+struct RaySource { const float* rays; unsigned sample0, n_samples; const float* p_film; bool on_device; unsigned rec_floats; };
+struct CamRaysOut { float* rays; float* p_film; unsigned sample0, n_samples, rec_floats; };
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
                         rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr,
-                        const RaySource* ray_src = nullptr) {
-  const bool rays = ray_src != nullptr;
+                        const RaySource* ray_src = nullptr, const CamRaysOut* cam_out = nullptr) {
+  const bool rays = ray_src != nullptr, camrays = cam_out != nullptr;
   const bool samples = samples_rad != nullptr;
   const bool fsamples = samples_feat != nullptr, features = fsamples || (fr && fr->features);
   // the window of rt_render_samples: pixel_bounds inside the sample bounds, and its size - checked before any device work
@@ -1067,6 +1074,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   const int wx1 = std::min(path->pixel_bounds[2], film->sample_bounds[2]), wy1 = std::min(path->pixel_bounds[3], film->sample_bounds[3]);
   unsigned long long n_window_samples = 0;
   if (rays) n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * ray_src->n_samples;  // (rt_render_rays checked the size: the call's samples, not spp)
+  else if (camrays) n_window_samples = (unsigned long long)(wx1 - wx0) * (unsigned long long)(wy1 - wy0) * cam_out->n_samples;  // (rt_camera_rays checked it: the window is the sample bounds)
   else if (samples) {
     if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_samples: the reference-stream frame has no per-sample output");
     if (wx1 <= wx0 || wy1 <= wy0) return fail(RT_ERR_INVALID, "rt_render_samples: pixel_bounds and the film's sample bounds share no pixel");
@@ -1122,7 +1130,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
 
   // integrator.preprocess (renderer.rs:30)
   tm.begin(&stats.ms_lightdist);
-  int rc = build_light_distribution(s, path->light_strategy, stream);
+  int rc = camrays ? RT_OK : build_light_distribution(s, path->light_strategy, stream);  // (rt_camera_rays traces nothing)
   if (rc != RT_OK) return rc;
   tm.end();
 
@@ -1193,7 +1201,9 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
 
   const bool resident = fr && fr->resident;                   // the sampler tables of every batch live in the frame ...
   const bool build_tables = !(resident && fr->tables_built);  // ... and are built by its first step only
-  const unsigned s_begin = fr ? fr->done : (rays ? ray_src->sample0 : 0u), s_end = fr ? step_end : (rays ? ray_src->sample0 + ray_src->n_samples : spp);  // the samples this call renders
+  const unsigned s_begin = fr ? fr->done : (rays ? ray_src->sample0 : (camrays ? cam_out->sample0 : 0u));  // the samples this call renders
+  const unsigned s_end = fr ? step_end : (rays ? ray_src->sample0 + ray_src->n_samples : (camrays ? cam_out->sample0 + cam_out->n_samples : spp));
+  const unsigned rec_floats = rays ? ray_src->rec_floats : (camrays ? cam_out->rec_floats : 8u);  // floats per ray record of the caller's array
   unsigned long long batch_pixels = 0, chunk_pixels = 0, cap = 0, lead_pixels = 0; unsigned pass_samples = 0, shard_cap = 0; bool multi_batch = false; size_t n_slots = 0;
   static const char* lead_env = getenv("RTX_LEAD_BATCH");  // measurement knob (round 4), see lead_pixels below: 1 always, 0 never, unset: at 1024 spp
   const bool lead_on = lead_env ? lead_env[0] == '1' : spp == 1024u;
@@ -1231,7 +1241,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         {&s->ws[B_SH], cap * 48}, {&s->ws[B_MI], cap * 100}, {&s->ws[B_OCCSH], cap}, {&s->ws[B_OCCMI], cap}, {&s->ws[B_HITMASK], shade_split ? (size_t)((cap + 63) / 64) * 8 : 16},
         {&s->ws[B_QSH], szq}, {&s->ws[B_QMI], szq}, {&s->ws[B_QMA], has_infinite ? szq : 16},
         {&s->counters, counter_words * 4}, {&s->stats, (size_t)ST_COUNT * 8}};
-    if (!fr && !fsamples && !rays) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
+    if (!fr && !fsamples && !rays && !camrays) { want.push_back({&s->film_acc, (size_t)cw * ch * 16}); want.push_back({&s->own_acc, (size_t)chunk_pixels * 16}); want.push_back({&s->filter_table, 1024}); }  // (a progressive frame has its own)
     if (!resident) { want.push_back({&s->scrambles[0], (size_t)chunk_pixels * 3 * dims * 4}); want.push_back({&s->perms[0], (size_t)(chunk_pixels * table_bytes_per_pixel)}); }
     if (build_tables) want.push_back({&s->sampler_plan.partners, (size_t)(chunk_pixels * table_bytes_per_pixel)});
     if (use_bins) { want.push_back({&s->bin_words, (size_t)(fp.max_depth + 1) * bin_stride * 4}); want.push_back({&s->bin_sorted, (size_t)cap * 4}); want.push_back({&s->bin_at, (size_t)cap * 2}); }
@@ -1239,11 +1249,12 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     if (features && !fsamples) want.push_back({&s->feat, cap * 32});
     if (!(flags & RT_FLAG_FILM_ON_DEVICE) && !fr) {
       if (fsamples) want.push_back({&s->samples_feat, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4});
+      else if (camrays) { want.push_back({&s->rays_in, (size_t)n_window_samples * rec_floats * 4}); if (cam_out->p_film) want.push_back({&s->pfilm_in, (size_t)n_window_samples * 8}); }  // (staged for the copy to the host)
       else if (!samples) want.push_back({&s->film_out, (size_t)cw * ch * 16});
       else { want.push_back({&s->samples_rad, (size_t)n_window_samples * 16}); if (samples_pf) want.push_back({&s->samples_pf, (size_t)n_window_samples * 8}); }
     }
     if (rays && !ray_src->on_device) {
-      want.push_back({&s->rays_in, (size_t)n_window_samples * 32});
+      want.push_back({&s->rays_in, (size_t)n_window_samples * rec_floats * 4});
       if (fr && ray_src->p_film) want.push_back({&s->pfilm_in, (size_t)n_window_samples * 8});
     }
     if (rays) want.push_back({&s->rays_skipped, 16});
@@ -1268,28 +1279,33 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   float4* const d_out = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)film_xyzw : s->film_out.as<float4>();
   float4* const d_samples_rad = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)samples_rad : s->samples_rad.as<float4>();
   float2* const d_samples_pf = !samples_pf ? nullptr : ((flags & RT_FLAG_FILM_ON_DEVICE) ? (float2*)samples_pf : s->samples_pf.as<float2>());
+  float4* const d_cam_rays = !camrays ? nullptr : ((flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)cam_out->rays : s->rays_in.as<float4>());
+  float2* const d_cam_pf = !(camrays && cam_out->p_film) ? nullptr : ((flags & RT_FLAG_FILM_ON_DEVICE) ? (float2*)cam_out->p_film : s->pfilm_in.as<float2>());
   FeatureOut fo{};
   if (fsamples) { fo.samples = (flags & RT_FLAG_FILM_ON_DEVICE) ? (float4*)samples_feat : s->samples_feat.as<float4>(); fo.wx0 = wx0; fo.wy0 = wy0; fo.ww = wx1 - wx0; }
   else if (features) { fo.nd = s->feat.as<float4>(); fo.ah = fo.nd + cap; }
-  if (!samples && !fsamples && !fr) {  // (no kernel of a samples frame reads the filter table or the film sums; a progressive frame keeps its own)
+  if (!samples && !fsamples && !fr && !camrays) {  // (no kernel of a samples frame reads the filter table or the film sums; a progressive frame keeps its own)
     HIP_TRY(hipMemcpyAsync(s->filter_table.p, film->filter_table, 1024, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)cw * ch * 16, stream));
   }
   HIP_TRY(hipMemsetAsync(s->stats.p, 0, ST_COUNT * 8, stream));
   // A ray frame: the caller's rays in device memory, and the one scan that picks the route of its passes (timed with ray generation). Its launches take the scene
-  // record with needs_differentials cleared (DScene travels by value): the rays are Ray { differential: None }, every derivative stays zero (interaction.rs:245-314).
+  // record with needs_differentials cleared (DScene travels by value): the rays are Ray { differential: None }, every derivative stays zero (interaction.rs:245-314) -
+  // unless the records carry differentials (ray_diff: RT_FLAG_RAY_DIFFERENTIALS on a scene that reads them), which bounce 0's shade kernels then load (k_shade_rays).
+  const bool ray_diff = rays && rec_floats == (unsigned)RT_RAY_DIFF_FLOATS && s->d.needs_differentials != 0;
   const float4* d_rays = nullptr;
   const float2* d_pfilm = nullptr;  // (a ray frame's film positions; NULL: pixel centres)
   DScene dsc_rays;
   if (rays) {
-    dsc_rays = s->d; dsc_rays.needs_differentials = 0;
+    dsc_rays = s->d; if (!ray_diff) dsc_rays.needs_differentials = 0;
+    const size_t rec_bytes = (size_t)rec_floats * 4;
     if (ray_src->on_device) { d_rays = (const float4*)ray_src->rays; d_pfilm = fr ? (const float2*)ray_src->p_film : nullptr; }
-    else if (!fr) { HIP_TRY(hipMemcpyAsync(s->rays_in.p, ray_src->rays, (size_t)n_window_samples * 32, hipMemcpyHostToDevice, stream)); d_rays = s->rays_in.as<float4>(); }
+    else if (!fr) { HIP_TRY(hipMemcpyAsync(s->rays_in.p, ray_src->rays, (size_t)n_window_samples * rec_bytes, hipMemcpyHostToDevice, stream)); d_rays = s->rays_in.as<float4>(); }
     else {  // a ray frame: the rows the rank owns (bands of `band` rows, every world-th one), at their place in the whole array
       const size_t row_rays = (size_t)W * ray_src->n_samples;
       for (int r0 = rank * band; r0 < H; r0 += world * band) {
         const size_t first = (size_t)r0 * row_rays, n = (size_t)(std::min(r0 + band, H) - r0) * row_rays;
-        HIP_TRY(hipMemcpyAsync((char*)s->rays_in.p + first * 32, (const char*)ray_src->rays + first * 32, n * 32, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync((char*)s->rays_in.p + first * rec_bytes, (const char*)ray_src->rays + first * rec_bytes, n * rec_bytes, hipMemcpyHostToDevice, stream));
         if (ray_src->p_film) HIP_TRY(hipMemcpyAsync((char*)s->pfilm_in.p + first * 8, (const char*)ray_src->p_film + first * 8, n * 8, hipMemcpyHostToDevice, stream));
       }
       d_rays = s->rays_in.as<float4>(); d_pfilm = ray_src->p_film ? s->pfilm_in.as<float2>() : nullptr;
@@ -1300,10 +1316,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       if (fr && world > 1) {
         const unsigned long long n_owned = owned_pixels * ray_src->n_samples;
         rtx_launch_rays_scan_owned((unsigned)std::min<unsigned long long>((n_owned + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, fp, (const float*)d_rays, owned_pixels,
-                                   ray_src->n_samples, s->rays_skipped.as<unsigned>());
+                                   ray_src->n_samples, rec_floats, s->rays_skipped.as<unsigned>());
       } else
         rtx_launch_rays_scan((unsigned)std::min<unsigned long long>((n_window_samples + 255ull) / 256ull, (unsigned long long)s->n_cu * 8ull), stream, (const float*)d_rays, n_window_samples,
-                             s->rays_skipped.as<unsigned>());
+                             rec_floats, s->rays_skipped.as<unsigned>());
       tm.end();
       HIP_TRY(hipGetLastError());
       unsigned any_skipped = 0;
@@ -1413,15 +1429,24 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       static const bool tail_off = env_is("RTX_DEAD_TAIL", '0');  // measurement knob: cast the rays nothing reads as well
       ps.skip_dead_tail = (!tail_off && (!count || (flags & RT_FLAG_COUNT_AS_RENDERED))) ? 1 : 0;
       const int skip_dead_tail = ps.skip_dead_tail;
+      if (camrays) {  // rt_camera_rays: the pass's camera rays, handed out instead of traced
+        if (build_tables) for (int g = 1; g < 3; ++g) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][g], 0));  // (no bounce waits for the later groups: the call returns with every table built)
+        tm.begin(&stats.ms_raygen);
+        rtx_launch_camera_rays(pgrid, stream, fp, ps, cam_out->sample0, cam_out->n_samples, rec_floats / 4u, d_cam_rays, d_cam_pf);
+        tm.end();
+        stats.n_passes += 1;
+        HIP_TRY(hipGetLastError());
+        continue;
+      }
       tm.begin(&stats.ms_raygen);
       if (rays && fr) {  // the step of a ray frame: k_raygen_rays' tiles, and the film positions (masked in an adaptive step)
         unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
-        rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, d_rays, d_pfilm, ray_src->sample0, ray_src->n_samples, ts_log2, active_mask);
+        rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, d_rays, d_pfilm, ray_src->sample0, ray_src->n_samples, rec_floats / 4u, ts_log2, active_mask);
       }
       else if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
       else if (rays) {  // tiles of 2^(8 - ts) pixels x 2^ts samples, ts = log2(min(16, the pass's samples rounded up))
         unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
-        rtx_launch_raygen_rays(pgrid, stream, fp, ps, d_rays, ray_src->sample0, ray_src->n_samples, ts_log2, d_samples_rad);
+        rtx_launch_raygen_rays(pgrid, stream, fp, ps, d_rays, ray_src->sample0, ray_src->n_samples, rec_floats / 4u, ts_log2, d_samples_rad);
       }
       else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
       tm.end();
@@ -1439,7 +1464,10 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
         launch_trace<false>(s, count, io_path, ps.cnt_in, ps.cnt_in, ps.shard_cap, ps.cap, dstats, ST_RAYS_CLOSEST, ST_NODES_CLOSEST, ST_TRIS_CLOSEST, stream);
         tm.end();
         if (bounce <= 1 && build_tables) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][bounce + 1], 0));  // table groups 1 / 2: first read by the shade launches of bounce 0 / 1
-#define RT_SHADE(MODE, P) stats.launches_shade += 1, launch_shade<MODE>(gshade, lean_shade, bounce >= 1, sgrid, sblock, stream, dsc, fp, P, qlights, lds_shade)
+        // (a call or step whose rays carry differentials: bounce 0 through k_shade_rays, the plain / GENERAL form of the same front-end that loads them from the caller's records)
+        const RayDiffSrc rdiff{d_rays, rays ? ray_src->sample0 : 0u, rays ? ray_src->n_samples : 0u, rec_floats / 4u};
+#define RT_SHADE(MODE, P) stats.launches_shade += 1, ((ray_diff && bounce == 0) ? rtx_launch_shade_rays(MODE, gshade, sgrid, sblock, stream, dsc, fp, P, rdiff) \
+                                                                                 : launch_shade<MODE>(gshade, lean_shade, bounce >= 1, sgrid, sblock, stream, dsc, fp, P, qlights, lds_shade))
         if (s->lambert_only) {
           tm.begin(&stats.ms_shade_lambert_const);
           if (split_launch) rtx_launch_shade_split(bounce == 0, sgrid, stream, dsc, fp, ps, io_path.hit_mask);
@@ -1517,6 +1545,11 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
     }
   } else if (fsamples) {
     if (!(flags & RT_FLAG_FILM_ON_DEVICE)) HIP_TRY(hipMemcpyAsync(samples_feat, fo.samples, (size_t)n_window_samples * RT_FEATURE_FLOATS * 4, hipMemcpyDeviceToHost, stream));
+  } else if (camrays) {
+    if (!(flags & RT_FLAG_FILM_ON_DEVICE)) {
+      HIP_TRY(hipMemcpyAsync(cam_out->rays, d_cam_rays, (size_t)n_window_samples * rec_floats * 4, hipMemcpyDeviceToHost, stream));
+      if (cam_out->p_film) HIP_TRY(hipMemcpyAsync(cam_out->p_film, d_cam_pf, (size_t)n_window_samples * 8, hipMemcpyDeviceToHost, stream));
+    }
   } else if (!samples) {
     tm.begin(&stats.ms_film);
     {
@@ -1589,8 +1622,33 @@ extern "C" int rt_render_rays(rt_scene* s, const float* rays, int32_t width, int
   film.filter_radius[0] = film.filter_radius[1] = 0.5f; film.max_sample_luminance = std::numeric_limits<float>::infinity();
   rt_path_desc p = *path;  // pixel_bounds is ignored: every ray with t_max > 0 is traced
   p.pixel_bounds[0] = p.pixel_bounds[1] = 0; p.pixel_bounds[2] = width; p.pixel_bounds[3] = height;
-  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
   return render_frame(s, &cam, &film, smp, &p, nullptr, flags, stream_, nullptr, stats_out, radiance, nullptr, nullptr, 0, nullptr, false, nullptr, &src);
+}
+// The perspective camera's rays (and film positions) of samples [sample0, sample0 + n_samples) of every pixel of the film's sample bounds, as a camera frame generates
+// them: render_frame's batches, passes and sampler tables, k_camera_rays per pass, no path work.
+extern "C" int rt_camera_rays(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, int32_t sample0, int32_t n_samples, uint32_t flags,
+                              void* stream_, float* rays, float* p_film) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  if (!s || !cam || !film || !smp || !rays) return fail(RT_ERR_INVALID, "rt_camera_rays: null argument");
+  if (flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_RAY_DIFFERENTIALS))
+    return fail(RT_ERR_INVALID, "rt_camera_rays: the flags of the call are RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers) and RT_FLAG_RAY_DIFFERENTIALS");
+  const long long W = (long long)film->sample_bounds[2] - film->sample_bounds[0], H = (long long)film->sample_bounds[3] - film->sample_bounds[1];
+  const long long cw = (long long)film->cropped_pixel_bounds[2] - film->cropped_pixel_bounds[0], ch = (long long)film->cropped_pixel_bounds[3] - film->cropped_pixel_bounds[1];
+  if (W <= 0 || H <= 0 || cw <= 0 || ch <= 0) return fail(RT_ERR_INVALID, "rt_camera_rays: empty film");
+  if (smp->spp > 16384) return fail(RT_ERR_INVALID, "rt_camera_rays: spp > 16384 unsupported");
+  if (smp->dimensions < 2 || smp->dimensions > 8) return fail(RT_ERR_INVALID, "rt_camera_rays: sampler dimensions must be in [2, 8]");
+  const long long spp_r = (long long)next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
+  if (n_samples <= 0 || sample0 < 0 || (long long)sample0 + (long long)n_samples > spp_r)
+    return fail(RT_ERR_INVALID, "rt_camera_rays: [sample0, sample0 + n_samples) must be a non-empty range inside [0, spp)");
+  if ((unsigned long long)W * (unsigned long long)H > (unsigned long long)RT_RAYS_MAX ||
+      (unsigned long long)W * (unsigned long long)H * (unsigned long long)n_samples > (unsigned long long)RT_RAYS_MAX)
+    return fail(RT_ERR_INVALID, "rt_camera_rays: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+  if (!rt_device_available()) return fail(RT_ERR_NO_DEVICE, "rt_camera_rays: no HIP device visible; this backend has no CPU fallback");
+  rt_path_desc p{};  // no path is traced; pixel_bounds = the sample bounds: every sample of the film gets its ray
+  memcpy(p.pixel_bounds, film->sample_bounds, 16);
+  const CamRaysOut out{rays, p_film, (unsigned)sample0, (unsigned)n_samples, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
+  return render_frame(s, cam, film, smp, &p, nullptr, flags & RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, nullptr, nullptr, &out);
 }
 
 // ---------------------------------------------------------------------------------------------- progressive frames
@@ -1758,7 +1816,8 @@ extern "C" int rt_frame_begin_rays(rt_scene* s, int32_t width, int32_t height, c
 // What both advance calls refuse, in two halves: the pointers, the flags and the kind of frame ...
 static int frame_rays_kind_check(const char* who, rt_frame* fr, const float* rays, uint32_t flags) {
   if (!fr || !rays) return fail(RT_ERR_INVALID, std::string(who) + ": null frame or rays");
-  if (flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE) return fail(RT_ERR_INVALID, std::string(who) + ": the only flag of a step is RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers)");
+  if (flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_RAY_DIFFERENTIALS))
+    return fail(RT_ERR_INVALID, std::string(who) + ": the flags of a step are RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers) and RT_FLAG_RAY_DIFFERENTIALS (records of 20 floats)");
   if (!fr->ray_frame) return fail(RT_ERR_INVALID, std::string(who) + ": the frame was begun with a camera (rt_frame_begin): it takes its steps from rt_frame_advance / _adaptive");
   return RT_OK;
 }
@@ -1780,7 +1839,7 @@ extern "C" int rt_frame_advance_rays(rt_frame* fr, const float* rays, const floa
   if (rc != RT_OK) return rc;
   if (finished) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }
   const unsigned end = fr->done + (unsigned)n_samples;
-  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
+  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
   rt_stats st{};
   rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, &st, nullptr, nullptr, fr, end, nullptr,
                     false, nullptr, &src);
@@ -1801,7 +1860,7 @@ extern "C" int rt_frame_advance_rays_adaptive(rt_frame* fr, const float* rays, c
   rc = frame_rays_count_check(who, fr, n_samples, &finished);
   if (rc != RT_OK) return rc;
   if (finished) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }
-  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0};
+  const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
   return frame_adaptive_step(fr, fr->done + (unsigned)n_samples, threshold, floor_y, min_samples, stream, stats_out, &src);
 }
 static size_t frame_read_bytes(int32_t what) {  // bytes per cropped pixel of a read-out

@@ -1328,6 +1328,24 @@ int rtxh_render_rays(rtxh_scene* s, const rtxh_render_params* p, const float* ra
   if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_render_rays(s->dev, rays, width, height, sample0, n_samples, &smp, &path, p->flags, stream, radiance, stats);
 }
+// The camera's rays of the frame rtxh_render would render (rt_camera_rays): camera and film exactly as rtxh_render sets them up.
+int rtxh_camera_rays(rtxh_scene* s, const rtxh_render_params* p, int32_t sample0, int32_t n_samples, uint32_t flags, void* stream, float* rays, float* p_film) {
+  if (!s || !p || !rays) return fail(RT_ERR_INVALID, "rtxh_camera_rays: null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  {  // the sizes rt_camera_rays refuses, before the scene is uploaded for it
+    long long spp = 1; while (spp < (long long)std::max(p->spp, 1)) spp <<= 1;
+    const long long W = (long long)cf.film.sample_bounds[2] - cf.film.sample_bounds[0], H = (long long)cf.film.sample_bounds[3] - cf.film.sample_bounds[1];
+    if (W <= 0 || H <= 0) return fail(RT_ERR_INVALID, "rtxh_camera_rays: empty film");
+    if (n_samples <= 0 || sample0 < 0 || (long long)sample0 + (long long)n_samples > spp) return fail(RT_ERR_INVALID, "rtxh_camera_rays: [sample0, sample0 + n_samples) must be a non-empty range inside [0, spp)");
+    if ((unsigned long long)W * (unsigned long long)H > (unsigned long long)RT_RAYS_MAX / (unsigned long long)n_samples)
+      return fail(RT_ERR_INVALID, "rtxh_camera_rays: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+    if (flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_RAY_DIFFERENTIALS)) return fail(RT_ERR_INVALID, "rtxh_camera_rays: the flags are RT_FLAG_FILM_ON_DEVICE and RT_FLAG_RAY_DIFFERENTIALS");
+  }
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_camera_rays(s->dev, &cf.cam, &cf.film, &smp, sample0, n_samples, flags, stream, rays, p_film);
+}
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
 int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {

@@ -166,6 +166,10 @@ enum { ST_CAMERA = 0, ST_RAYS_CLOSEST, ST_RAYS_SHADOW, ST_RAYS_MIS, ST_NODES_CLO
 #define RT_STAMP(k) do { } while (0)
 #endif
 
+// The caller's ray records of a call or ray-frame step with RT_FLAG_RAY_DIFFERENTIALS, as bounce 0's shade kernels (k_shade_rays) read them: device memory,
+// [pixel_index][ray_ns] records of rec4 float4 (5 = RT_RAY_DIFF_FLOATS / 4), ray_s0 the first sample of the array. A kernel argument of its own, not part of PassState.
+struct RayDiffSrc { const float4* rays; unsigned ray_s0, ray_ns, rec4; };
+
 // path id = local sample * n_pixels + batch pixel. q = mulhi(pid, floor(2^32 / n)) is floor(pid / n) or one less: one compare fixes it (an integer division is
 // ~30 instructions, twice per path vertex otherwise).
 RT_DEV void split_path_id(const PassState& ps, unsigned pid, unsigned& sl, unsigned& pix) {

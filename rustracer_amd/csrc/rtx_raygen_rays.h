@@ -1,6 +1,7 @@
 // rtx_raygen_rays.h — bounce 0 from caller-supplied rays (rt_render_rays): the producer that stands where k_raygen stands when a frame's first rays do not come
 // from the perspective camera - and from the caller's rays AND film positions for the step of a ray frame (k_raygen_rays_film, at the end of the file).
-// Included by rtx_rays.hip alone (launchers: rtx_rays_launch.h); k_raygen / k_raygen_masked (rtx_raygen_body.inl) are not touched.
+// And k_camera_rays, rt_camera_rays' kernel: the perspective camera's rays handed out. Included by rtx_rays.hip alone (launchers: rtx_rays_launch.h); k_raygen /
+// k_raygen_masked (rtx_raygen_body.inl) are not touched.
 #pragma once
 #include "rtx_kernels.h"
 
@@ -8,10 +9,10 @@ namespace rtx {
 
 // Does any ray of the call carry a t_max that is not > 0 (zero, negative, NaN: the ray is skipped)? One scan of the rays before the first pass, one word read back:
 // the answer picks the route of every pass - none skipped: PassState::all_in_bounds with the fresh records, else the sharded bounce-0 queue of a cropped frame.
-static __global__ void __launch_bounds__(256) k_rays_scan(const float* __restrict__ rays, unsigned long long n_rays, unsigned* __restrict__ any_skipped) {
+static __global__ void __launch_bounds__(256) k_rays_scan(const float* __restrict__ rays, unsigned long long n_rays, unsigned rec_floats, unsigned* __restrict__ any_skipped) {
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   bool skip = false;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_rays; i += stride) skip |= !(rays[i * 8ull + 3ull] > 0.0f);
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_rays; i += stride) skip |= !(rays[i * rec_floats + 3ull] > 0.0f);
   if (__ballot(skip) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(any_skipped, 1u);
 }
 
@@ -21,12 +22,13 @@ static __global__ void __launch_bounds__(256) k_rays_scan(const float* __restric
 // into LDS, and after a barrier every lane takes the ray of ITS path id, so that the record stores of a wave are the runs of neighbouring slots k_raygen's are.
 // ts_log2 = log2(min(16, the pass's samples rounded up to a power of two)), tp_log2 = 8 - ts_log2.
 // What it writes per ray is what rtx_raygen_body.inl writes per camera sample: lacc (zero | RT_STATE_OUT_OF_BOUNDS for a skipped ray), pfilm (the pixel centre: nothing
-// reads it, a ray frame shades with DScene::needs_differentials = 0), the ray at its slot with the caller's t_max in o.w, the throughput and state records unless the pass
+// reads it - the shade launches of caller-supplied rays rebuild no camera ray: no differentials, or the caller's, k_shade_rays), the ray at its slot with the caller's t_max in o.w, the throughput and state records unless the pass
 // leaves them out (PassState::fresh), the shard push where rays are skipped, and ST_CAMERA. A skipped ray (t_max not > 0) gets no slot and its answer right here:
 // rad[ray] = (0, 0, 0, 2.0) - k_sample_store passes over samples marked out of bounds.
-// ray_s0 / ray_ns: first sample and samples per pixel of the CALL (the pass renders [ps.s0, ps.s0 + ps.n_samples) of them).
-static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, unsigned ray_s0, unsigned ray_ns, unsigned ts_log2,
-                                                            float4* __restrict__ rad) {
+// ray_s0 / ray_ns: first sample and samples per pixel of the CALL (the pass renders [ps.s0, ps.s0 + ps.n_samples) of them). rec4: float4 per record of the caller's array - 2,
+// or 5 with RT_FLAG_RAY_DIFFERENTIALS; the kernel reads the first two of each (k_rays_scan / k_rays_scan_owned: rec_floats = 4 * rec4).
+static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, unsigned ray_s0, unsigned ray_ns, unsigned rec4,
+                                                            unsigned ts_log2, float4* __restrict__ rad) {
   __shared__ float4 s_ray[512 + 256];  // [tile pixel][2 * TS + 1]: one float4 of padding per pixel row
   const unsigned tp_log2 = 8u - ts_log2, TS = 1u << ts_log2, TP = 1u << tp_log2, row = 2u * TS + 1u;
   const unsigned n_ptiles = (ps.n_pixels + TP - 1u) >> tp_log2, n_stiles = (ps.n_samples + TS - 1u) >> ts_log2, n_tiles = n_ptiles * n_stiles;
@@ -40,7 +42,7 @@ static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, Pass
       const unsigned pix = pix0 + lp, sl = sl0 + (within >> 1);
       if (pix < ps.n_pixels && sl < ps.n_samples) {
         int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
-        s_ray[lp * row + within] = rays[(size_t)((pixel_index * ray_ns + (ps.s0 + sl - ray_s0)) * 2ull + (within & 1u))];
+        s_ray[lp * row + within] = rays[(size_t)((pixel_index * ray_ns + (ps.s0 + sl - ray_s0)) * rec4 + (within & 1u))];
       }
     }
     __syncthreads();
@@ -84,28 +86,55 @@ static __global__ void __launch_bounds__(256) k_raygen_rays(FrameParams fp, Pass
 // k_rays_scan for the step of a SHARDED ray frame: the same question asked of the rays of the rank's own rows only - the rows of other ranks are never read. One lane per
 // (owned pixel, sample of the step); fp.chunk_first is 0.
 static __global__ void __launch_bounds__(256) k_rays_scan_owned(FrameParams fp, const float* __restrict__ rays, unsigned long long owned_pixels, unsigned ray_ns,
-                                                                unsigned* __restrict__ any_skipped) {
+                                                                unsigned rec_floats, unsigned* __restrict__ any_skipped) {
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, n = owned_pixels * ray_ns;
   bool skip = false;
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const unsigned long long k = i / ray_ns;
     int x, y; unsigned long long pixel_index; owned_pixel(fp, k, x, y, pixel_index);
-    skip |= !(rays[(pixel_index * ray_ns + (i - k * ray_ns)) * 8ull + 3ull] > 0.0f);
+    skip |= !(rays[(pixel_index * ray_ns + (i - k * ray_ns)) * rec_floats + 3ull] > 0.0f);
   }
   if (__ballot(skip) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(any_skipped, 1u);
 }
 // Bounce 0 of a ray frame's step (rtx_raygen_rays_film.inl): k_raygen_rays with the film position of every sample, and no per-sample output. ray_s0 / ray_ns: first
 // sample and samples per pixel of the STEP - rays and p_film hold [pixel_index][ray_ns] records.
 static __global__ void __launch_bounds__(256) k_raygen_rays_film(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, RT_SPTR_R(const float2) p_film, unsigned ray_s0,
-                                                                 unsigned ray_ns, unsigned ts_log2) {
+                                                                 unsigned ray_ns, unsigned rec4, unsigned ts_log2) {
 #include "rtx_raygen_rays_film.inl"
 }
 // ... of an adaptive step: a pixel whose byte is 0 takes none of the step's samples, and its rays are not read.
 static __global__ void __launch_bounds__(256) k_raygen_rays_film_masked(FrameParams fp, PassState ps, RT_SPTR_R(const float4) rays, RT_SPTR_R(const float2) p_film,
-                                                                        unsigned ray_s0, unsigned ray_ns, unsigned ts_log2, const unsigned char* __restrict__ active) {
+                                                                        unsigned ray_s0, unsigned ray_ns, unsigned rec4, unsigned ts_log2, const unsigned char* __restrict__ active) {
 #define RT_RAYGEN_RAYS_MASKED
 #include "rtx_raygen_rays_film.inl"
 #undef RT_RAYGEN_RAYS_MASKED
+}
+// rt_camera_rays: the perspective camera's rays of a pass, handed out instead of traced - what k_raygen computes per camera sample (film position from 2D#0, lens
+// sample from 2D#1, generate_camera_ray with differentials scaled by 1 / sqrt(spp)) and, with rec4 = 5, the differentials bounce 0's shade kernels would rebuild from it.
+// One lane per (pixel, sample) with the SAMPLE running fastest: lane i of the pass takes pixel i / n_samples, local sample i % n_samples, so consecutive lanes store
+// consecutive records of the caller's [pixel_index][ray_ns] array. ray_s0 / ray_ns: first sample and samples per pixel of the CALL. p_film may be NULL.
+static __global__ void __launch_bounds__(256) k_camera_rays(FrameParams fp, PassState ps, unsigned ray_s0, unsigned ray_ns, unsigned rec4, float4* __restrict__ rays,
+                                                            float2* __restrict__ p_film_out) {
+  const Tables tb = tables_of(ps);
+  const unsigned stride = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < ps.cap; i += stride) {  // (ps.cap = n_pixels * n_samples <= 2^31 - 1)
+    const unsigned pix = i / ps.n_samples, sl = i - pix * ps.n_samples, s = ps.s0 + sl;
+    int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
+    const f2 o = table_2d(tb, pix, 0, s);
+    const f2 p_film = mk2((float)x + o.x, (float)y + o.y);
+    const f2 p_lens = fp.lens_radius > 0.0f ? table_2d(tb, pix, 1, s) : mk2(0.0f, 0.0f);
+    const CameraRay cr = generate_camera_ray(fp, p_film, p_lens, 1.0f / sqrtf((float)ps.spp));
+    const size_t rec = (size_t)(pixel_index * ray_ns + (s - ray_s0));  // (< RT_RAYS_MAX: checked by rt_camera_rays)
+    float4* r = rays + rec * rec4;
+    r[0] = make_float4(cr.o.x, cr.o.y, cr.o.z, kInf);
+    r[1] = make_float4(cr.d.x, cr.d.y, cr.d.z, 0.0f);
+    if (rec4 == 5u) {
+      r[2] = make_float4(cr.rx_o.x, cr.rx_o.y, cr.rx_o.z, cr.ry_o.x);
+      r[3] = make_float4(cr.ry_o.y, cr.ry_o.z, cr.rx_d.x, cr.rx_d.y);
+      r[4] = make_float4(cr.rx_d.z, cr.ry_d.x, cr.ry_d.y, cr.ry_d.z);
+    }
+    if (p_film_out) p_film_out[rec] = make_float2(p_film.x, p_film.y);
+  }
 }
 // rt_frame_read(RT_FRAME_SUMS): k_frame_resolve's walk - one lane per cropped pixel, film sum + the pixel's own sum where this shard owns its row - with the sums stored as
 // they are, (sum w L).rgb and the weight sum: no colour matrix, no division. A kernel of this translation unit, not a branch of frame_resolve_store, so that the code

@@ -23,7 +23,7 @@
 #endif
       if (take) {
         int x, y; unsigned long long pixel_index; owned_pixel(fp, fp.chunk_first + pix, x, y, pixel_index);
-        s_ray[lp * row + within] = rays[(size_t)((pixel_index * ray_ns + (ps.s0 + sl - ray_s0)) * 2ull + (within & 1u))];
+        s_ray[lp * row + within] = rays[(size_t)((pixel_index * ray_ns + (ps.s0 + sl - ray_s0)) * rec4 + (within & 1u))];
       }
     }
     if (has_pf) {  // ... and its film positions: one float2 per lane

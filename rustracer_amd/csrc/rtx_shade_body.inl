@@ -1,7 +1,8 @@
 // The body of the shade kernels (rtx_shade_kernels.h includes it in k_shade<...> and in k_shade_split<SPLIT>). Shared as text, not as a function, like rtx_raygen_body.inl:
 // the kernels' LDS arrays are then function-scope statics of each KERNEL, under the names they had, and k_shade<...> compiles to the code it had before the split kernels
 // existed (as a __device__ template the same text gave k_shade<1, .., 1> and k_shade<1, .., 3> two more spilled dwords each: the arrays' names order the LDS layout).
-// Expects: MODE, GENERAL, LEAN, BOUNCED, QLIGHTS, LDSREC, SPLIT (constants), sc, fp, ps (the kernel's arguments) and hit_mask (the split kernels' argument, else NULL).
+// Expects: MODE, GENERAL, LEAN, BOUNCED, QLIGHTS, LDSREC, SPLIT (constants), sc, fp, ps (the kernel's arguments) and hit_mask (the split kernels' argument, else NULL);
+// RAYDIFF (constant) and rdiff (RayDiffSrc): k_shade_rays takes a camera vertex's differentials from the caller's ray records; false and unread in every other kernel.
   static_assert(SPLIT == RT_SPLIT_NONE || (MODE == 1 && LDSREC == 1), "the split kernels are forms of k_shade<1, .., LDSREC = 1>");
   // LDSREC (MODE 1, round 5): a scene of <= RT_SMALL_TRIS triangles and <= RT_LDS_LIGHTS emitters keeps its shade records, traversal records and light table in LDS
   // for the launch. k_shade<1> is busy issuing VALU instructions half of the time and waits for memory two thirds of a wave's life (SQ counters), yet neither ~10 % fewer
@@ -115,10 +116,18 @@
       }
       if (found && bounces < fp.max_depth) {  // path.rs:139
         if ((MODE != 1 && !LEAN && !BOUNCED) && bounces == 0 && sc.needs_differentials && !RT_DBG(sc, 16)) {  // only the camera ray carries differentials (interaction.rs:245-314)
+          if constexpr (RAYDIFF) {  // k_shade_rays: the differentials the caller's record of this ray carries (floats 8 - 19: rx_o, ry_o, rx_d, ry_d), used as given
+            int rx_, ry_; unsigned long long rpix; owned_pixel(fp, fp.chunk_first + pix, rx_, ry_, rpix);
+            const float4* r = rdiff.rays + (size_t)((rpix * rdiff.ray_ns + (s - rdiff.ray_s0)) * rdiff.rec4) + 2;
+            const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+            const f3 rx_o = mk3(r0.x, r0.y, r0.z), ry_o = mk3(r0.w, r1.x, r1.y), rx_d = mk3(r1.z, r1.w, r2.x), ry_d = mk3(r2.y, r2.z, r2.w);
+            if (MODE == 0) compute_differential_call(si, rx_o, ry_o, rx_d, ry_d); else compute_differential(si, rx_o, ry_o, rx_d, ry_d);
+          } else {
           f2 pf; { float2 t = pfilm_[pid]; pf = mk2(t.x, t.y); }
           const f2 pl = fp.lens_radius > 0.0f ? table_2d(smp.tb, pix, 1, s) : mk2(0.0f, 0.0f);
           CameraRay cr = generate_camera_ray(fp, pf, pl, 1.0f / sqrtf((float)ps.spp));
           if (MODE == 0) compute_differential_call(si, cr.rx_o, cr.ry_o, cr.rx_d, cr.ry_d); else compute_differential(si, cr.rx_o, cr.ry_o, cr.rx_d, cr.ry_d);
+          }
         }
         typename std::conditional<MODE == 1, SingleLambert, typename std::conditional<MODE == 3, SingleLambertT<!LEAN, BOUNCED>,
                                   typename std::conditional<MODE == 5, SmallBsdfT<false, LEAN>, typename std::conditional<MODE == 6, SmallBsdfT<true, LEAN>, GenericBsdf>::type>::type>::type>::type bsdf;

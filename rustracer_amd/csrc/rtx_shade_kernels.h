@@ -1,4 +1,4 @@
-// rtx_shade_kernels.h - K3: the shade kernel k_shade<MODE, ...> and its Bsdf front-ends (split from rtx_kernels.h in round 6; compiled by rtx_shade.hip only).
+// rtx_shade_kernels.h - K3: the shade kernel k_shade<MODE, ...> and its Bsdf front-ends (split from rtx_kernels.h in round 6; compiled by rtx_shade.hip, and by rtx_shade_rays.hip for k_shade_rays).
 #pragma once
 #include "rtx_kernels.h"
 
@@ -344,6 +344,7 @@ RT_DEV auto instance_interaction_visit(const DScene& sc, unsigned hit_id, f3 o, 
 template <int MODE, bool GENERAL = false, bool LEAN = false, bool BOUNCED = false, bool QLIGHTS = false, int LDSREC = 0>
 __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN || BOUNCED) ? (BOUNCED ? RT_SHADE_BOUNCED_MIN_WAVES : RT_SHADE_LEAN_MIN_WAVES) : RT_SHADE_MIN_WAVES) : (MODE == 3 && !GENERAL ? RT_SHADE3_MIN_WAVES : ((MODE == 5 || MODE == 6) && !GENERAL ? RT_SHADE56_MIN_WAVES : (MODE != 0 && GENERAL ? RT_SHADE_GEN_MIN_WAVES : RT_SHADE0_MIN_WAVES)))) k_shade(DScene sc, FrameParams fp, PassState ps) {
   constexpr int SPLIT = RT_SPLIT_NONE; const unsigned long long* const hit_mask = nullptr;
+  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{};
 #include "rtx_shade_body.inl"
 }
 // The two kernels of such a frame: the same body under the same four-wave bound, hit_mask = the words the bounce's k_trace launch wrote.
@@ -356,6 +357,15 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
 template <int SPLIT>
 __global__ void __launch_bounds__(256, RT_SHADE_MIN_WAVES) k_shade_split(DScene sc, FrameParams fp, PassState ps, const unsigned long long* __restrict__ hit_mask) {
   constexpr int MODE = 1, LDSREC = 1; constexpr bool GENERAL = false, LEAN = false, BOUNCED = false, QLIGHTS = false;
+  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{};
+#include "rtx_shade_body.inl"
+}
+// Bounce 0 of a call or ray-frame step whose rays carry differentials (RT_FLAG_RAY_DIFFERENTIALS, rtx_shade_rays.hip): the plain / GENERAL, LDSREC = 0 form of k_shade<MODE>
+// under its launch bound, with the one site that builds a camera vertex's differentials reading them from the caller's record of the vertex's ray (RayDiffSrc) instead
+// of regenerating the perspective camera's. MODE 0, 3, 5, 6: the forms that can see a camera vertex and read differentials.
+template <int MODE, bool GENERAL>
+__global__ void __launch_bounds__(256, MODE == 3 && !GENERAL ? RT_SHADE3_MIN_WAVES : ((MODE == 5 || MODE == 6) && !GENERAL ? RT_SHADE56_MIN_WAVES : (MODE != 0 && GENERAL ? RT_SHADE_GEN_MIN_WAVES : RT_SHADE0_MIN_WAVES))) k_shade_rays(DScene sc, FrameParams fp, PassState ps, RayDiffSrc rdiff) {
+  constexpr int SPLIT = RT_SPLIT_NONE, LDSREC = 0; constexpr bool LEAN = false, BOUNCED = false, QLIGHTS = false, RAYDIFF = true; const unsigned long long* const hit_mask = nullptr;
 #include "rtx_shade_body.inl"
 }
 

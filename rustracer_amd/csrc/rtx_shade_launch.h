@@ -13,6 +13,10 @@ void rtx_launch_shade_split(bool camera, unsigned grid, hipStream_t stream, cons
 // k_feature_hits (first-hit features: it builds the interaction with the shade kernels' fill routines, so it lives beside them)
 void rtx_launch_feature_hits(bool samples, bool general, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const FeatureOut& fo);
 void rtx_shade_set_ewa_lut(const float* lut128);  // kEwaLut of that translation unit
+// rtx_shade_rays.hip: bounce 0's shade launch of front-end `mode` for rays that carry differentials - k_shade_rays<mode, general>, the plain / GENERAL form of k_shade<mode>
+// with LDSREC = 0, whose camera vertices take their differentials from the caller's records (rd)
+void rtx_launch_shade_rays(int mode, bool general, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const RayDiffSrc& rd);
+void rtx_shade_rays_set_ewa_lut(const float* lut128);  // kEwaLut of that translation unit
 // rt_bsdf_eval: one Bsdf front-end of k_shade - mode 0 GenericBsdf, 3 SingleLambertT, 5 SmallBsdfT<false>, 6 SmallBsdfT<true>; const_tex: the constant-texture form
 // k_shade<1> and the LEAN forms use - on n queries, one lane each. Device pointers; surface NULL = the canonical hit. d.tri_p: record k carries orientation flag k (0, 1).
 struct BsdfEvalArgs { int material; const float4* surface; const float* wo; const float* wi; const float* u; unsigned n; float* out; };

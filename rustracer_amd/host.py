@@ -28,6 +28,8 @@ RT_FLAG_COUNT_AS_RENDERED = 8
 RT_FLAG_REF_STREAM = 16
 RT_FLAG_FRAME_STATS = 32   # rt_frame_begin: per-pixel luminance moments, adaptive steps
 RT_FLAG_FRAME_FEATURES = 64  # rt_frame_begin: per-pixel sums of the samples' first-hit features (albedo, normal, depth, coverage)
+RT_FLAG_RAY_DIFFERENTIALS = 128  # rt_render_rays / rt_frame_advance_rays* / rt_camera_rays: ray records of RT_RAY_DIFF_FLOATS floats (the ray, then rx_o, ry_o, rx_d, ry_d)
+RT_RAY_DIFF_FLOATS = 20
 RT_FEATURE_FLOATS = 16
 RT_FEATURE_SAMPLES_MAX = 1 << 25
 RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
@@ -45,6 +47,10 @@ BSDF_FRONT_ENDS = dict(auto=RT_BSDF_FRONT_AUTO, generic=RT_BSDF_FRONT_GENERIC, l
 
 class BackendError(RuntimeError):
     pass
+
+
+class RayRecordError(BackendError, ValueError):
+    """A ray array whose last axis is neither 8 nor RT_RAY_DIFF_FLOATS floats: a ValueError, and a BackendError as every other refusal of `render_rays` is."""
 
 
 STAMP = os.path.join(_BUILD, "source.sha")
@@ -529,13 +535,50 @@ class HostScene:
         _check(L.rtxh_render_sample_features(self.h, C.byref(p), C.c_void_p(stream), out.ctypes.data_as(C.c_void_p)), "sample_features")
         return out
 
+    def camera_rays(self, sample0=0, n_samples=None, differentials=False, with_p_film=True, device_out=None, stream=0):
+        """The perspective camera's rays as a camera frame generates them (rt_camera_rays): (rays (H, W, ns, 8) float32 - o.xyz, t_max = inf, d.xyz, 0 -, p_film
+        (H, W, ns, 2) or None) for samples [sample0, sample0 + ns) of every pixel of the film's sample bounds; `n_samples` defaults to the rest of the (rounded) spp.
+        `differentials=True`: records of 20 floats, the ray and then rx_o, ry_o, rx_d, ry_d as the camera frame's bounce 0 uses them (scaled by 1 / sqrt(spp)) - the
+        input of `render_rays` / `RayFrame.advance` that reproduces the camera frame on a textured scene. `device_out`: a contiguous torch CUDA float32 tensor of the
+        rays' shape, or a pair (rays, p_film) of them; they receive the records in HBM and are returned."""
+        st = self.setup()
+        p = st["params"]
+        sb = [int(v) for v in st["sample_bounds"]]
+        w, h = sb[2] - sb[0], sb[3] - sb[1]
+        spp = 1
+        while spp < max(int(p.spp), 1):
+            spp *= 2
+        ns = spp - int(sample0) if n_samples is None else int(n_samples)
+        rec = RT_RAY_DIFF_FLOATS if differentials else 8
+        if w <= 0 or h <= 0 or ns <= 0 or w * h * ns > RT_RAYS_MAX:
+            raise BackendError(f"camera_rays: {max(w, 0)} x {max(h, 0)} pixels x {ns} samples are none, or more than RT_RAYS_MAX rays - cut the job by sample range")
+        flags = RT_FLAG_RAY_DIFFERENTIALS if differentials else 0
+        L = lib()
+        L.rtxh_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if device_out is not None:
+            d_rays, d_pf = device_out if isinstance(device_out, (tuple, list)) else (device_out, None)
+            for t, shape in ((d_rays, (h, w, ns, rec)),) + (() if d_pf is None else ((d_pf, (h, w, ns, 2)),)):
+                if tuple(t.shape) != shape or not t.is_contiguous() or t.element_size() != 4:
+                    raise BackendError(f"camera_rays: device_out must be contiguous float32 of shape {shape}")
+            _check(L.rtxh_camera_rays(self.h, C.byref(p), int(sample0), ns, flags | RT_FLAG_FILM_ON_DEVICE, C.c_void_p(stream), C.c_void_p(d_rays.data_ptr()),
+                                      None if d_pf is None else C.c_void_p(d_pf.data_ptr())), "camera_rays")
+            return d_rays, d_pf
+        rays = np.zeros((h, w, ns, rec), np.float32)
+        pf = np.zeros((h, w, ns, 2), np.float32) if with_p_film else None
+        _check(L.rtxh_camera_rays(self.h, C.byref(p), int(sample0), ns, flags, C.c_void_p(stream), rays.ctypes.data_as(C.c_void_p),
+                                  None if pf is None else pf.ctypes.data_as(C.c_void_p)), "camera_rays")
+        return rays, pf
+
     def render_rays(self, rays, sample0=0, spp=None, max_depth=None, device_out=None, stream=0, count_traversal=False, time_kernels=False):
         """Path-traced radiance along caller-supplied rays (rt_render_rays): `rays` (H, W, ns, 8) float32 - o.xyz, t_max, d.xyz, unused; d is used as given -, returns
         (radiance (H, W, ns, 4), stats dict): L rgb as PathIntegrator::li returns it and a fourth float 0.0 / 1.0 (the renderer would scrub the sample) / 2.0 (t_max not
         > 0: the ray was not traced). Ray (x, y, sl) is sample sample0 + sl of pixel y * W + x of a virtual W x H film: `spp` (default: the scene's sampler's) sizes
         the sampler tables and [sample0, sample0 + ns) must lie inside it - a job of more than RT_RAYS_MAX rays is cut by sample range. `max_depth` defaults to the
         scene's integrator's; rr_threshold, light strategy and sampler dimensions are the scene's. `rays` may be a contiguous torch CUDA float32 tensor: `device_out`
-        must then be one of shape (H, W, ns, 4) (RT_FLAG_FILM_ON_DEVICE: both stay in HBM) and is returned."""
+        must then be one of shape (H, W, ns, 4) (RT_FLAG_FILM_ON_DEVICE: both stay in HBM) and is returned.
+        A last axis of 20 floats sets RT_FLAG_RAY_DIFFERENTIALS: the record goes on with the ray's differentials rx_o, ry_o, rx_d, ry_d (world space, used as given), which
+        enter compute_differential at the first vertex - what `camera_rays(differentials=True)` and `cameras.orthographic / environment(differentials=True)` return.
+        All-zero differentials, or a scene whose textures read none, give the 8-float result bit for bit. Any other width is a ValueError."""
         p = self._render_params()
         if spp is not None:
             p.spp = int(spp)
@@ -545,8 +588,12 @@ class HostScene:
         on_device = hasattr(rays, "data_ptr")
         if not on_device:
             rays = np.ascontiguousarray(rays, np.float32)
-        if len(rays.shape) != 4 or rays.shape[3] != 8:
-            raise BackendError(f"render_rays: rays must have shape (H, W, ns, 8), not {tuple(rays.shape)}")
+        if len(rays.shape) == 4 and rays.shape[3] not in (8, RT_RAY_DIFF_FLOATS):
+            raise RayRecordError(f"render_rays: a ray record is 8 floats, or {RT_RAY_DIFF_FLOATS} with differentials, not {int(rays.shape[3])}")
+        if len(rays.shape) != 4:
+            raise BackendError(f"render_rays: rays must have shape (H, W, ns, 8 | {RT_RAY_DIFF_FLOATS}), not {tuple(rays.shape)}")
+        if rays.shape[3] == RT_RAY_DIFF_FLOATS:
+            p.flags |= RT_FLAG_RAY_DIFFERENTIALS
         h, w, ns = (int(v) for v in rays.shape[:3])
         if h * w * ns > RT_RAYS_MAX:
             raise BackendError(f"render_rays: {h} x {w} x {ns} rays are more than RT_RAYS_MAX - cut the job by sample range")
@@ -733,7 +780,8 @@ class ProgressiveFrame:
 class RayFrame(ProgressiveFrame):
     """A progressive frame whose steps take their rays and film positions from the caller (HostScene.progressive_rays; rt_frame_begin_rays / rt_frame_advance_rays*):
     the film stage - pixel filter, clamp, read-outs, statistics, features, shards - for rays of any camera. `advance(rays, p_film=None)` renders the next n samples of
-    every pixel from `rays` (H, W, n, 8) float32 and splats each at `p_film` (H, W, n, 2) (None: the pixel centre); a ray whose t_max is not > 0 is skipped. Both may be
+    every pixel from `rays` (H, W, n, 8) float32 - or (H, W, n, 20): the ray and its differentials, as in `HostScene.render_rays` (RT_FLAG_RAY_DIFFERENTIALS, per step) -
+    and splats each at `p_film` (H, W, n, 2) (None: the pixel centre); a ray whose t_max is not > 0 is skipped. Both may be
     numpy arrays or contiguous torch device tensors (then both of them). Every read-out method and property is ProgressiveFrame's."""
 
     def __init__(self, scene, width, height, spp=None, max_depth=None, rank=0, world_size=1, table_budget=None, pixel_stats=False, features=False, count_traversal=False,
@@ -770,17 +818,20 @@ class RayFrame(ProgressiveFrame):
             rays = np.ascontiguousarray(rays, np.float32)
             if p_film is not None:
                 p_film = np.ascontiguousarray(p_film, np.float32)
-        if len(rays.shape) != 4 or tuple(rays.shape[:2]) != (self.height, self.width) or rays.shape[3] != 8:
-            raise BackendError(f"ray frame: rays must have shape ({self.height}, {self.width}, n, 8), not {tuple(rays.shape)}")
+        if len(rays.shape) == 4 and rays.shape[3] not in (8, RT_RAY_DIFF_FLOATS):
+            raise RayRecordError(f"ray frame: a ray record is 8 floats, or {RT_RAY_DIFF_FLOATS} with differentials, not {int(rays.shape[3])}")
+        if len(rays.shape) != 4 or tuple(rays.shape[:2]) != (self.height, self.width):
+            raise BackendError(f"ray frame: rays must have shape ({self.height}, {self.width}, n, 8 | {RT_RAY_DIFF_FLOATS}), not {tuple(rays.shape)}")
         n = int(rays.shape[2])
+        diff = RT_FLAG_RAY_DIFFERENTIALS if rays.shape[3] == RT_RAY_DIFF_FLOATS else 0
         if p_film is not None and tuple(p_film.shape) != (self.height, self.width, n, 2):
             raise BackendError(f"ray frame: p_film must have shape ({self.height}, {self.width}, {n}, 2), not {tuple(p_film.shape)}")
         if on_device:
             for t in (rays,) + (() if p_film is None else (p_film,)):
                 if not t.is_contiguous() or t.element_size() != 4:
                     raise BackendError("ray frame: device rays and p_film must be contiguous float32 tensors")
-            return C.c_void_p(rays.data_ptr()), (None if p_film is None else C.c_void_p(p_film.data_ptr())), n, RT_FLAG_FILM_ON_DEVICE, (rays, p_film)
-        return rays.ctypes.data_as(C.c_void_p), (None if p_film is None else p_film.ctypes.data_as(C.c_void_p)), n, 0, (rays, p_film)
+            return C.c_void_p(rays.data_ptr()), (None if p_film is None else C.c_void_p(p_film.data_ptr())), n, RT_FLAG_FILM_ON_DEVICE | diff, (rays, p_film)
+        return rays.ctypes.data_as(C.c_void_p), (None if p_film is None else p_film.ctypes.data_as(C.c_void_p)), n, diff, (rays, p_film)
 
     def advance(self, rays, p_film=None, stream=0):
         """Renders samples [samples_done, samples_done + n) of every pixel from `rays` (H, W, n, 8); returns the step's stats dict. n past the frame's spp is refused."""

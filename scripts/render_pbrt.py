@@ -2,7 +2,7 @@
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
-                                  [--camera-model orthographic|environment [--seed N] [--ray-frame]]
+                                  [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -26,7 +26,10 @@ the script's own, sample ranges of at most RT_RAYS_MAX rays, the radiance box-fi
 this command line, not a file directive: the loader refuses Camera "orthographic" / "environment" as the reference does.
 --ray-frame (with --camera-model): the same rays and film positions through a ray frame (rt_frame_begin_rays / rt_frame_advance_rays*) - filtered on the device with the
 file's PixelFilter, clamp and film scale, no sample travels back. Honours --preview-every N (steps of N samples, the image rewritten after each), --adaptive T with
---min-samples / --noise-floor / --sample-map, and --features; the PNG is RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights (RT_FRAME_SUMS). Without the flag --camera-model renders as before."""
+--min-samples / --noise-floor / --sample-map, and --features; the PNG is RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights (RT_FRAME_SUMS). Without the flag --camera-model renders as before.
+--ray-differentials (with --camera-model, with or without --ray-frame): the rays carry the camera model's differentials (records of 20 floats, RT_FLAG_RAY_DIFFERENTIALS;
+pbrt-v3's GenerateRayDifferential of each camera, scaled by 1 / sqrt(spp)), so image maps, checkerboards, fbm and bump maps are filtered at the first hit as under the
+file's perspective camera. Opt-in: without it the rays have none and textures are looked up at zero width, as before."""
 import argparse
 import os
 import sys
@@ -34,10 +37,11 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def camera_model_samples(s, model, seed=0):
+def camera_model_samples(s, model, seed=0, differentials=False):
     """The generator behind --camera-model: (w, h, spp, chunks) where `chunks` yields (s0, p_film [h, w, ns, 2] float64, rays [h, w, ns, 8] float32) for sample ranges
     [s0, s0 + ns) of at most RT_RAYS_MAX rays that together are [0, spp). The camera takes the file's camera-to-world and, orthographic, its "screenwindow" (pbrt's
-    default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5) from numpy's default_rng(seed), drawn range after range."""
+    default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5) from numpy's default_rng(seed), drawn range after range.
+    `differentials`: records of 20 floats with the camera model's differentials, scaled for `spp`."""
     import numpy as np
     from rustracer_amd import cameras, host
     p = s._render_params()
@@ -59,19 +63,20 @@ def camera_model_samples(s, model, seed=0):
         for s0 in range(0, spp, step):
             ns = min(step, spp - s0)
             p_film = cameras.pixel_centres(w, h, ns) + rng.uniform(-0.5, 0.5, (h, w, ns, 2))
-            rays = cameras.orthographic(c2w, win, w, h, p_film) if model == "orthographic" else cameras.environment(c2w, w, h, p_film)
+            kw = dict(differentials=True, spp=spp) if differentials else {}
+            rays = cameras.orthographic(c2w, win, w, h, p_film, **kw) if model == "orthographic" else cameras.environment(c2w, w, h, p_film, **kw)
             yield s0, p_film, rays
 
     return w, h, spp, chunks()
 
 
-def render_camera_model(s, model, seed=0):
+def render_camera_model(s, model, seed=0, differentials=False):
     """The scene through `HostScene.render_rays` with a camera of rustracer_amd/cameras.py in place of the file's: returns (rgb [yres, xres, 3] float32 - the box-filtered
     radiance, each pixel the mean of its own samples, scrubbed samples black as in the renderer -, stats summed over the calls). The camera takes the file's
     camera-to-world and, orthographic, its "screenwindow" (pbrt's default from the aspect ratio without one); film positions are pixel + 0.5 + a jitter in [-0.5, 0.5)
-    from numpy's default_rng(seed); the samples go through in sample ranges of at most RT_RAYS_MAX rays."""
+    from numpy's default_rng(seed); the samples go through in sample ranges of at most RT_RAYS_MAX rays. `differentials`: --ray-differentials."""
     import numpy as np
-    w, h, spp, chunks = camera_model_samples(s, model, seed)
+    w, h, spp, chunks = camera_model_samples(s, model, seed, differentials)
     total = np.zeros((h, w, 3), np.float64)
     stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
     for s0, _, rays in chunks:
@@ -94,14 +99,15 @@ def frame_rgb(frame):
     return (q * np.float32(frame.scale)).astype(np.float32)
 
 
-def render_camera_model_frame(s, model, seed=0, preview_every=0, adaptive=None, noise_floor=1e-3, min_samples=8, features=False, on_step=None):
+def render_camera_model_frame(s, model, seed=0, preview_every=0, adaptive=None, noise_floor=1e-3, min_samples=8, features=False, on_step=None, differentials=False):
     """--camera-model --ray-frame: the same rays and film positions as `render_camera_model` draws for `seed`, through a ray frame (`HostScene.progressive_rays`) - the
     film stage on the device, with the file's PixelFilter, max_sample_luminance and film scale instead of the numpy box filter. Steps of `preview_every` samples (0: a
     whole sample range each; 4 under `adaptive`); `on_step(frame)` is called after each. `adaptive` = T: the steps are `advance_adaptive(.., T, noise_floor,
     min_samples)` and end when no pixel is active. Returns dict(rgb [yres, xres, 3] float32 - `frame_rgb` -, png8 [yres, xres, 3] uint8 - RT_FRAME_RGB8 -, stats,
-    samples_done, samples_taken, spp, counts - the per-pixel sample counts, adaptive only -, features - [yres, xres, 8] where asked for)."""
+    samples_done, samples_taken, spp, counts - the per-pixel sample counts, adaptive only -, features - [yres, xres, 8] where asked for). `differentials`:
+    --ray-differentials."""
     import numpy as np
-    w, h, spp, chunks = camera_model_samples(s, model, seed)
+    w, h, spp, chunks = camera_model_samples(s, model, seed, differentials)
     stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
     with s.progressive_rays(w, h, spp=spp, pixel_stats=adaptive is not None, features=features) as frame:
         stopped = False
@@ -133,6 +139,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="with --camera-model: seed of the film-position jitter")
     ap.add_argument("--ray-frame", action="store_true",
                     help="with --camera-model: filter the samples on the device through a ray frame (rt_frame_advance_rays) with the file's PixelFilter, in steps")
+    ap.add_argument("--ray-differentials", action="store_true",
+                    help="with --camera-model: the rays carry the camera model's differentials (RT_FLAG_RAY_DIFFERENTIALS), so textures are filtered at the first hit")
     ap.add_argument("scene")
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
@@ -161,6 +169,8 @@ def main():
         raise SystemExit("Unsupported file format")   # rc/imageio.rs:47-49 (EXR output is not written here)
     if a.ray_frame and not a.camera_model:
         raise SystemExit("--ray-frame goes with --camera-model")
+    if a.ray_differentials and not a.camera_model:
+        raise SystemExit("--ray-differentials goes with --camera-model")
     if a.camera_model and a.ray_frame:
         import numpy as np
         if a.devices:
@@ -177,7 +187,7 @@ def main():
             print(f"{out}: {frame.samples_done} / {frame.spp} samples per pixel" + (f", {frame.active_pixels} pixels active" if a.adaptive is not None else ""), flush=True)
 
         r = render_camera_model_frame(s, a.camera_model, a.seed, preview_every=a.preview_every, adaptive=a.adaptive, noise_floor=a.noise_floor, min_samples=a.min_samples,
-                                      features=bool(a.features), on_step=preview if a.preview_every > 0 else None)
+                                      features=bool(a.features), on_step=preview if a.preview_every > 0 else None, differentials=a.ray_differentials)
         put(r["rgb"], r["png8"])
         if a.adaptive is not None:
             full = int(np.count_nonzero(r["counts"])) * r["spp"]
@@ -191,7 +201,7 @@ def main():
         print(f"{out}: {r['rgb'].shape[1]}x{r['rgb'].shape[0]}, {a.camera_model} camera through a ray frame, {stats['camera_rays']} rays, {stats['paths_scrubbed']} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
         return
     if a.camera_model:
-        rgb, stats = render_camera_model(s, a.camera_model, a.seed)
+        rgb, stats = render_camera_model(s, a.camera_model, a.seed, differentials=a.ray_differentials)
         if out.endswith(".pfm"):
             write_pfm(out, rgb)
         else:
