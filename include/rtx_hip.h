@@ -636,7 +636,9 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
                                      const_tex 1: its constant-texture form), 0 before the first call */,
        RT_QUERY_NEEDS_DIFFERENTIALS = 6 /* 1 if some texture or bump map of the scene reads ray differentials (image maps, closed-form checkerboards, fbm): the shade kernels
                                            then regenerate the camera ray's at bounce 0 in the frames of a camera, and load the caller's from the ray records in a call or ray-frame step with
-                                           RT_FLAG_RAY_DIFFERENTIALS; without the flag caller-supplied rays have none */ };
+                                           RT_FLAG_RAY_DIFFERENTIALS; without the flag caller-supplied rays have none */,
+       RT_QUERY_LDS_SPEC = 7 /* the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC, read by rt_scene_create; 0: leaf holders wait,
+                                1: they keep walking up to the next leaf), 0 for every other scene */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

@@ -70,6 +70,7 @@ struct rt_scene {
   int stack_depth = 64;  // entries the to-visit stack needs for this tree (<= 64, rc/bvh/mod.rs:374)
   unsigned n_nodes = 0, n_tris = 0; int n_lights = 0;
   DevBuf link8, link8_full; unsigned lds_nodes_tested = 0;  // link tables of the stackless LDS walks; nodes they test (of n_nodes)
+  int lds_spec = 0;  // the form of the closest-hit link walk (closest_small_links' SPEC) of an LDS-resident scene of plain triangles: RTX_LDS_SPEC, read per scene
   DevBuf pairs, tmin_stack;  // child-pair node records and the HBM half of the traversal stack (k_trace_pair)
   DevBuf top_pairs, deep_stack; bool use_top = false;  // k_trace_top: LDS-resident top of the tree, HBM spill of stack entries beyond the LDS ones
   bool top_for_closest = false;  // closest-hit rays through k_trace_top as well (shadow rays always, when no four-wide records exist)
@@ -373,6 +374,7 @@ extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (what == RT_QUERY_SHADOW_EMPTY) return s->shadow_sets ? (int)s->shadow.empty : 0;
   if (what == RT_QUERY_BSDF_LAUNCHED) return s->bsdf_launched < 0 ? 0 : s->bsdf_launched + 1;
   if (what == RT_QUERY_NEEDS_DIFFERENTIALS) return s->d.needs_differentials ? 1 : 0;
+  if (what == RT_QUERY_LDS_SPEC) return s->lds_spec;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -495,6 +497,11 @@ extern "C" int rt_light_distribution(rt_scene* s, int32_t n_voxels[3], float* fu
 }
 
 // ---------------------------------------------------------------------------------------------- trace launches
+// the forms of the closest-hit link walk this library holds (k_trace: 0, k_trace_spec<1>: 1) and the one a scene gets without RTX_LDS_SPEC
+#ifndef RT_LDS_SPEC_DEFAULT
+#define RT_LDS_SPEC_DEFAULT 1  // S1 closest hit 188 -> 174 ms per frame (MEASUREMENTS R9)
+#endif
+static bool lds_spec_built(int spec) { return spec == 0 || spec == 1; }
 // LDS a workgroup of the trace kernels declares, and the persistent grid that fills every CU at that residency
 template <bool ANY, bool SMALL, int BLOCK, int DEPTH>
 static unsigned trace_grid(const rt_scene* s, bool links = false) {  // links: an LDS-resident scene's rays that count no visits (link rows instead of a stack, k_trace)
@@ -548,6 +555,10 @@ static int scene_from_plan(const RtScenePlan& p, const rt_scene_desc* desc, int 
   }
   const bool links = s->small || s->mid;
   if (links) s->lds_nodes_tested = p.links.nodes_tested;
+  if (s->small && !s->general_prims) {  // RTX_LDS_SPEC: measurement / test knob, read per scene like RTX_LDS_PRUNE; a form that is not built is refused, not replaced
+    s->lds_spec = env_int("RTX_LDS_SPEC", RT_LDS_SPEC_DEFAULT);
+    if (!lds_spec_built(s->lds_spec)) return fail(RT_ERR_INVALID, "RTX_LDS_SPEC names a form of the closest-hit link walk that is not built");
+  }
   int rc = RT_OK;  // the first failure; what follows it is skipped
   auto up = [&rc](DevBuf& b, const void* src, size_t bytes) { if (rc == RT_OK) rc = upload(b, src, bytes); };
   auto up_all = [&up](DevBuf& b, const auto& v) { up(b, v.data(), v.size() * sizeof(v[0])); };
@@ -731,6 +742,9 @@ static void launch_trace_c(rt_scene* s, const TraceIO& io, const unsigned* queue
       return;
     }
     if (s->small) {  // the link walks: no stack, whatever the tree's depth
+      if constexpr (!ANY) {  // closest hit: the walk's form (rt_scene::lds_spec)
+        if (s->lds_spec == 1) { hipLaunchKernelGGL((k_trace_spec<1>), dim3(trace_grid<ANY, true, 256, 16>(s, true)), dim3(256), 0, stream, RT_KARGS, st_nodes, st_tris); return; }
+      }
       hipLaunchKernelGGL((k_trace<ANY, false, 256, 16>), dim3(trace_grid<ANY, true, 256, 16>(s, true)), dim3(256), 0, stream, RT_KARGS, st_nodes, st_tris);
       return;
     }

@@ -894,7 +894,14 @@ RT_DEV bool occluded_small_links(const float* __restrict__ s_nodes, const float*
   return found;
 }
 // TRIS_GLOBAL: the triangles are read from HBM (tri_p; s_tris unused) - the mid-size scenes' closest-hit walk, whose LDS holds the bounds and eight link rows
-template <int N, int T, bool FINITE, int LEAF_MIN, int GENERAL = 0, bool TRIS_GLOBAL = false>
+// SPEC (FINITE walks only; DESIGN 5.3 "leaf holders keep walking"): 0 - a lane that holds a leaf sits out the node rounds until the leaf phases have emptied it.
+// 1 - it keeps stepping nodes with the t_max it has; at the next leaf whose box it passes it STALLS (bit 31 of `cur`, which stays on that node) and, once its held leaf
+// is empty, tests that node again as any walker would - with the t_max SPEC 0 has there.
+// Leaves are entered in link order, each after a box test under the t_max the as-built walk has at that point, so the primitive tests and their t_max are SPEC 0's: a box
+// that fails under a larger t_max fails under a smaller one (nothing is skipped that SPEC 0 tests), and below a node SPEC 0 would have rejected every box fails the
+// re-test (bounds are nested, (bound - o) * inv_dir is monotone in the bound). Termination: a node round advances `cur` of every stepping lane or stalls it; a stalled
+// lane holds a leaf, and once nobody can step a leaf phase runs and shortens it.
+template <int N, int T, bool FINITE, int LEAF_MIN, int GENERAL = 0, bool TRIS_GLOBAL = false, int SPEC = 0>
 RT_DEV bool closest_small_links(const float* __restrict__ s_nodes, const float* __restrict__ s_tris, const unsigned* __restrict__ link8 /* rows N (LDS) or n_nodes (HBM) apart */, const int row, const int n_nodes, Ray ray, int& prim_out, TriHit& hit_out, const GeneralCtx gen = GeneralCtx{nullptr, false}, const float4* __restrict__ tri_p = nullptr) {
   const f3 inv_dir = mk3(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
   const int neg_x = inv_dir.x < 0.0f, neg_y = inv_dir.y < 0.0f, neg_z = inv_dir.z < 0.0f;
@@ -904,6 +911,47 @@ RT_DEV bool closest_small_links(const float* __restrict__ s_nodes, const float* 
   const float* const tpx = s_tris + rp.kx * T; const float* const tpy = s_tris + rp.ky * T; const float* const tpz = s_tris + rp.kz * T;
   const f3 op = permute(ray.o, rp.kx, rp.ky, rp.kz);
   bool found = false;
+  if constexpr (SPEC != 0 && FINITE) {
+    static_assert(SPEC == 1, "closest_small_links: forms 0 and 1");
+    constexpr unsigned STALL = 0x80000000u;
+    unsigned cur = link8[8 * row + oct];  // the node the lane tests next; >= n_nodes: the walk is over, or (STALL) it waits on that node for its held leaf to run out
+    int leaf_off = 0, leaf_n = 0;
+    for (;;) {
+      unsigned long long holders = 0ull;
+      for (;;) {
+        if (cur < (unsigned)n_nodes) {
+          const float* nd = s_nodes + cur;
+          const float4 n0 = make_float4(nd[0], nd[2 * N], nd[4 * N], nd[N]), n1 = make_float4(nd[3 * N], nd[5 * N], 0.0f, 0.0f);
+          const unsigned lk = link[cur];
+          unsigned next = lk & 0xffffu;
+          if (slab_test_t<true>(n0, n1, ray, inv_dir, neg_x, neg_y, neg_z)) {
+            if ((int)lk < 0) {
+              if (leaf_n == 0) { leaf_off = RT_LINK_LEAF_OFF(lk, N); leaf_n = RT_LINK_LEAF_N(lk, N); }
+              else next = cur | STALL;
+            } else next = lk >> 16;
+          }
+          cur = next;
+        }
+        holders = __ballot(leaf_n > 0);
+        if (__ballot(cur < (unsigned)n_nodes) == 0ull) break;
+        if (__builtin_popcount((unsigned)holders) + __builtin_popcount((unsigned)(holders >> 32)) >= LEAF_MIN) break;
+      }
+      if (holders == 0ull) break;
+      if (leaf_n > 0) {
+        const int t = leaf_off;
+        TriHit h;
+        bool hit;
+        if (GENERAL) hit = leaf_prim_test<GENERAL>(LdsSrcT<N, T>{s_nodes, s_tris}, gen, t, ray, rp, h);
+        else if (TRIS_GLOBAL) { f3 q0, q1, q2; load_tri(tri_p, t, q0, q1, q2); hit = tri_test_pre(q0, q1, q2, ray, rp, h); }
+        else { const f3 p0t = mk3(tpx[t] - op.x, tpy[t] - op.y, tpz[t] - op.z), p1t = mk3(tpx[3 * T + t] - op.x, tpy[3 * T + t] - op.y, tpz[3 * T + t] - op.z), p2t = mk3(tpx[6 * T + t] - op.x, tpy[6 * T + t] - op.y, tpz[6 * T + t] - op.z);
+          hit = tri_test_permuted(p0t, p1t, p2t, rp.sx, rp.sy, rp.sz, ray.t_max, h); }
+        if (hit) { found = true; ray.t_max = h.t; prim_out = t; hit_out = h; }
+        leaf_off += 1; leaf_n -= 1;
+        if (leaf_n == 0) cur &= ~STALL;
+      }
+    }
+    return found;
+  }
   int cur = (int)link8[8 * row + oct], leaf_off = 0, leaf_n = 0;  // the octant's first tested node
   for (;;) {
     unsigned long long holders = 0ull;
@@ -1036,91 +1084,27 @@ RT_DEV void trace_write_any(float4* __restrict__ lacc, size_t ls, const AddPtr d
 #ifndef RT_MID_LEAF_MIN_CLOSEST
 #define RT_MID_LEAF_MIN_CLOSEST 16
 #endif
+#ifndef RT_LDS_LEAF_MIN_SPEC  // the plain closest-hit walk with leaf holders that keep walking (k_trace_spec): leaf phases at this many holders
+#define RT_LDS_LEAF_MIN_SPEC RT_LDS_LEAF_MIN_CLOSEST
+#endif
 #define RT_MID_NODES 2816
 #define RT_MID_TRIS 1408
 template <bool ANY, bool COUNT, int BLOCK, int DEPTH, int GENERAL = 0, int MID = 0>  // LDS-resident and mid-size scenes. GENERAL: quadrics / alpha-masked triangles in the leaves (no object instances)
 __global__ void __launch_bounds__(BLOCK, MID ? 4 : ((GENERAL == 0 && !COUNT) ? (ANY ? RT_LDS_ANY_WAVES : RT_LDS_TRACE_WAVES) : RT_GEN_MIN_WAVES(GENERAL))) k_trace(DScene sc, TraceIO io, const unsigned* __restrict__ queue, const unsigned* __restrict__ shard_counts, unsigned shard_cap,
                                                  unsigned count_static, unsigned long long* stats, int st_rays, int st_nodes, int st_tris) {
-  // (plain loads and stores, no non-temporal hint: the scene is in LDS, the ray streams are all these launches read)
-  const float4* __restrict__ ray_o = sraw(io.ray_o); const float4* __restrict__ ray_d = sraw(io.ray_d); const size_t rs = io.ray_stride;
-  float4* __restrict__ hits = sraw(io.hits); const size_t hs = io.hit_stride; const bool hit_b2 = io.hit_b2 != 0;
-  unsigned* __restrict__ occluded = io.occluded; const size_t os = io.occ_stride;
-  float4* __restrict__ lacc = io.lacc; const size_t ls = io.lacc_stride; const float4* __restrict__ direct_add = sraw(io.direct_add); const size_t as = io.add_stride;
-  // node indices of a tiny scene fit 16 bits: half the stack bytes => more resident waves per CU
-  typedef unsigned short StackT;
-  // LINKS: an LDS-resident scene's rays that do not count visits walk WITHOUT a stack over the link tables (closest_small_links, occluded_small_links[_rounds]) -
-  // plain triangles, quadrics and masked triangles alike. Counting launches (the reference's walk, visit by visit) and HBM scenes keep the stack walk (traverse).
-  constexpr bool LINKS = !COUNT;
-  __shared__ StackT stack[LINKS ? 1 : DEPTH * BLOCK];
-  constexpr int NN = MID ? RT_MID_NODES : RT_SMALL_NODES, NT = MID ? RT_MID_TRIS : RT_SMALL_TRIS;
-  static_assert(!MID || (!COUNT && GENERAL == 0), "mid-size LDS scenes: plain triangles, no visit counts");
-  constexpr bool MIDC = MID != 0 && !ANY;  // closest hit of a mid-size scene: six bound planes + eight link rows fill the LDS, the triangles stay in HBM
-  typedef LdsSrcT<NN, NT> LdsS;
-  __shared__ float s_nodes[(MIDC ? 6 : 8) * NN];
-  __shared__ float s_tris[MIDC ? 1 : 10 * NT];
-  QView qv; if (queue) qv.init(io.queue_is_slots ? nullptr : queue, shard_counts, shard_cap);
-  const unsigned count = queue ? qv.total() : count_static;
-  if (blockIdx.x * BLOCK >= count) return;  // short queues (MIS rays, late bounces): most blocks of the persistent grid have nothing to stage for
-  __shared__ unsigned s_link[LINKS ? (ANY ? 1 : 8) * NN + 8 : 1];  // DScene::link8 (the tested nodes' links), rows NN apart, then the 8 start nodes
-  stage_small_scene<BLOCK, NN, NT, MIDC>(sc, s_nodes, s_tris); __syncthreads();
-  if (LINKS) {
-    // DScene::link8: rows 0 - 7 (closest hit, by octant), their 8 starts, row 8 (occlusion rays), its start
-    if (ANY) { for (unsigned k = threadIdx.x; k < sc.n_nodes; k += BLOCK) s_link[k] = sc.link8[8u * sc.n_nodes + 8u + k]; if (threadIdx.x == 0u) s_link[NN] = sc.link8[9u * sc.n_nodes + 8u]; }
-    else {
-      for (unsigned i = threadIdx.x; i < 8u * sc.n_nodes; i += BLOCK) { const unsigned o = i / sc.n_nodes, k = i - o * sc.n_nodes; s_link[o * NN + k] = sc.link8[i]; }
-      if (threadIdx.x < 8u) s_link[8 * NN + threadIdx.x] = sc.link8[8u * sc.n_nodes + threadIdx.x];
-    }
-    __syncthreads();
-  }
-  const unsigned stride = gridDim.x * BLOCK;
-  unsigned n_nodes = 0, n_tris = 0, n_rays = 0;
-  auto trace_one = [&](unsigned pid) {
-    float4 o4 = ray_o[pid * rs], d4 = ray_d[pid * rs];
-    Ray ray; ray.o = mk3(o4.x, o4.y, o4.z); ray.d = mk3(d4.x, d4.y, d4.z); ray.t_max = o4.w;
-    int prim = -1; TriHit h; h.t = kInf; h.b0 = h.b1 = h.b2 = 0.0f;
-    bool found;
-    constexpr int LM = ANY ? (MID ? RT_MID_LEAF_MIN_ANY : (GENERAL ? RT_LDS_LEAF_MIN_ANY_GENERAL : RT_LDS_LEAF_MIN_ANY)) : (MID ? RT_MID_LEAF_MIN_CLOSEST : (GENERAL ? RT_LDS_LEAF_MIN_CLOSEST_GENERAL : RT_LDS_LEAF_MIN_CLOSEST));
-    const GeneralCtx gen{sc.self, ANY && io.shadow_masks != 0};
-    // Plain-triangle launches that do not count visits take the min / max node test (slab_test_finite) when every ray of the wave has a finite reciprocal
-    // direction - all but a few hundred waves of a frame; a wave that holds one ray with a zero direction component walks with the reference's selects.
-    constexpr bool FIN_FORMS = !COUNT;
-    const bool fin = FIN_FORMS && __ballot(!inv_dir_finite(mk3(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z))) == 0ull;
-    if (LINKS) {
-      static_assert(!LINKS || ANY || (LM > 1 && LM < 64), "the closest-hit link walk tests its leaves in phases: 1 < LEAF_MIN < 64");
-      if (!ANY) {
-        if (fin) found = closest_small_links<NN, NT, true, LM, GENERAL, MIDC>(s_nodes, s_tris, s_link, NN, (int)sc.n_nodes, ray, prim, h, gen, sc.tri_p);  // (s_link: 8 rows NN apart, the starts behind them)
-        else found = closest_small_links<NN, NT, false, LM, GENERAL, MIDC>(s_nodes, s_tris, sc.link8_full, (int)sc.n_nodes, (int)sc.n_nodes, ray, prim, h, gen, sc.tri_p);
-      } else if (LM > 1 && LM < 64) {
-        found = fin ? occluded_small_links_rounds<NN, NT, true, LM, GENERAL>(s_nodes, s_tris, s_link, (int)sc.n_nodes, (int)s_link[NN], ray, gen)
-                    : occluded_small_links_rounds<NN, NT, false, LM, GENERAL>(s_nodes, s_tris, sc.link8_full + 8u * sc.n_nodes + 8u, (int)sc.n_nodes, (int)sc.link8_full[9u * sc.n_nodes + 8u], ray, gen);
-      } else {
-        found = fin ? occluded_small_links<NN, NT, true, GENERAL>(s_nodes, s_tris, s_link, (int)sc.n_nodes, (int)s_link[NN], ray, gen)
-                    : occluded_small_links<NN, NT, false, GENERAL>(s_nodes, s_tris, sc.link8_full + 8u * sc.n_nodes + 8u, (int)sc.n_nodes, (int)sc.link8_full[9u * sc.n_nodes + 8u], ray, gen);
-      }
-    }
-    else {  // a frame that counts the reference's walk, visit by visit: the stack walk over the LDS copy
-      LdsS src{s_nodes, s_tris};
-      found = traverse<ANY, COUNT, LdsS, StackT, GENERAL>(src, ray, stack + threadIdx.x, BLOCK, prim, h, n_nodes, n_tris, gen);
-    }
-    n_rays += 1;
-    if (ANY) trace_write_any(lacc, ls, direct_add, as, occluded, os, pid, d4.w, found);
-    else hits[pid * hs] = make_float4(hit_b2 ? h.b2 : (found ? h.t : kInf), __int_as_float(found ? prim : -1), h.b0, h.b1);
-    return found;
-  };
-  for (unsigned i = blockIdx.x * BLOCK + threadIdx.x; i < count; i += stride) {
-    const bool found = trace_one(queue ? qv.get(i) : i);
-    if constexpr (!ANY) {  // TraceIO::hit_mask: the wave's 64 entries (lanes past the queue's end are not here: their bits are zero), stored by its first lane
-      if (io.hit_mask != nullptr) { const unsigned long long m = __ballot(found); if ((threadIdx.x & 63u) == 0u) io.hit_mask[i >> 6] = m; }
-    } else (void)found;
-  }
-  if (stats) {
-    // one atomic per wave and counter
-    for (int off = 32; off > 0; off >>= 1) { n_rays += __shfl_down(n_rays, off); if (COUNT) { n_nodes += __shfl_down(n_nodes, off); n_tris += __shfl_down(n_tris, off); } }
-    if ((threadIdx.x & 63u) == 0u) {
-      if (n_rays) atomicAdd(&stats[st_rays], (unsigned long long)n_rays);
-      if (COUNT) { atomicAdd(&stats[st_nodes], (unsigned long long)n_nodes); atomicAdd(&stats[st_tris], (unsigned long long)n_tris); }
-    }
-  }
+  constexpr int SPEC = 0;
+#include "rtx_trace_body.inl"
+}
+// k_trace<false, false, 256, 16>, the closest-hit kernel of an LDS-resident scene of plain triangles, with leaf holders that keep walking (SPEC 1; a kernel of its
+// own name: k_trace's instantiations keep theirs and their allocation)
+#ifndef RT_LDS_SPEC_WAVES
+#define RT_LDS_SPEC_WAVES RT_LDS_TRACE_WAVES
+#endif
+template <int SPEC>
+__global__ void __launch_bounds__(256, RT_LDS_SPEC_WAVES) k_trace_spec(DScene sc, TraceIO io, const unsigned* __restrict__ queue, const unsigned* __restrict__ shard_counts, unsigned shard_cap,
+                                                                        unsigned count_static, unsigned long long* stats, int st_rays, int st_nodes, int st_tris) {
+  constexpr bool ANY = false, COUNT = false; constexpr int BLOCK = 256, DEPTH = 16, GENERAL = 0, MID = 0;
+#include "rtx_trace_body.inl"
 }
 
 // ---- Measured on the LDS-resident kernel in round 4 and not kept (S1, one box, closest hit / shadow rays per frame; k_trace as it stands: 336 / 168 ms):

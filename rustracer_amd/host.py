@@ -37,6 +37,7 @@ RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
 RT_SAMPLES_MAX = 1 << 27
 RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
+RT_QUERY_LDS_SPEC = 7  # rt_scene_query: the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC: 0, 1)
 RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
 RT_QUERY_BSDF_LAUNCHED = 5# rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
 RT_FRAME_XYZW, RT_FRAME_RGB, RT_FRAME_RGB8, RT_FRAME_STATS, RT_FRAME_FEATURES, RT_FRAME_SUMS = range(6)                    # rt_frame_read: what

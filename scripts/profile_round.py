@@ -75,7 +75,7 @@ def source_sha():
             h.update(open(os.path.join(d, f), 'rb').read())
     return h.hexdigest()[:16]
 
-# closest-hit kernels of the timed frames: k_trace<false, false, ...> (LDS scenes), k_trace_pair<false, ...> or k_trace_top<false, ...> (HBM scenes)
+# closest-hit kernels of the timed frames: k_trace<false, false, ...> or k_trace_spec<1> (LDS scenes), k_trace_pair<false, ...> or k_trace_top<false, ...> (HBM scenes)
 import datetime, subprocess
 try:
     commit = subprocess.run(['git', 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip() or None
@@ -84,7 +84,7 @@ except Exception:
 out = {'scene': scene, 'collected': f'{tag}, {datetime.date.today().isoformat()}' + (f', tree {commit}' if commit else ''),
        'method': 'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes; KiB->B. hbm_bytes_per_launch_raw = writes + reads as counted (64 B per L2-miss read request), hbm_bytes_per_launch = writes + 2 x reads (rounds 1 - 5). Calibrated in round 6 (profiles/r06_fetch_calibration.txt): a coalesced stream is fetched in 128-byte requests (counter = half its bytes), a gather that misses L2 is one request per 64-byte sector (counter = what it moved) - bench.py therefore reports raw + half of the STREAMED read bytes of the stage as `traffic`',
        'source': f'profiles/{tag}_{scene}_pmc_hbm.csv', 'kernel_source_sha': source_sha(),
-       'trace_closest': pick(['rtx::k_trace<false, false', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false']),
+       'trace_closest': pick(['rtx::k_trace<false, false', 'rtx::k_trace_spec<', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false']),
        'shade': pick(['rtx::k_shade'], per_stage=True)}
 
 def per_sample(prefixes):
@@ -100,7 +100,7 @@ try:  # the PMC runs write their full measurement next to their counters (bench.
     samples = json.load(open(os.path.join(base, 'fetch_detail.json')))['camera_samples_per_step']
 except Exception:
     pass
-out['trace_closest_all'] = per_sample(['rtx::k_trace<false, false', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false'])  # k_trace_big is the visit-counting frame's kernel: not a timed launch
+out['trace_closest_all'] = per_sample(['rtx::k_trace<false, false', 'rtx::k_trace_spec<', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false'])  # k_trace_big is the visit-counting frame's kernel: not a timed launch
 out['trace_any_all'] = per_sample(['rtx::k_trace<true, false', 'rtx::k_trace_pair<true', 'rtx::k_trace_top<true', 'rtx::k_trace_quad'])  # (<ANY, COUNT = false, ...>: the counting frame's kernels are not timed launches)
 
 # Per shade front-end: HBM bytes per VERTEX of the class the form serves ("kernel: k_shade" hid which form wastes the bytes). Vertex counts by
@@ -143,7 +143,7 @@ def valu_busy(prefixes):
         return None
 _, sq_disp_n = per_kernel('sq', 'SQ_INSTS_VALU')
 sq_disp = {(k, 'SQ_INSTS_VALU'): v for k, v in sq_disp_n.items()}
-for grp, pre in (('trace_closest', ['rtx::k_trace<false, false', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false']), ('shade', ['rtx::k_shade'])):
+for grp, pre in (('trace_closest', ['rtx::k_trace<false, false', 'rtx::k_trace_spec<', 'rtx::k_trace_pair<false', 'rtx::k_trace_top<false']), ('shade', ['rtx::k_shade'])):
     if out.get(grp):
         out[grp]['valu_busy'] = valu_busy(pre)
 json.dump(out, open(os.path.join('profiles', f'pmc_{scene}.json'), 'w'), indent=1)
