@@ -585,6 +585,48 @@ int rt_frame_advance_rays(rt_frame* frame, const float* rays, const float* p_fil
 int rt_frame_advance_rays_adaptive(rt_frame* frame, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, float threshold, float floor_y,
                                    int32_t min_samples, uint32_t flags, void* stream, rt_stats* stats /* of this step, may be NULL */);
 
+/* Camera models: pbrt-v3's orthographic and environment (lat-long) cameras generated ON THE DEVICE from the pixel-keyed sampler - the first users of rt_render_rays and
+ * ray frames no longer compute their rays on the host, upload them, or bring a jitter of their own. A model is `int32_t model` plus `const float camera[RT_CAMERA_MODEL_FLOATS]`:
+ *   camera[0..15]  camera_to_world, row-major 4 x 4 (points as columns; the last row is not read): o_w = M o, d_w = normalize(M3x3 d), no origin nudge
+ *   camera[16..19] screen_window x0, x1, y0, y1 of the plane z = 0 of camera space (orthographic; the environment camera reads none)
+ *   camera[20]     lens_radius (orthographic: pbrt-v3's thin lens; the environment camera has none: must be 0)
+ *   camera[21]     focal_distance (read where lens_radius > 0)
+ *   camera[22..23] reserved, must be 0
+ * The film is the VIRTUAL FILM of rt_render_rays and ray frames, W x H = the extent of film->cropped_pixel_bounds - the film's full resolution: a model has no crop window, so
+ * the bounds must start at (0, 0); film->sample_bounds is ignored - and sample bounds = cropped pixel bounds = [0, W) x [0, H), pixel_index = y * W + x.
+ * The camera sample of (pixel, sample) is the perspective frame's: p_film = (x, y) + 2D#0 of the pixel's tables, p_lens = 2D#1 where lens_radius > 0, the keyed RNG stream
+ * and the dimension counters where get_camera_sample leaves them - so dimension 2D#0 keeps its (0,2)-sequence stratification, and a shard generates its own rows' rays.
+ *   RT_CAMERA_ORTHOGRAPHIC: p_cam = (x0 + p_film.x / W (x1 - x0), y1 - p_film.y / H (y1 - y0), 0), d = (0, 0, 1); with a lens pl = lens_radius * concentric_sample_disk(p_lens),
+ *     the ray leaves (pl.x, pl.y, 0) toward p_cam + focal_distance / d.z * d. Differentials: rx_o = o + ((x1 - x0) / W, 0, 0), ry_o = o + (0, -(y1 - y0) / H, 0), rx_d = ry_d = d;
+ *     with a lens rx_o = ry_o = o and rx_d = normalize(p_cam + dx + (0, 0, ft) - o), ft = focal_distance / d.z of the main ray, ry_d likewise.
+ *   RT_CAMERA_ENVIRONMENT: theta = pi p_film.y / H, phi = 2 pi p_film.x / W, o = 0, d = (sin theta cos phi, cos theta, sin theta sin phi); the differentials are the same
+ *     generator at p_film + (1, 0) and p_film + (0, 1).
+ *   In world space the differentials are pulled toward the main ray by 1 / sqrt(spp) (spp rounded up to a power of two), as rt_camera_rays' are. t_max = inf.
+ * rt_camera_model_rays: rt_camera_rays for a model - same record layouts ([H][W][n_samples][8 | RT_RAY_DIFF_FLOATS], p_film [H][W][n_samples][2] or NULL), flags
+ *   (RT_FLAG_FILM_ON_DEVICE, RT_FLAG_RAY_DIFFERENTIALS; any other bit is refused) and limits (RT_RAYS_MAX). p_film equals rt_camera_rays' of a film with these bounds, byte for byte.
+ * rt_frame_begin_model: a progressive frame whose steps generate the model's rays on the device - no ray, film position or sample crosses the host bus. Of `film`
+ *   filter_radius, filter_table and max_sample_luminance are read as in rt_frame_begin_rays (a radius in (0, 8]); path->pixel_bounds is ignored. flags: RT_FLAG_FRAME_STATS /
+ *   _FRAME_FEATURES / _COUNT_TRAVERSAL / _TIME_KERNELS / _COUNT_AS_RENDERED as in rt_frame_begin, and RT_FLAG_RAY_DIFFERENTIALS: bounce 0 is shaded with the model's
+ *   differentials on a scene that reads them (without the flag, or on a scene that reads none, none are generated). rt_frame_advance, rt_frame_advance_adaptive,
+ *   rt_frame_read, rt_frame_query and rt_frame_end work on the frame; rt_frame_advance_rays* refuse it. A step stages its records in a buffer the frame owns
+ *   (counted in RT_FRAME_STATE_BYTES; 40 or 88 bytes per pixel and sample of the step) and then runs the step of a ray frame on it; a step of more than RT_RAYS_MAX rays
+ *   is cut by sample range internally. THE FRAME IS THE RAY FRAME OF ITS OWN RAYS: rt_frame_advance_rays with rt_camera_model_rays' records and positions of the same
+ *   sample ranges gives the same sums, statistics and feature planes byte for byte. ms_raygen of a step: generation and k_raygen_rays_film.
+ * rt_render_model: rt_render's one-call form - begin, one step of spp samples, rt_frame_read(RT_FRAME_XYZW), end: film_xyzw [H][W][4] (device memory with
+ *   RT_FLAG_FILM_ON_DEVICE), the bytes of the finished model frame.
+ * Refused with RT_ERR_INVALID and a message that names the field, before any device work: an unknown model; a screen_window that is empty or not finite (orthographic);
+ *   lens_radius < 0 or not finite; focal_distance not > 0 while lens_radius > 0; a non-zero lens_radius on the environment camera; a camera_to_world entry that is not
+ *   finite; non-zero reserved floats; cropped_pixel_bounds that do not start at (0, 0) or are empty; and what rt_camera_rays / rt_frame_begin_rays refuse. Single device. */
+#define RT_CAMERA_ORTHOGRAPHIC 1
+#define RT_CAMERA_ENVIRONMENT 2
+#define RT_CAMERA_MODEL_FLOATS 24
+int rt_camera_model_rays(rt_scene* scene, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], const rt_film_desc* film, const rt_sampler_desc* sampler,
+                         int32_t sample0, int32_t n_samples, uint32_t flags, void* stream, float* rays, float* p_film /* may be NULL */);
+int rt_frame_begin_model(rt_scene* scene, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                         const rt_shard* shard /* may be NULL */, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out);
+int rt_render_model(rt_scene* scene, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_path_desc* path,
+                    const rt_shard* shard /* may be NULL */, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats /* may be NULL */);
+
 /* Progressive and adaptive frames across the workers of an rt_multi: the frame of rt_frame_* spread over the devices of rt_multi_create, read as ONE film.
  * rt_multi_frame_begin opens one rt_frame per worker k on the multi's replica k with rt_shard{k, n_devices} - the static split into interleaved bands of
  *   RT_SHARD_ROWS rows: a pixel's own sum, its sampler tables and its moments live on one device for the life of the frame, so the chunk queue of rt_multi_render

@@ -182,6 +182,22 @@ int rtxh_frame_advance_rays(rtxh_frame*, const float* rays, const float* p_film 
                             rt_stats* stats /* of this step, may be NULL */);
 int rtxh_frame_advance_rays_adaptive(rtxh_frame*, const float* rays, const float* p_film /* may be NULL */, int32_t n_samples, float threshold, float floor_y,
                                      int32_t min_samples, uint32_t flags, void* hip_stream, rt_stats* stats /* of this step, may be NULL */);
+/* Camera models generated on the device (rt_camera_model_rays / rt_frame_begin_model / rt_render_model in rtx_hip.h): pbrt-v3's orthographic and environment cameras.
+ * rtxh_camera_model fills the RT_CAMERA_MODEL_FLOATS floats of `model` (RT_CAMERA_ORTHOGRAPHIC / RT_CAMERA_ENVIRONMENT) from render parameters, such as a loaded pbrt
+ * scene's: cam_to_world; screen_window, or - all four zero - pbrt's default from the aspect ratio xres / yres ((-a, a, -1, 1) for a > 1, else (-1, 1, -1 / a, 1 / a));
+ * lens_radius and focal_distance (orthographic only: the environment camera has no lens); the reserved floats 0.
+ * The other three take the film from the parameters as rtxh_frame_begin_rays does - xres x yres pixels, the pixel filter, max_sample_luminance; crop and pixel bounds are
+ * ignored -, the sampler, the integrator, rank / world_size and the flags (RT_FLAG_RAY_DIFFERENTIALS among them: the frame shades bounce 0 with the model's
+ * differentials). rtxh_camera_model_rays: rays yres x xres x n_samples x 8 floats, or x RT_RAY_DIFF_FLOATS with RT_FLAG_RAY_DIFFERENTIALS in `flags`; p_film
+ * yres x xres x n_samples x 2 or NULL; device pointers with RT_FLAG_FILM_ON_DEVICE in `flags`. The frame of rtxh_frame_begin_model takes its steps from
+ * rtxh_frame_advance / _advance_adaptive and is read, queried and ended as every rtxh_frame. rtxh_render_model: film_xyzw yres x xres x 4 floats (a device pointer with
+ * RT_FLAG_FILM_ON_DEVICE among the parameters' flags). The scene is uploaded first if need be; what the rt_ calls
+ * refuse they refuse before any device work of their own. */
+int rtxh_camera_model(const rtxh_render_params*, int32_t model, float camera[RT_CAMERA_MODEL_FLOATS]);
+int rtxh_camera_model_rays(rtxh_scene*, const rtxh_render_params*, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], int32_t sample0, int32_t n_samples, uint32_t flags,
+                           void* hip_stream, float* rays, float* p_film /* may be NULL */);
+int rtxh_frame_begin_model(rtxh_scene*, const rtxh_render_params*, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], uint64_t table_budget_bytes, rtxh_frame** out);
+int rtxh_render_model(rtxh_scene*, const rtxh_render_params*, int32_t model, const float camera[RT_CAMERA_MODEL_FLOATS], void* hip_stream, float* film_xyzw, rt_stats* stats);
 /* The same frame on several GPUs of this process (rt_multi_* in rtx_hip.h): the scene is replicated on `devices` (kept for later calls with the
  * same list), host threads pull chunks of tile rows, the film is gathered on devices[0] and returned in host memory (or in memory of devices[0]
  * with RT_FLAG_FILM_ON_DEVICE). rank / world_size of the parameters are ignored. */

@@ -20,6 +20,7 @@
 #include "rtx_shade_launch.h"
 #include "rtx_ref_launch.h"
 #include "rtx_rays_launch.h"
+#include "rtx_cameras_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -1047,7 +1048,12 @@ struct rt_frame {
   DevBuf feature_plane;
   // rt_frame_begin_rays: every step takes its rays and film positions from the caller (rt_frame_advance_rays*); `cam` is unused
   bool ray_frame = false;
-  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes + feature_plane.bytes; }
+  // rt_frame_begin_model: every step generates the model's rays into the frame's staging buffers ([pixel_index][samples of the step] records and film positions) and
+  // then runs the step of a ray frame on them; model_diff: records of RT_RAY_DIFF_FLOATS floats on a scene that reads differentials
+  int model = 0; bool model_diff = false;
+  float model_cam[RT_CAMERA_MODEL_FLOATS] = {};
+  DevBuf model_rays, model_pfilm;
+  size_t state_bytes() const { return film_acc.bytes + own_acc.bytes + filter_table.bytes + out.bytes + scrambles.bytes + perms.bytes + moments.bytes + active.bytes + n_active.bytes + feature_plane.bytes + model_rays.bytes + model_pfilm.bytes; }
 };
 static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u * (size_t)(owned_pixels / 4096u + 4u); }  // alignment room: a batch holds >= 4096 pixels, plus a leading and a last one
 
@@ -1076,10 +1082,20 @@ static size_t frame_table_slack(unsigned long long owned_pixels) { return 256u *
 // camera's rays of samples [sample0, sample0 + n_samples) to k_camera_rays ([pixel][sample of the call] records of rec_floats floats, film positions where asked for).
 struct RaySource { const float* rays; unsigned sample0, n_samples; const float* p_film; bool on_device; unsigned rec_floats; };
 struct CamRaysOut { float* rays; float* p_film; unsigned sample0, n_samples, rec_floats; };
+// model != NULL: the camera of the call is a camera model (rtx_cameras.hip). With cam_out: rt_camera_model_rays - k_camera_model_rays in the place of k_camera_rays.
+// With fr: the step of a MODEL FRAME (rt_frame_begin_model) - a ray frame's step whose records and film positions k_camera_model_rays (_masked under active_mask)
+// writes, pass by pass, into the frame's staging buffers right before k_raygen_rays_film reads them: nothing of it comes from or goes to the host. Every ray is traced
+// (t_max = inf), so the scan that picks a ray frame's route is left out: its answer is known.
 static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
                         const rt_shard* shard, uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out, float* samples_rad, float* samples_pf,
                         rt_frame* fr = nullptr, unsigned step_end = 0, const unsigned char* active_mask = nullptr, bool have_lock = false, float* samples_feat = nullptr,
-                        const RaySource* ray_src = nullptr, const CamRaysOut* cam_out = nullptr) {
+                        const RaySource* ray_src = nullptr, const CamRaysOut* cam_out = nullptr, const CameraModel* model = nullptr) {
+  const bool model_step = model != nullptr && fr != nullptr && cam_out == nullptr;
+  RaySource model_src{};
+  if (model_step) {  // (the staging buffers are allocated below, under the scene's mutex)
+    model_src = RaySource{nullptr, fr->done, step_end - fr->done, nullptr, true, fr->model_diff ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
+    ray_src = &model_src;
+  }
   const bool rays = ray_src != nullptr, camrays = cam_out != nullptr;
   const bool samples = samples_rad != nullptr;
   const bool fsamples = samples_feat != nullptr, features = fsamples || (fr && fr->features);
@@ -1107,6 +1123,12 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   if (!have_lock) render_lock.lock();
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t stream = (hipStream_t)stream_;
+  if (model_step) {
+    if (fr->model_rays.ensure((size_t)n_window_samples * model_src.rec_floats * 4) != hipSuccess || fr->model_pfilm.ensure((size_t)n_window_samples * 8) != hipSuccess) {
+      (void)hipGetLastError(); return fail(RT_ERR_OOM, "rt_frame_advance: not enough device memory for the rays of the model frame's step - take fewer samples per step");
+    }
+    model_src.rays = fr->model_rays.as<float>(); model_src.p_film = fr->model_pfilm.as<float>();
+  }
   const unsigned spp = next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
   const unsigned dims = (unsigned)smp->dimensions;
   if (dims < 2 || dims > 8) return fail(RT_ERR_INVALID, "sampler dimensions must be in [2, 8]");
@@ -1324,7 +1346,7 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       }
       d_rays = s->rays_in.as<float4>(); d_pfilm = ray_src->p_film ? s->pfilm_in.as<float2>() : nullptr;
     }
-    if (all_in_bounds && owned_pixels > 0) {  // (the step of rt_frame_advance_rays_adaptive takes the queued route whatever the rays hold: nothing to decide)
+    if (all_in_bounds && owned_pixels > 0 && !model_step) {  // (the step of rt_frame_advance_rays_adaptive takes the queued route whatever the rays hold: nothing to decide)
       HIP_TRY(hipMemsetAsync(s->rays_skipped.p, 0, 4, stream));
       tm.begin(&stats.ms_raygen);
       if (fr && world > 1) {
@@ -1446,7 +1468,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       if (camrays) {  // rt_camera_rays: the pass's camera rays, handed out instead of traced
         if (build_tables) for (int g = 1; g < 3; ++g) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][g], 0));  // (no bounce waits for the later groups: the call returns with every table built)
         tm.begin(&stats.ms_raygen);
-        rtx_launch_camera_rays(pgrid, stream, fp, ps, cam_out->sample0, cam_out->n_samples, rec_floats / 4u, d_cam_rays, d_cam_pf);
+        if (model) rtx_launch_camera_model_rays(pgrid, stream, fp, ps, *model, cam_out->sample0, cam_out->n_samples, rec_floats / 4u, d_cam_rays, d_cam_pf, nullptr);
+        else rtx_launch_camera_rays(pgrid, stream, fp, ps, cam_out->sample0, cam_out->n_samples, rec_floats / 4u, d_cam_rays, d_cam_pf);
         tm.end();
         stats.n_passes += 1;
         HIP_TRY(hipGetLastError());
@@ -1455,6 +1478,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
       tm.begin(&stats.ms_raygen);
       if (rays && fr) {  // the step of a ray frame: k_raygen_rays' tiles, and the film positions (masked in an adaptive step)
         unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < ps.n_samples) ++ts_log2;
+        if (model_step)  // the pass's records and film positions, from the tables the pass waits for above (group 0: 2D#0 and, with a lens, 2D#1)
+          rtx_launch_camera_model_rays(pgrid, stream, fp, ps, *model, ray_src->sample0, ray_src->n_samples, rec_floats / 4u, fr->model_rays.as<float4>(), fr->model_pfilm.as<float2>(), active_mask);
         rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, d_rays, d_pfilm, ray_src->sample0, ray_src->n_samples, rec_floats / 4u, ts_log2, active_mask);
       }
       else if (active_mask) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, active_mask);
@@ -1665,6 +1690,71 @@ extern "C" int rt_camera_rays(rt_scene* s, const rt_camera* cam, const rt_film_d
   return render_frame(s, cam, film, smp, &p, nullptr, flags & RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, nullptr, nullptr, &out);
 }
 
+// ---------------------------------------------------------------------------------------------- camera models
+// What every entry point that takes a camera model refuses, before any device work: each message names the field.
+static int camera_model_check(const char* who, int32_t model, const float* c) {
+  const std::string w(who);
+  if (model != RT_CAMERA_ORTHOGRAPHIC && model != RT_CAMERA_ENVIRONMENT) return fail(RT_ERR_INVALID, w + ": unknown model (RT_CAMERA_ORTHOGRAPHIC = 1, RT_CAMERA_ENVIRONMENT = 2)");
+  for (int i = 0; i < 16; ++i) if (!std::isfinite(c[i])) return fail(RT_ERR_INVALID, w + ": camera_to_world holds an entry that is not finite");
+  if (c[22] != 0.0f || c[23] != 0.0f) return fail(RT_ERR_INVALID, w + ": the reserved floats camera[22..23] must be 0");
+  const float lens_radius = c[20], focal_distance = c[21];
+  if (!std::isfinite(lens_radius) || lens_radius < 0.0f) return fail(RT_ERR_INVALID, w + ": lens_radius must be a finite number >= 0");
+  if (model == RT_CAMERA_ENVIRONMENT) {
+    if (lens_radius != 0.0f) return fail(RT_ERR_INVALID, w + ": the environment camera has no lens: lens_radius must be 0");
+    return RT_OK;
+  }
+  for (int i = 16; i < 20; ++i) if (!std::isfinite(c[i])) return fail(RT_ERR_INVALID, w + ": screen_window holds an entry that is not finite");
+  if (!(c[17] > c[16]) || !(c[19] > c[18])) return fail(RT_ERR_INVALID, w + ": screen_window (x0, x1, y0, y1) is empty: x1 > x0 and y1 > y0 are required");
+  if (lens_radius > 0.0f && !(focal_distance > 0.0f && std::isfinite(focal_distance))) return fail(RT_ERR_INVALID, w + ": focal_distance must be a finite number > 0 where lens_radius > 0");
+  return RT_OK;
+}
+// ... and of the film: a model renders the film's full resolution, cropped_pixel_bounds = [0, W) x [0, H)
+static int camera_model_film_check(const char* who, const rt_film_desc* film, long long* W, long long* H) {
+  const std::string w(who);
+  if (film->cropped_pixel_bounds[0] != 0 || film->cropped_pixel_bounds[1] != 0) return fail(RT_ERR_INVALID, w + ": cropped_pixel_bounds must start at (0, 0) - a camera model renders the film's full resolution");
+  *W = film->cropped_pixel_bounds[2]; *H = film->cropped_pixel_bounds[3];
+  if (*W <= 0 || *H <= 0) return fail(RT_ERR_INVALID, w + ": empty film (cropped_pixel_bounds)");
+  return RT_OK;
+}
+static CameraModel make_camera_model(int32_t model, const float* c, int W, int H) {
+  CameraModel cm{};
+  cm.model = model; memcpy(cm.c2w, c, sizeof(cm.c2w)); memcpy(cm.sw, c + 16, sizeof(cm.sw));
+  cm.lens_radius = c[20]; cm.focal_distance = c[21]; cm.width = (float)W; cm.height = (float)H;
+  return cm;
+}
+// The rays (and film positions) of a camera model over its virtual film: rt_camera_rays' batches, passes and sampler tables with k_camera_model_rays per pass.
+extern "C" int rt_camera_model_rays(rt_scene* s, int32_t model, const float* camera, const rt_film_desc* film, const rt_sampler_desc* smp, int32_t sample0, int32_t n_samples,
+                                    uint32_t flags, void* stream_, float* rays, float* p_film) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  const char* who = "rt_camera_model_rays";
+  if (!s || !camera || !film || !smp || !rays) return fail(RT_ERR_INVALID, "rt_camera_model_rays: null argument");
+  if (flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_RAY_DIFFERENTIALS))
+    return fail(RT_ERR_INVALID, "rt_camera_model_rays: the flags of the call are RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers) and RT_FLAG_RAY_DIFFERENTIALS");
+  int rc = camera_model_check(who, model, camera);
+  if (rc != RT_OK) return rc;
+  long long W = 0, H = 0;
+  if ((rc = camera_model_film_check(who, film, &W, &H)) != RT_OK) return rc;
+  if (smp->spp > 16384) return fail(RT_ERR_INVALID, "rt_camera_model_rays: spp > 16384 unsupported");
+  if (smp->dimensions < 2 || smp->dimensions > 8) return fail(RT_ERR_INVALID, "rt_camera_model_rays: sampler dimensions must be in [2, 8]");
+  const long long spp_r = (long long)next_pow2((unsigned)(smp->spp > 0 ? smp->spp : 1));
+  if (n_samples <= 0 || sample0 < 0 || (long long)sample0 + (long long)n_samples > spp_r)
+    return fail(RT_ERR_INVALID, "rt_camera_model_rays: [sample0, sample0 + n_samples) must be a non-empty range inside [0, spp)");
+  if ((unsigned long long)W * (unsigned long long)H > (unsigned long long)RT_RAYS_MAX ||
+      (unsigned long long)W * (unsigned long long)H * (unsigned long long)n_samples > (unsigned long long)RT_RAYS_MAX)
+    return fail(RT_ERR_INVALID, "rt_camera_model_rays: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+  if (!rt_device_available()) return fail(RT_ERR_NO_DEVICE, "rt_camera_model_rays: no HIP device visible; this backend has no CPU fallback");
+  rt_camera cam{};  // of the perspective camera's record only the lens radius is read: a lens makes the frame's tables hold 2D#1
+  cam.lens_radius = camera[20]; cam.focal_distance = camera[21];
+  rt_film_desc f{};  // the virtual film
+  f.cropped_pixel_bounds[2] = f.sample_bounds[2] = (int32_t)W; f.cropped_pixel_bounds[3] = f.sample_bounds[3] = (int32_t)H;
+  f.filter_radius[0] = f.filter_radius[1] = 0.5f; f.max_sample_luminance = std::numeric_limits<float>::infinity();
+  rt_path_desc p{};  // no path is traced; pixel_bounds = the sample bounds: every sample of the film gets its ray
+  memcpy(p.pixel_bounds, f.sample_bounds, 16);
+  const CamRaysOut out{rays, p_film, (unsigned)sample0, (unsigned)n_samples, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
+  const CameraModel cm = make_camera_model(model, camera, (int)W, (int)H);
+  return render_frame(s, &cam, &f, smp, &p, nullptr, flags & RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, false, nullptr, nullptr, &out, &cm);
+}
+
 // ---------------------------------------------------------------------------------------------- progressive frames
 extern "C" int rt_frame_begin(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path, const rt_shard* shard,
                               uint32_t flags, uint64_t table_budget_bytes, rt_frame** out) {
@@ -1729,6 +1819,14 @@ extern "C" int rt_frame_begin(rt_scene* s, const rt_camera* cam, const rt_film_d
   *out = fr.release();
   return RT_OK;
 }
+static void stats_add(rt_stats& a, const rt_stats& b);
+// A model frame's camera as the kernels take it, and the end of the next sample range of a step that ends at `end`: at most RT_RAYS_MAX rays in the staging buffers
+static CameraModel frame_camera_model(const rt_frame* fr) { return make_camera_model(fr->model, fr->model_cam, fr->film.sample_bounds[2], fr->film.sample_bounds[3]); }
+static unsigned model_step_end(const rt_frame* fr, unsigned end) {
+  const unsigned long long px = (unsigned long long)fr->film.sample_bounds[2] * (unsigned long long)fr->film.sample_bounds[3];
+  const unsigned long long ns = std::max<unsigned long long>(1ull, (unsigned long long)RT_RAYS_MAX / std::max<unsigned long long>(px, 1ull));
+  return (unsigned)std::min<unsigned long long>(end, (unsigned long long)fr->done + ns);
+}
 extern "C" int rt_frame_advance(rt_frame* fr, int32_t n_samples, void* stream, rt_stats* stats_out) {
   if (!fr) return fail(RT_ERR_INVALID, "rt_frame_advance: null frame");
   if (fr->ray_frame) return fail(RT_ERR_INVALID, "rt_frame_advance: a ray frame takes its steps from rt_frame_advance_rays");
@@ -1736,6 +1834,19 @@ extern "C" int rt_frame_advance(rt_frame* fr, int32_t n_samples, void* stream, r
   if (fr->done >= fr->spp) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }  // a finished frame: nothing to render
   const unsigned end = (unsigned)std::min<unsigned long long>(fr->spp, (unsigned long long)fr->done + (unsigned long long)n_samples);
   rt_stats st{};
+  if (fr->model) {  // a model frame: the step of a ray frame on the rays the frame generates, in sample ranges of at most RT_RAYS_MAX rays
+    const CameraModel cm = frame_camera_model(fr);
+    rt_stats total{};
+    while (fr->done < end) {
+      const unsigned sub = model_step_end(fr, end);
+      const int rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, &st, nullptr, nullptr, fr, sub,
+                                  nullptr, false, nullptr, nullptr, nullptr, &cm);
+      if (rc != RT_OK) return rc;
+      fr->done = sub; fr->samples_taken += st.camera_rays; stats_add(total, st);
+    }
+    if (stats_out) *stats_out = total;
+    return RT_OK;
+  }
   const int rc = render_frame(fr->scene, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream, nullptr, &st, nullptr, nullptr, fr, end);
   if (rc == RT_OK) { fr->done = end; fr->samples_taken += st.camera_rays; if (stats_out) *stats_out = st; }
   return rc;
@@ -1775,6 +1886,19 @@ static int frame_adaptive_step(rt_frame* fr, unsigned end, float threshold, floa
   }
   fr->active_pixels = n_active;
   rt_stats st{};
+  if (n_active > 0 && fr->model) {  // a model frame: the one mask in front of every sample range of the step (rt_frame_advance)
+    const CameraModel cm = frame_camera_model(fr);
+    while (fr->done < end) {
+      const unsigned sub = model_step_end(fr, end);
+      rt_stats part{};
+      const int rc = render_frame(s, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, &part, nullptr, nullptr, fr, sub,
+                                  fr->active.as<unsigned char>(), true, nullptr, nullptr, nullptr, &cm);
+      if (rc != RT_OK) return rc;
+      fr->done = sub; fr->samples_taken += part.camera_rays; stats_add(st, part);
+    }
+    if (stats_out) *stats_out = st;
+    return RT_OK;
+  }
   if (n_active > 0) {  // (no active pixel: no path kernel, no film kernel - the step only moves `done`)
     const int rc = render_frame(s, &fr->cam, &fr->film, &fr->smp, &fr->path, &fr->shard, fr->flags & ~(uint32_t)RT_FLAG_FILM_ON_DEVICE, stream_, nullptr, &st, nullptr, nullptr, fr, end,
                                 fr->active.as<unsigned char>(), true, nullptr, ray_src);
@@ -1832,6 +1956,7 @@ static int frame_rays_kind_check(const char* who, rt_frame* fr, const float* ray
   if (!fr || !rays) return fail(RT_ERR_INVALID, std::string(who) + ": null frame or rays");
   if (flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_RAY_DIFFERENTIALS))
     return fail(RT_ERR_INVALID, std::string(who) + ": the flags of a step are RT_FLAG_FILM_ON_DEVICE (rays and p_film are device pointers) and RT_FLAG_RAY_DIFFERENTIALS (records of 20 floats)");
+  if (fr->model) return fail(RT_ERR_INVALID, std::string(who) + ": the frame was begun with a camera model (rt_frame_begin_model): it generates its own rays and takes its steps from rt_frame_advance / _adaptive");
   if (!fr->ray_frame) return fail(RT_ERR_INVALID, std::string(who) + ": the frame was begun with a camera (rt_frame_begin): it takes its steps from rt_frame_advance / _adaptive");
   return RT_OK;
 }
@@ -1876,6 +2001,39 @@ extern "C" int rt_frame_advance_rays_adaptive(rt_frame* fr, const float* rays, c
   if (finished) { if (stats_out) *stats_out = rt_stats{}; return RT_OK; }
   const RaySource src{rays, fr->done, (unsigned)n_samples, p_film, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, (flags & RT_FLAG_RAY_DIFFERENTIALS) ? (unsigned)RT_RAY_DIFF_FLOATS : 8u};
   return frame_adaptive_step(fr, fr->done + (unsigned)n_samples, threshold, floor_y, min_samples, stream, stats_out, &src);
+}
+// ---------------------------------------------------------------------------------------------- model frames
+// A ray frame that generates its own rays: rt_frame_begin_rays' frame over the virtual film, with the model kept for its steps (render_frame: model_step).
+extern "C" int rt_frame_begin_model(rt_scene* s, int32_t model, const float* camera, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                                    const rt_shard* shard, uint32_t flags, uint64_t table_budget_bytes, rt_frame** out) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  const char* who = "rt_frame_begin_model";
+  if (!out) return fail(RT_ERR_INVALID, "rt_frame_begin_model: NULL out");
+  *out = nullptr;
+  if (!s || !camera || !film || !smp || !path) return fail(RT_ERR_INVALID, "rt_frame_begin_model: null argument");
+  int rc = camera_model_check(who, model, camera);
+  if (rc != RT_OK) return rc;
+  long long W = 0, H = 0;
+  if ((rc = camera_model_film_check(who, film, &W, &H)) != RT_OK) return rc;
+  if ((unsigned long long)W * (unsigned long long)H > (unsigned long long)RT_RAYS_MAX) return fail(RT_ERR_INVALID, "rt_frame_begin_model: the film holds more than RT_RAYS_MAX (2^27) pixels");
+  rc = rt_frame_begin_rays(s, (int32_t)W, (int32_t)H, film, smp, path, shard, flags & ~(uint32_t)RT_FLAG_RAY_DIFFERENTIALS, table_budget_bytes, out);
+  if (rc != RT_OK) return rc;
+  rt_frame* fr = *out;
+  fr->ray_frame = false; fr->model = model; memcpy(fr->model_cam, camera, sizeof(fr->model_cam));
+  fr->cam.lens_radius = camera[20]; fr->cam.focal_distance = camera[21];  // (a lens: the frame's tables hold 2D#1; nothing else of the perspective record is read)
+  fr->model_diff = (flags & RT_FLAG_RAY_DIFFERENTIALS) != 0 && s->d.needs_differentials != 0;
+  return RT_OK;
+}
+extern "C" int rt_render_model(rt_scene* s, int32_t model, const float* camera, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_path_desc* path,
+                               const rt_shard* shard, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats_out) {
+  if (!film_xyzw) return fail(RT_ERR_INVALID, "rt_render_model: null argument");
+  rt_frame* fr = nullptr;
+  int rc = rt_frame_begin_model(s, model, camera, film, smp, path, shard, flags & ~(uint32_t)(RT_FLAG_FILM_ON_DEVICE | RT_FLAG_FRAME_STATS | RT_FLAG_FRAME_FEATURES), 0, &fr);
+  if (rc != RT_OK) return rc;
+  rc = rt_frame_advance(fr, (int32_t)fr->spp, stream, stats_out);
+  if (rc == RT_OK) rc = rt_frame_read(fr, RT_FRAME_XYZW, 1.0f, flags & RT_FLAG_FILM_ON_DEVICE, stream, film_xyzw);
+  rt_frame_end(fr);
+  return rc;
 }
 static size_t frame_read_bytes(int32_t what) {  // bytes per cropped pixel of a read-out
   return what == RT_FRAME_FEATURES ? 32 : (what == RT_FRAME_STATS ? 24 : ((what == RT_FRAME_XYZW || what == RT_FRAME_SUMS) ? 16 : (what == RT_FRAME_RGB ? 12 : 3)));

@@ -1433,6 +1433,74 @@ int rtxh_frame_advance_rays_adaptive(rtxh_frame* f, const float* rays, const flo
   g_err.clear();
   return rt_frame_advance_rays_adaptive(f->f, rays, p_film, n_samples, threshold, floor_y, min_samples, flags, stream, stats);
 }
+// Camera models (rt_camera_model_rays / rt_frame_begin_model / rt_render_model): the 24 floats from render parameters, and the three calls over the parameters' film.
+int rtxh_camera_model(const rtxh_render_params* p, int32_t model, float* camera) {
+  if (!p || !camera) return fail(RT_ERR_INVALID, "rtxh_camera_model: null argument");
+  if (model != RT_CAMERA_ORTHOGRAPHIC && model != RT_CAMERA_ENVIRONMENT) return fail(RT_ERR_INVALID, "rtxh_camera_model: unknown model (RT_CAMERA_ORTHOGRAPHIC = 1, RT_CAMERA_ENVIRONMENT = 2)");
+  if (p->xres <= 0 || p->yres <= 0) return fail(RT_ERR_INVALID, "rtxh_camera_model: xres and yres must be positive");
+  g_err.clear();
+  for (int i = 0; i < RT_CAMERA_MODEL_FLOATS; ++i) camera[i] = 0.0f;
+  memcpy(camera, p->cam_to_world, 64);
+  const float* sw = p->screen_window;
+  if (sw[0] == 0.0f && sw[1] == 0.0f && sw[2] == 0.0f && sw[3] == 0.0f) {  // pbrt's default: the shorter axis spans [-1, 1]
+    const float a = (float)p->xres / (float)p->yres;
+    if (a > 1.0f) { camera[16] = -a; camera[17] = a; camera[18] = -1.0f; camera[19] = 1.0f; }
+    else { camera[16] = -1.0f; camera[17] = 1.0f; camera[18] = -1.0f / a; camera[19] = 1.0f / a; }
+  } else memcpy(camera + 16, sw, 16);
+  if (model == RT_CAMERA_ORTHOGRAPHIC) { camera[20] = p->lens_radius; camera[21] = p->focal_distance; }
+  return RT_OK;
+}
+// The virtual film of a camera model over the parameters: xres x yres pixels, the pixel filter tabulated as setup_camera_film tabulates it, the clamp
+static int model_film_of(const char* who, const rtxh_render_params* p, rt_film_desc& film) {
+  film = rt_film_desc{};
+  const float xw = p->filter_params[0], yw = p->filter_params[1];
+  if (!(xw > 0.0f && yw > 0.0f) || xw > 8.0f || yw > 8.0f) return fail(RT_ERR_INVALID, std::string(who) + ": the filter radius must lie in (0, 8]");
+  film.cropped_pixel_bounds[2] = film.sample_bounds[2] = p->xres; film.cropped_pixel_bounds[3] = film.sample_bounds[3] = p->yres;
+  film.filter_radius[0] = xw; film.filter_radius[1] = yw;
+  for (int y = 0; y < 16; ++y) {
+    float fy = ((float)y + 0.5f) * (yw / 16.0f);
+    for (int x = 0; x < 16; ++x) { float fx = ((float)x + 0.5f) * (xw / 16.0f); film.filter_table[y * 16 + x] = filter_eval(p->filter_kind, p->filter_params, fx, fy); }
+  }
+  film.max_sample_luminance = p->max_sample_luminance;
+  return RT_OK;
+}
+int rtxh_camera_model_rays(rtxh_scene* s, const rtxh_render_params* p, int32_t model, const float* camera, int32_t sample0, int32_t n_samples, uint32_t flags, void* stream,
+                           float* rays, float* p_film) {
+  if (!s || !p || !camera || !rays) return fail(RT_ERR_INVALID, "rtxh_camera_model_rays: null argument");
+  g_err.clear();
+  rt_film_desc film; int rc = model_film_of("rtxh_camera_model_rays", p, film); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_camera_model_rays(s->dev, model, camera, &film, &smp, sample0, n_samples, flags, stream, rays, p_film);
+}
+int rtxh_frame_begin_model(rtxh_scene* s, const rtxh_render_params* p, int32_t model, const float* camera, uint64_t table_budget_bytes, rtxh_frame** out) {
+  if (!s || !p || !camera || !out) return fail(RT_ERR_INVALID, "rtxh_frame_begin_model: null argument");
+  g_err.clear();
+  *out = nullptr;
+  rt_film_desc film; int rc = model_film_of("rtxh_frame_begin_model", p, film); if (rc != RT_OK) return rc;
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_path_desc path{}; path.max_depth = p->max_depth; path.rr_threshold = p->rr_threshold; path.light_strategy = p->light_strategy;
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  rt_frame* f = nullptr;
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  rc = rt_frame_begin_model(s->dev, model, camera, &film, &smp, &path, &shard, p->flags, table_budget_bytes, &f);
+  if (rc != RT_OK) return rc;
+  *out = new rtxh_frame{f};
+  return RT_OK;
+}
+int rtxh_render_model(rtxh_scene* s, const rtxh_render_params* p, int32_t model, const float* camera, void* stream, float* film_xyzw, rt_stats* stats) {
+  if (!s || !p || !camera || !film_xyzw) return fail(RT_ERR_INVALID, "rtxh_render_model: null argument");
+  rtxh_frame* f = nullptr;
+  rtxh_render_params q = *p; q.flags &= ~(uint32_t)(RT_FLAG_FRAME_STATS | RT_FLAG_FRAME_FEATURES | RT_FLAG_FILM_ON_DEVICE);
+  int rc = rtxh_frame_begin_model(s, &q, model, camera, 0, &f);
+  if (rc != RT_OK) return rc;
+  uint64_t spp = 0;
+  rc = rt_frame_query(f->f, RT_FRAME_SPP, &spp);
+  if (rc == RT_OK) rc = rt_frame_advance(f->f, (int32_t)spp, stream, stats);
+  if (rc == RT_OK) rc = rt_frame_read(f->f, RT_FRAME_XYZW, 1.0f, p->flags & RT_FLAG_FILM_ON_DEVICE, stream, film_xyzw);
+  rtxh_frame_end(f);
+  return rc;
+}
 // The replicas of the scene on `devices`: made on first use, kept while the device list and the commit stay the same.
 static int ensure_multi(rtxh_scene* s, const int32_t* devices, int32_t n_devices) {
   const std::vector<int32_t> want(devices, devices + n_devices);

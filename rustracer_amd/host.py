@@ -30,6 +30,9 @@ RT_FLAG_FRAME_STATS = 32   # rt_frame_begin: per-pixel luminance moments, adapti
 RT_FLAG_FRAME_FEATURES = 64  # rt_frame_begin: per-pixel sums of the samples' first-hit features (albedo, normal, depth, coverage)
 RT_FLAG_RAY_DIFFERENTIALS = 128  # rt_render_rays / rt_frame_advance_rays* / rt_camera_rays: ray records of RT_RAY_DIFF_FLOATS floats (the ray, then rx_o, ry_o, rx_d, ry_d)
 RT_RAY_DIFF_FLOATS = 20
+RT_CAMERA_ORTHOGRAPHIC, RT_CAMERA_ENVIRONMENT = 1, 2  # rt_camera_model_rays / rt_frame_begin_model / rt_render_model: the camera models generated on the device
+RT_CAMERA_MODEL_FLOATS = 24
+CAMERA_MODELS = dict(orthographic=RT_CAMERA_ORTHOGRAPHIC, environment=RT_CAMERA_ENVIRONMENT)
 RT_FEATURE_FLOATS = 16
 RT_FEATURE_SAMPLES_MAX = 1 << 25
 RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
@@ -163,6 +166,36 @@ def look_at(pos, look, up):
     mi = np.zeros((4, 4), np.float32)
     lib().rtxh_look_at(_p(np.float32(pos)), _p(np.float32(look)), _p(np.float32(up)), _p(m), _p(mi))
     return m, mi
+
+
+def default_screen_window(width, height):
+    """pbrt's default screen window of a film of `width` x `height` pixels: the shorter axis spans [-1, 1] (float32 arithmetic, as rtxh_camera_model's)."""
+    a = np.float32(width) / np.float32(height)
+    if a > 1.0:
+        return (float(-a), float(a), -1.0, 1.0)
+    return (-1.0, 1.0, float(np.float32(-1.0) / a), float(np.float32(1.0) / a))
+
+
+def camera_model(kind, camera_to_world, width, height, screen_window=None, lens_radius=0, focal_distance=1e6):
+    """The RT_CAMERA_MODEL_FLOATS float32 of a camera model (rt_camera_model_rays, rt_frame_begin_model): camera_to_world (4 x 4, row-major, points as columns:
+    `look_at(pos, look, up)[1]`), the screen window (x0, x1, y0, y1) - None: pbrt's default from the aspect ratio width / height -, lens_radius, focal_distance and two
+    reserved zeros. `kind`: "orthographic" / "environment" (or the RT_CAMERA_* value). The environment camera reads neither window nor lens: its lens must be 0."""
+    if CAMERA_MODELS.get(kind, kind) not in CAMERA_MODELS.values():
+        raise BackendError(f"camera_model: unknown kind {kind!r} (orthographic, environment)")
+    out = np.zeros(RT_CAMERA_MODEL_FLOATS, np.float32)
+    out[:16] = np.asarray(camera_to_world, np.float32).reshape(16)
+    out[16:20] = default_screen_window(width, height) if screen_window is None else [float(v) for v in screen_window]
+    out[20] = lens_radius
+    out[21] = focal_distance
+    return out
+
+
+def _model_args(kind, camera):
+    model = CAMERA_MODELS.get(kind, kind)
+    cam = np.ascontiguousarray(camera, np.float32).reshape(-1)
+    if cam.size != RT_CAMERA_MODEL_FLOATS:
+        raise BackendError(f"a camera model is {RT_CAMERA_MODEL_FLOATS} floats (host.camera_model), not {cam.size}")
+    return int(model) if isinstance(model, (int, np.integer)) else -1, cam
 
 
 def screen_window_of(camera):
@@ -570,6 +603,84 @@ class HostScene:
                                   None if pf is None else pf.ctypes.data_as(C.c_void_p)), "camera_rays")
         return rays, pf
 
+    def camera_model_params(self, kind):
+        """`host.camera_model` filled from this scene's render parameters (rtxh_camera_model), such as a loaded pbrt scene's: camera-to-world, "screenwindow" or
+        pbrt's default from the film's aspect ratio, and - orthographic - "lensradius" / "focaldistance"."""
+        out = np.zeros(RT_CAMERA_MODEL_FLOATS, np.float32)
+        p = self._render_params()
+        _check(lib().rtxh_camera_model(C.byref(p), C.c_int32(int(CAMERA_MODELS.get(kind, kind))), _p(out)), "camera_model")
+        return out
+
+    def _model_params(self, spp, max_depth, **kw):
+        p = self._render_params(**kw)
+        if spp is not None:
+            p.spp = int(spp)
+        if max_depth is not None:
+            p.max_depth = int(max_depth)
+        return p
+
+    def camera_model_rays(self, kind, camera, sample0=0, n_samples=None, differentials=False, with_p_film=True, device_out=None, stream=0, spp=None):
+        """`camera_rays` for a camera model (rt_camera_model_rays): (rays (H, W, ns, 8 | 20) float32, p_film (H, W, ns, 2) or None) of the orthographic or environment
+        camera `camera` (`host.camera_model`) over the scene's film resolution, generated on the device from the pixel-keyed sampler: p_film is `camera_rays`' of a
+        film with these bounds, and the records are what a model frame (`progressive_model`) traces. `spp` (default: the scene's sampler's) sizes the tables and
+        scales the differentials; the other arguments as in `camera_rays`."""
+        model, cam = _model_args(kind, camera)
+        p = self._model_params(spp, None)
+        w, h = int(p.xres), int(p.yres)
+        r = 1
+        while r < max(int(p.spp), 1):
+            r *= 2
+        ns = r - int(sample0) if n_samples is None else int(n_samples)
+        rec = RT_RAY_DIFF_FLOATS if differentials else 8
+        if w <= 0 or h <= 0 or ns <= 0 or w * h * ns > RT_RAYS_MAX:
+            raise BackendError(f"camera_model_rays: {max(w, 0)} x {max(h, 0)} pixels x {ns} samples are none, or more than RT_RAYS_MAX rays - cut the job by sample range")
+        flags = RT_FLAG_RAY_DIFFERENTIALS if differentials else 0
+        L = lib()
+        L.rtxh_camera_model_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        pc = cam.ctypes.data_as(C.c_void_p)
+        if device_out is not None:
+            d_rays, d_pf = device_out if isinstance(device_out, (tuple, list)) else (device_out, None)
+            for t, shape in ((d_rays, (h, w, ns, rec)),) + (() if d_pf is None else ((d_pf, (h, w, ns, 2)),)):
+                if tuple(t.shape) != shape or not t.is_contiguous() or t.element_size() != 4:
+                    raise BackendError(f"camera_model_rays: device_out must be contiguous float32 of shape {shape}")
+            _check(L.rtxh_camera_model_rays(self.h, C.byref(p), model, pc, int(sample0), ns, flags | RT_FLAG_FILM_ON_DEVICE, C.c_void_p(stream), C.c_void_p(d_rays.data_ptr()),
+                                            None if d_pf is None else C.c_void_p(d_pf.data_ptr())), "camera_model_rays")
+            return d_rays, d_pf
+        rays = np.zeros((h, w, ns, rec), np.float32)
+        pf = np.zeros((h, w, ns, 2), np.float32) if with_p_film else None
+        _check(L.rtxh_camera_model_rays(self.h, C.byref(p), model, pc, int(sample0), ns, flags, C.c_void_p(stream), rays.ctypes.data_as(C.c_void_p),
+                                        None if pf is None else pf.ctypes.data_as(C.c_void_p)), "camera_model_rays")
+        return rays, pf
+
+    def progressive_model(self, kind, camera, spp=None, max_depth=None, differentials=False, rank=0, world_size=1, table_budget=None, pixel_stats=False, features=False,
+                          count_traversal=False, time_kernels=False):
+        """A progressive frame of the orthographic or environment camera `camera` (`host.camera_model`) whose steps generate their rays on the device
+        (rt_frame_begin_model): a ProgressiveFrame - `advance`, `advance_adaptive` and every read-out - over the scene's film resolution with its pixel filter, clamp and
+        film scale. No ray, film position or sample crosses the host bus. `differentials=True`: bounce 0 is shaded with the model's ray differentials on a scene that
+        reads them. The frame is the ray frame (`progressive_rays`) of `camera_model_rays`' records and positions, byte for byte."""
+        return ModelFrame(self, kind, camera, spp=spp, max_depth=max_depth, differentials=differentials, rank=rank, world_size=world_size, table_budget=table_budget,
+                          pixel_stats=pixel_stats, features=features, count_traversal=count_traversal, time_kernels=time_kernels)
+
+    def render_model(self, kind, camera, spp=None, max_depth=None, differentials=False, rank=0, world_size=1, device_out=None, stream=0, time_kernels=False):
+        """The finished frame of `progressive_model` in one call (rt_render_model): (film_xyzw (H, W, 4) float32, stats dict). `device_out`: a contiguous torch CUDA
+        float32 tensor (H, W, 4) that receives the film in HBM and is returned."""
+        model, cam = _model_args(kind, camera)
+        p = self._model_params(spp, max_depth, rank=rank, world_size=world_size)
+        p.flags = (RT_FLAG_RAY_DIFFERENTIALS if differentials else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        w, h = int(p.xres), int(p.yres)
+        L = lib()
+        L.rtxh_render_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if device_out is not None:
+            if tuple(device_out.shape) != (h, w, 4) or not device_out.is_contiguous() or device_out.element_size() != 4:
+                raise BackendError(f"render_model: device_out must be contiguous float32 of shape {(h, w, 4)}")
+            p.flags |= RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_model(self.h, C.byref(p), model, cam.ctypes.data_as(C.c_void_p), C.c_void_p(stream), C.c_void_p(device_out.data_ptr()), C.byref(stats)), "render_model")
+            return device_out, stats.as_dict()
+        film = np.zeros((h, w, 4), np.float32)
+        _check(L.rtxh_render_model(self.h, C.byref(p), model, cam.ctypes.data_as(C.c_void_p), C.c_void_p(stream), film.ctypes.data_as(C.c_void_p), C.byref(stats)), "render_model")
+        return film, stats.as_dict()
+
     def render_rays(self, rays, sample0=0, spp=None, max_depth=None, device_out=None, stream=0, count_traversal=False, time_kernels=False):
         """Path-traced radiance along caller-supplied rays (rt_render_rays): `rays` (H, W, ns, 8) float32 - o.xyz, t_max, d.xyz, unused; d is used as given -, returns
         (radiance (H, W, ns, 4), stats dict): L rgb as PathIntegrator::li returns it and a fourth float 0.0 / 1.0 (the renderer would scrub the sample) / 2.0 (t_max not
@@ -851,6 +962,29 @@ class RayFrame(ProgressiveFrame):
                                                       C.c_void_p(stream), C.byref(stats)), "frame_advance_rays_adaptive")
         del keep
         return stats.as_dict()
+
+
+class ModelFrame(ProgressiveFrame):
+    """A progressive frame of a camera model (HostScene.progressive_model; rt_frame_begin_model): ProgressiveFrame's `advance`, `advance_adaptive`, read-outs and
+    properties, with the orthographic or environment camera's rays generated on the device from the pixel-keyed sampler at every step."""
+
+    def __init__(self, scene, kind, camera, spp=None, max_depth=None, differentials=False, rank=0, world_size=1, table_budget=None, pixel_stats=False, features=False,
+                 count_traversal=False, time_kernels=False):
+        L = lib()
+        L.rtxh_frame_end.argtypes = [C.c_void_p]
+        L.rtxh_frame_begin_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
+        self.scene = scene   # (the frame's device state belongs to the scene's device: the scene must outlive it)
+        self.h = None
+        model, cam = _model_args(kind, camera)
+        p = scene._model_params(spp, max_depth, rank=rank, world_size=world_size)
+        self.width, self.height = int(p.xres), int(p.yres)
+        p.flags = ((RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0) | (RT_FLAG_FRAME_STATS if pixel_stats else 0) |
+                   (RT_FLAG_FRAME_FEATURES if features else 0) | (RT_FLAG_RAY_DIFFERENTIALS if differentials else 0))
+        self.scale = float(p.film_scale)
+        h = C.c_void_p()
+        _check(L.rtxh_frame_begin_model(scene.h, C.byref(p), model, cam.ctypes.data_as(C.c_void_p), C.c_uint64(0 if table_budget is None else max(int(table_budget), 1)),
+                                        C.byref(h)), "frame_begin_model")
+        self.h = h
 
 
 class MultiProgressiveFrame(ProgressiveFrame):

@@ -2,7 +2,7 @@
 
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
-                                  [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials]]
+                                  [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials] [--device-camera]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -29,7 +29,11 @@ file's PixelFilter, clamp and film scale, no sample travels back. Honours --prev
 --min-samples / --noise-floor / --sample-map, and --features; the PNG is RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights (RT_FRAME_SUMS). Without the flag --camera-model renders as before.
 --ray-differentials (with --camera-model, with or without --ray-frame): the rays carry the camera model's differentials (records of 20 floats, RT_FLAG_RAY_DIFFERENTIALS;
 pbrt-v3's GenerateRayDifferential of each camera, scaled by 1 / sqrt(spp)), so image maps, checkerboards, fbm and bump maps are filtered at the first hit as under the
-file's perspective camera. Opt-in: without it the rays have none and textures are looked up at zero width, as before."""
+file's perspective camera. Opt-in: without it the rays have none and textures are looked up at zero width, as before.
+--device-camera (with --camera-model): the camera's rays are generated on the device (rt_frame_begin_model) from the file's ZeroTwoSequence tables - film positions
+pixel + the sampler's 2D#0 instead of the script's seeded jitter (--seed is unused), the orthographic camera's "lensradius" / "focaldistance" as a thin lens from 2D#1 -
+and rendered through a model frame: nothing per sample crosses the host bus. Filtered as under --ray-frame (the file's PixelFilter, clamp and film scale; the PNG is
+RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights); honours --preview-every, --adaptive with its options, --features and --ray-differentials."""
 import argparse
 import os
 import sys
@@ -130,6 +134,26 @@ def render_camera_model_frame(s, model, seed=0, preview_every=0, adaptive=None, 
                     counts=frame.pixel_stats()[0] if adaptive is not None else None, features=frame.features() if features else None)
 
 
+def render_device_camera_frame(s, model, preview_every=0, adaptive=None, noise_floor=1e-3, min_samples=8, features=False, on_step=None, differentials=False):
+    """--camera-model --device-camera: the scene through a model frame (`HostScene.progressive_model`) whose camera is filled from the file's render parameters
+    (`HostScene.camera_model_params`). Steps of `preview_every` samples (0: the whole frame; 4 under `adaptive`); `on_step(frame)` after each. Returns what
+    `render_camera_model_frame` returns."""
+    stats = dict(ms_total=0.0, camera_rays=0, paths_scrubbed=0)
+    with s.progressive_model(model, s.camera_model_params(model), differentials=differentials, pixel_stats=adaptive is not None, features=features) as frame:
+        spp = frame.spp
+        step = preview_every if preview_every > 0 else (4 if adaptive is not None else spp)
+        while frame.samples_done < spp:
+            st = frame.advance(step) if adaptive is None else frame.advance_adaptive(step, adaptive, noise_floor, min_samples)
+            for k in stats:
+                stats[k] += st[k]
+            if adaptive is not None and frame.active_pixels == 0:
+                break
+            if on_step is not None:
+                on_step(frame)
+        return dict(rgb=frame_rgb(frame), png8=frame.display(), stats=stats, samples_done=frame.samples_done, samples_taken=frame.samples_taken, spp=spp,
+                    counts=frame.pixel_stats()[0] if adaptive is not None else None, features=frame.features() if features else None)
+
+
 def main():
     from rustracer_amd import host
     from rustracer_amd.ingest import write_pfm, write_png
@@ -141,6 +165,8 @@ def main():
                     help="with --camera-model: filter the samples on the device through a ray frame (rt_frame_advance_rays) with the file's PixelFilter, in steps")
     ap.add_argument("--ray-differentials", action="store_true",
                     help="with --camera-model: the rays carry the camera model's differentials (RT_FLAG_RAY_DIFFERENTIALS), so textures are filtered at the first hit")
+    ap.add_argument("--device-camera", action="store_true",
+                    help="with --camera-model: generate the camera's rays on the device from the file's sampler (rt_frame_begin_model) and render through a model frame")
     ap.add_argument("scene")
     ap.add_argument("out", nargs="?")
     ap.add_argument("--spp", type=int, default=0, help="override Sampler pixelsamples")
@@ -171,10 +197,12 @@ def main():
         raise SystemExit("--ray-frame goes with --camera-model")
     if a.ray_differentials and not a.camera_model:
         raise SystemExit("--ray-differentials goes with --camera-model")
-    if a.camera_model and a.ray_frame:
+    if a.device_camera and not a.camera_model:
+        raise SystemExit("--device-camera goes with --camera-model")
+    if a.camera_model and (a.ray_frame or a.device_camera):
         import numpy as np
         if a.devices:
-            raise SystemExit("--ray-frame renders on one device")
+            raise SystemExit("--ray-frame and --device-camera render on one device")
 
         def put(rgb, png8):
             if out.endswith(".pfm"):
@@ -186,8 +214,9 @@ def main():
             put(frame_rgb(frame), frame.display())
             print(f"{out}: {frame.samples_done} / {frame.spp} samples per pixel" + (f", {frame.active_pixels} pixels active" if a.adaptive is not None else ""), flush=True)
 
-        r = render_camera_model_frame(s, a.camera_model, a.seed, preview_every=a.preview_every, adaptive=a.adaptive, noise_floor=a.noise_floor, min_samples=a.min_samples,
-                                      features=bool(a.features), on_step=preview if a.preview_every > 0 else None, differentials=a.ray_differentials)
+        kw = dict(preview_every=a.preview_every, adaptive=a.adaptive, noise_floor=a.noise_floor, min_samples=a.min_samples, features=bool(a.features),
+                  on_step=preview if a.preview_every > 0 else None, differentials=a.ray_differentials)
+        r = render_device_camera_frame(s, a.camera_model, **kw) if a.device_camera else render_camera_model_frame(s, a.camera_model, a.seed, **kw)
         put(r["rgb"], r["png8"])
         if a.adaptive is not None:
             full = int(np.count_nonzero(r["counts"])) * r["spp"]
@@ -198,7 +227,7 @@ def main():
             np.save(a.features, r["features"])
             print(f"{a.features}: {r['features'].shape[1]}x{r['features'].shape[0]} x (albedo rgb, normal xyz, depth, coverage), mean coverage {float(r['features'][..., 7].mean()):.3f}")
         stats = r["stats"]
-        print(f"{out}: {r['rgb'].shape[1]}x{r['rgb'].shape[0]}, {a.camera_model} camera through a ray frame, {stats['camera_rays']} rays, {stats['paths_scrubbed']} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
+        print(f"{out}: {r['rgb'].shape[1]}x{r['rgb'].shape[0]}, {a.camera_model} camera through a {'model' if a.device_camera else 'ray'} frame, {stats['camera_rays']} rays, {stats['paths_scrubbed']} scrubbed, {stats['ms_total']:.1f} ms, {s.n_warnings} parser warnings")
         return
     if a.camera_model:
         rgb, stats = render_camera_model(s, a.camera_model, a.seed, differentials=a.ray_differentials)
