@@ -696,6 +696,10 @@ int rt_shadow_sets(const rt_scene_desc* desc, uint32_t* words, uint64_t capacity
 /* sizeof() of an ABI struct by its C name ("rt_stats", "rt_scene_desc", ...), or -1: lets a binding in another language check its mirror of the
  * header against the library it actually loaded (rustracer_amd/host.py does at load time; tests/test_abi_cpu.py checks every struct). */
 int rt_sizeof(const char* struct_name);
+/* The byte offsets at which the shade kernels' vertex bodies read their arguments in the kernarg segment (RT_SHADE_KARGS): out[0..2] = the scene
+ * record, the frame parameters and the pass state (the same in k_shade, k_shade_split and k_shade_rays), out[3] = k_shade_split's hit-mask pointer, out[4] =
+ * k_shade_rays' ray-differential source. tests/test_shade_kargs_cpu.py holds them to the argument metadata of the built code object. */
+void rt_shade_karg_offsets(uint32_t out[5]);
 
 const char* rt_last_error(void);
 /* 1 if a gfx950 device is visible to this process, else 0 (never falls back to a CPU path). */

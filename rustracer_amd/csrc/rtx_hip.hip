@@ -126,6 +126,7 @@ struct rt_scene {
 };
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
+extern "C" void rt_shade_karg_offsets(unsigned out[5]) { rtx::rtx_shade_karg_offsets(out); }
 extern "C" const char* rt_version(void) { return "rtx-mi355x 0.5 (gfx950 wavefront path tracer)"; }
 extern "C" int rt_sizeof(const char* name) {
   if (!name) return -1;
@@ -1233,6 +1234,9 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
   // of a pass that traces every sample is shaded by k_shade_split<1> - k_raygen then writes neither the throughput nor the state record - and every later bounce by
   // k_shade_split<2>. RTX_SHADE_SPLIT=0 (measurement knob, read per call): k_shade<1, .., 1> for every bounce, no masks, raygen as before.
   const bool shade_split = s->lambert_only && s->lds_records && closest_is_k_trace(s, (flags & RT_FLAG_COUNT_TRAVERSAL) != 0) && !env_is("RTX_SHADE_SPLIT", '0');
+  // RTX_SHADE_KARGS=0 (measurement knob, read per call): such a scene's three shade kernels in the form that keeps the kernel arguments live through the vertex (the
+  // control of round 10: k_shade_const_live, k_shade_split_live); the other front-ends have one form, chosen at compile time (RT_SHADE_KARGS)
+  const bool shade_live_args = env_is("RTX_SHADE_KARGS", '0');
   const unsigned long long table_bytes_per_pixel = 2ull * dims * spp * 2ull;
 
   const bool resident = fr && fr->resident;                   // the sampler tables of every batch live in the frame ...
@@ -1509,8 +1513,8 @@ static int render_frame(rt_scene* s, const rt_camera* cam, const rt_film_desc* f
                                                                                  : launch_shade<MODE>(gshade, lean_shade, bounce >= 1, sgrid, sblock, stream, dsc, fp, P, qlights, lds_shade))
         if (s->lambert_only) {
           tm.begin(&stats.ms_shade_lambert_const);
-          if (split_launch) rtx_launch_shade_split(bounce == 0, sgrid, stream, dsc, fp, ps, io_path.hit_mask);
-          else rtx_launch_shade_const(s->lds_records ? 1 : (s->lds_tables ? 3 : 0), sgrid, sblock, stream, dsc, fp, ps);  // LDSREC 3: a large mesh with few lights / materials (S2)
+          if (split_launch) rtx_launch_shade_split(bounce == 0, sgrid, stream, dsc, fp, ps, io_path.hit_mask, shade_live_args);
+          else rtx_launch_shade_const(s->lds_records ? 1 : (s->lds_tables ? 3 : 0), sgrid, sblock, stream, dsc, fp, ps, shade_live_args);  // LDSREC 3: a large mesh with few lights / materials (S2)
           tm.end(); stats.launches_shade += 1;
         }
         else if (s->lambert_materials) { tm.begin(&stats.ms_shade_lambert); RT_SHADE(3, ps); tm.end(); }

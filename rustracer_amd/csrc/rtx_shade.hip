@@ -47,15 +47,21 @@ void rtx_launch_shade(int mode, bool general, bool lean, bool bounced, unsigned 
     default: launch_shade_t<0>(general, lean, bounced, grid, block, stream, d, fp, p, qlights, lds); break;
   }
 }
-void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p) {
-  if (ldsrec == 1) hipLaunchKernelGGL((k_shade<1, false, false, false, false, 1>), dim3(grid), dim3(block), 0, stream, d, fp, p);
+void rtx_launch_shade_const(int ldsrec, unsigned grid, unsigned block, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, bool live_args) {
+  if (ldsrec == 1 && live_args) hipLaunchKernelGGL(k_shade_const_live<1>, dim3(grid), dim3(block), 0, stream, d, fp, p);
+  else if (ldsrec == 1) hipLaunchKernelGGL((k_shade<1, false, false, false, false, 1>), dim3(grid), dim3(block), 0, stream, d, fp, p);
   else if (ldsrec == 3) hipLaunchKernelGGL((k_shade<1, false, false, false, false, 3>), dim3(grid), dim3(block), 0, stream, d, fp, p);
   else hipLaunchKernelGGL(k_shade<1>, dim3(grid), dim3(block), 0, stream, d, fp, p);
 }
-void rtx_launch_shade_split(bool camera, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const unsigned long long* hit_mask) {
-  if (camera) hipLaunchKernelGGL(k_shade_split<RT_SPLIT_CAMERA>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
+void rtx_launch_shade_split(bool camera, unsigned grid, hipStream_t stream, const DScene& d, const FrameParams& fp, const PassState& p, const unsigned long long* hit_mask, bool live_args) {
+  if (live_args) {  // (RTX_SHADE_KARGS=0: the control)
+    if (camera) hipLaunchKernelGGL(k_shade_split_live<RT_SPLIT_CAMERA>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
+    else hipLaunchKernelGGL(k_shade_split_live<RT_SPLIT_BOUNCED>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
+  }
+  else if (camera) hipLaunchKernelGGL(k_shade_split<RT_SPLIT_CAMERA>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
   else hipLaunchKernelGGL(k_shade_split<RT_SPLIT_BOUNCED>, dim3(grid), dim3(256), 0, stream, d, fp, p, hit_mask);
 }
+void rtx_shade_karg_offsets(unsigned out[5]) { out[0] = RT_KARG_SC; out[1] = RT_KARG_FP; out[2] = RT_KARG_PS; out[3] = RT_KARG_HIT_MASK; out[4] = RT_KARG_RDIFF; }
 // ---- rt_bsdf_eval (rtx_hip.h): the front-end structs above on hand-made surface records. One lane per query builds the Bsdf of the material at its record the way
 // shade_vertex does (the generic front-end takes the scene record in device memory, the others the kernel argument) and evaluates f, pdf and sample_f over all lobes.
 RT_DEV int front_end_lobes(const GenericBsdf& b) { return b.b.n; }

@@ -3,6 +3,7 @@
 // existed (as a __device__ template the same text gave k_shade<1, .., 1> and k_shade<1, .., 3> two more spilled dwords each: the arrays' names order the LDS layout).
 // Expects: MODE, GENERAL, LEAN, BOUNCED, QLIGHTS, LDSREC, SPLIT (constants), sc, fp, ps (the kernel's arguments) and hit_mask (the split kernels' argument, else NULL);
 // RAYDIFF (constant) and rdiff (RayDiffSrc): k_shade_rays takes a camera vertex's differentials from the caller's ray records; false and unread in every other kernel.
+// KARGS (constant): the vertex body re-reads sc, fp, ps (and rdiff) from the kernarg segment instead of keeping the entry block's copies live (RT_SHADE_KARGS, below).
   static_assert(SPLIT == RT_SPLIT_NONE || (MODE == 1 && LDSREC == 1), "the split kernels are forms of k_shade<1, .., LDSREC = 1>");
   // LDSREC (MODE 1, round 5): a scene of <= RT_SMALL_TRIS triangles and <= RT_LDS_LIGHTS emitters keeps its shade records, traversal records and light table in LDS
   // for the launch. k_shade<1> is busy issuing VALU instructions half of the time and waits for memory two thirds of a wave's life (SQ counters), yet neither ~10 % fewer
@@ -37,24 +38,43 @@
   // also GATHERS from tables larger than a cache (triangle records, texels, environment rows - the hint keeps the streams from evicting them: S4 shade 2489 -> 2325 ms, S2
   // 22.0 -> 20.6, S3 117.6 -> 114.3); without it where every table sits in LDS and the streams are all the launch reads (LDSREC == 1: S1 shade 219 -> 234 ms WITH the hint).
   constexpr bool NTK = LDSREC != 1;
-  const auto in_o = sp<NTK>(ps.in.o), in_d = sp<NTK>(ps.in.d), in_beta = sp<NTK>(ps.in.beta); const auto in_st = sp<NTK>(ps.in.st); const auto pfilm_ = sp<NTK>(ps.pfilm);
-  const auto out_o = sp<NTK>(ps.out.o), out_d = sp<NTK>(ps.out.d), out_beta = sp<NTK>(ps.out.beta); const auto out_st = sp<NTK>(ps.out.st);
-  const auto sh_o = sp<NTK>(ps.sh.o), sh_d = sp<NTK>(ps.sh.d), sh_add = sp<NTK>(ps.sh.add);
-  const auto mi_o = sp<NTK>(ps.mi.o), mi_d = sp<NTK>(ps.mi.d), mi_a = sp<NTK>(ps.mi.a), mi_b = sp<NTK>(ps.mi.b), mi_c = sp<NTK>(ps.mi.c); const auto mi_flags = sp<NTK>(ps.mi.flags);
   constexpr bool CAMERA = SPLIT == RT_SPLIT_CAMERA;
   QView qv; if (ps.cnt_in) qv.init(ps.q_in, ps.cnt_in, ps.shard_cap);
   unsigned first = 0, count = ps.cnt_in ? qv.total() : ps.cap;  // no counts: bounce 0 of a pass whose samples are all traced (entry i = slot i = path i)
   if (MODE != 1 && ps.range) { first = ps.range[0]; count = ps.range[1]; }
   const unsigned stride = gridDim.x * blockDim.x;
   unsigned n_shaded = 0, n_unreached = 0, n_tail = 0, n_no_walk = 0;
-  const DScene& gsc = *sc.self;  // what out-of-line functions get: the scene record in device memory, not a private copy of the kernel argument
 #ifdef RT_ABLATE
   unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = clock64();
 #endif
   // one vertex per lane: entry i of the launch's queue, its records at slot rslot. Must be reached by every thread of the workgroup (the queue appends at its
   // end are workgroup-wide).
-  auto shade_vertex = [&](const bool lane_live, const unsigned i, const unsigned rslot) {
+  // KARGS (RT_SHADE_KARGS, round 10): every vertex re-reads the kernel's arguments from the kernarg segment. Taken by value they are loaded in the entry block and
+  // whatever a vertex reads of them - a few hundred scalars - is hoisted out of the persistent loop and live through the whole vertex body: the allocator parks
+  // 123 - 337 of them in lanes of vector registers (v_writelane / v_readlane), and those three or more vector registers are what pushes vector values over the
+  // kernel's register bound into scratch. Behind the empty asm the pointer is opaque, so the loads (scalar, constant address space: ~45 more s_load per 256-vertex
+  // iteration) stay inside the vertex and each field lives from its reload to its last use. Same values, same arithmetic. The LDS overrides above are re-applied.
+  const DScene& sc_k = sc; const FrameParams& fp_k = fp; const PassState& ps_k = ps; const RayDiffSrc& rdiff_k = rdiff;
+  auto shade_vertex = [&](const bool lane_live, const unsigned i, const unsigned rslot) __attribute__((always_inline)) {  // (two call sites in the compacting forms: with the asm in it the inliner would leave it a function)
     RT_STAMP(7);  // loop overhead / previous iteration's tail
+    // (k_shade_rays keeps the pass state live: with all four re-read its GENERAL forms of front-ends 3 and 5 take 232 / 255 VGPRs, one more than their k_shade siblings
+    // - tests/test_ray_differentials_cpu.py bounds them by the sibling's count -, with ps live 230 / 253 and not a spilled dword more in any of the eight)
+    constexpr bool KARGS_PS = KARGS && !RAYDIFF;
+    DScene sc_r; FrameParams fp_r; PassState ps_r; RayDiffSrc rdiff_r{};
+    if constexpr (KARGS) {
+      const RT_KARG_AS char* ka = shade_kargs();
+      sc_r = shade_karg<DScene>(ka, RT_KARG_SC); fp_r = shade_karg<FrameParams>(ka, RT_KARG_FP); if constexpr (KARGS_PS) ps_r = shade_karg<PassState>(ka, RT_KARG_PS);
+      if constexpr (RAYDIFF) rdiff_r = shade_karg<RayDiffSrc>(ka, RT_KARG_RDIFF);  // (re-read at its one use instead, it costs k_shade_rays<6, true> 4 spilled dwords)
+      if (LDSREC == 1) { sc_r.tri_rec = (const float4*)s_rec; sc_r.tri_p = (const float4*)s_trip; }
+      if (LDSREC == 1 || LDSREC == 3) sc_r.lights = (const DLight*)s_lights;
+      if (LDSREC) { sc_r.materials = (const DMaterial*)s_mats; sc_r.textures = (const DTexture*)s_texs; }
+    }
+    const DScene& sc = KARGS ? sc_r : sc_k; const FrameParams& fp = KARGS ? fp_r : fp_k; const PassState& ps = KARGS_PS ? ps_r : ps_k; const RayDiffSrc& rdiff = (KARGS && RAYDIFF) ? rdiff_r : rdiff_k;
+    const DScene& gsc = *sc.self;  // what out-of-line functions get: the scene record in device memory, not a private copy of the kernel argument
+    const auto in_o = sp<NTK>(ps.in.o), in_d = sp<NTK>(ps.in.d), in_beta = sp<NTK>(ps.in.beta); const auto in_st = sp<NTK>(ps.in.st); const auto pfilm_ = sp<NTK>(ps.pfilm);
+    const auto out_o = sp<NTK>(ps.out.o), out_d = sp<NTK>(ps.out.d), out_beta = sp<NTK>(ps.out.beta); const auto out_st = sp<NTK>(ps.out.st);
+    const auto sh_o = sp<NTK>(ps.sh.o), sh_d = sp<NTK>(ps.sh.d), sh_add = sp<NTK>(ps.sh.add);
+    const auto mi_o = sp<NTK>(ps.mi.o), mi_d = sp<NTK>(ps.mi.d), mi_a = sp<NTK>(ps.mi.a), mi_b = sp<NTK>(ps.mi.b), mi_c = sp<NTK>(ps.mi.c); const auto mi_flags = sp<NTK>(ps.mi.flags);
     bool cont = false, want_shadow = false, want_mis = false, mis_occlusion_only = false, tail = false, no_walk = false;
     // what a continuing path takes to its slot in the next bounce's queue (stored after the append below has named the slot)
     f3 nr_o = mk3(0, 0, 0), nr_d = mk3(0, 0, 0); rgb3 beta = mkc(0, 0, 0); float eta_scale = 1.0f; unsigned st_out = 0u, pid = 0u; unsigned long long rng_out = 0ull;
@@ -309,6 +329,8 @@
       { const unsigned wb = base + 64u * wv; n_shaded += wb < count ? (count - wb < 64u ? count - wb : 64u) : 0u; }  // (the WAVE's entries, a scalar: a per-lane count is a vector register live through every vertex - 7 / 6 spilled dwords instead of 3 / 4)
       const unsigned w0 = base >> 6;
       unsigned before = 0, total = 0; unsigned long long m = 0ull;
+      // (KARGS, measured on the allocation and not kept: hit_mask re-read here like the other arguments - the pointer is then no longer __restrict__ and the four
+      // mask words become vector loads: k_shade_split<1> / <2> 49 / 66 more VALU instructions, 0 / 3 fewer spilled scalars, nothing else moves)
 #pragma unroll
       for (unsigned w = 0; w < 4u; ++w) {
         const unsigned long long mw = w0 + w < n_words ? hit_mask[w0 + w] : 0ull;

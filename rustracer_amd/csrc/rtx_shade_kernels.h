@@ -341,10 +341,55 @@ RT_DEV auto instance_interaction_visit(const DScene& sc, unsigned hit_id, f3 o, 
 #define RT_SPLIT_NONE 0
 #define RT_SPLIT_CAMERA 1
 #define RT_SPLIT_BOUNCED 2
+// RT_SHADE_KARGS (round 10, rtx_shade_body.inl: KARGS): 1 - every shade kernel's vertex body re-reads the kernel's arguments from the kernarg segment; 0 (make
+// EXTRA=-DRT_SHADE_KARGS=0) - the entry block's copies stay live through the vertex, as before. The kernels' arguments as the kernarg segment lays them out: each at the
+// next multiple of its alignment, which is how a struct of the same members is laid out. rt_shade_karg_offsets (rtx_hip.h) exports the offsets and
+// tests/test_shade_kargs_cpu.py holds them to the `.offset` entries of the built kernels' argument metadata.
+#ifndef RT_SHADE_KARGS
+#define RT_SHADE_KARGS 1
+#endif
+struct ShadeKArgs { DScene sc; FrameParams fp; PassState ps; };                                            // k_shade
+struct ShadeSplitKArgs { DScene sc; FrameParams fp; PassState ps; const unsigned long long* hit_mask; };  // k_shade_split
+struct ShadeRaysKArgs { DScene sc; FrameParams fp; PassState ps; RayDiffSrc rdiff; };                     // k_shade_rays
+#define RT_KARG_SC ((unsigned)offsetof(ShadeKArgs, sc))
+#define RT_KARG_FP ((unsigned)offsetof(ShadeKArgs, fp))
+#define RT_KARG_PS ((unsigned)offsetof(ShadeKArgs, ps))
+#define RT_KARG_HIT_MASK ((unsigned)offsetof(ShadeSplitKArgs, hit_mask))
+#define RT_KARG_RDIFF ((unsigned)offsetof(ShadeRaysKArgs, rdiff))
+static_assert(offsetof(ShadeSplitKArgs, ps) == offsetof(ShadeKArgs, ps) && offsetof(ShadeRaysKArgs, ps) == offsetof(ShadeKArgs, ps) && offsetof(ShadeSplitKArgs, fp) == offsetof(ShadeKArgs, fp) &&
+              offsetof(ShadeRaysKArgs, fp) == offsetof(ShadeKArgs, fp), "the three signatures share their first three arguments");
+#define RT_KARG_AS __attribute__((address_space(4)))
+// the kernarg segment's address behind an empty asm: what is loaded through it cannot be hoisted over the asm, and stays a scalar load from the constant address space
+// (the host pass only parses the kernels)
+RT_DEV const RT_KARG_AS char* shade_kargs() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const RT_KARG_AS char* p = (const RT_KARG_AS char*)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p)); return p;
+#else
+  return nullptr;
+#endif
+}
+// one argument out of the segment: word loads through the constant address space, unrolled (the words nothing reads are never loaded), then a bit cast
+template <class T> RT_DEV T shade_karg(const RT_KARG_AS char* ka, unsigned offset) {
+  static_assert(sizeof(T) % 4 == 0 && alignof(T) >= 4 && std::is_trivially_copyable<T>::value, "an argument is copied by words");
+  struct Words { unsigned w[sizeof(T) / 4]; } r;
+  const RT_KARG_AS unsigned* s = (const RT_KARG_AS unsigned*)(ka + offset);
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(T) / 4; ++k) r.w[k] = s[k];
+  return __builtin_bit_cast(T, r);
+}
 template <int MODE, bool GENERAL = false, bool LEAN = false, bool BOUNCED = false, bool QLIGHTS = false, int LDSREC = 0>
 __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN || BOUNCED) ? (BOUNCED ? RT_SHADE_BOUNCED_MIN_WAVES : RT_SHADE_LEAN_MIN_WAVES) : RT_SHADE_MIN_WAVES) : (MODE == 3 && !GENERAL ? RT_SHADE3_MIN_WAVES : ((MODE == 5 || MODE == 6) && !GENERAL ? RT_SHADE56_MIN_WAVES : (MODE != 0 && GENERAL ? RT_SHADE_GEN_MIN_WAVES : RT_SHADE0_MIN_WAVES)))) k_shade(DScene sc, FrameParams fp, PassState ps) {
   constexpr int SPLIT = RT_SPLIT_NONE; const unsigned long long* const hit_mask = nullptr;
   constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{};
+  constexpr bool KARGS = RT_SHADE_KARGS != 0;
+#include "rtx_shade_body.inl"
+}
+// The control of S1's frames (RTX_SHADE_KARGS=0, read per render call): k_shade<1, .., LDSREC = 1> and the two split kernels below with the arguments kept live, as they
+// were before round 10, under names of their own.
+template <int LDSREC>
+__global__ void __launch_bounds__(256, RT_SHADE_MIN_WAVES) k_shade_const_live(DScene sc, FrameParams fp, PassState ps) {
+  constexpr int MODE = 1, SPLIT = RT_SPLIT_NONE; constexpr bool GENERAL = false, LEAN = false, BOUNCED = false, QLIGHTS = false; const unsigned long long* const hit_mask = nullptr;
+  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{}; constexpr bool KARGS = false;
 #include "rtx_shade_body.inl"
 }
 // The two kernels of such a frame: the same body under the same four-wave bound, hit_mask = the words the bounce's k_trace launch wrote.
@@ -353,11 +398,18 @@ __global__ void __launch_bounds__(256, (MODE == 1 || LEAN || BOUNCED) ? ((LEAN |
 // every return path of that function (mk_ls(.., 0u) three times, the wo.z == 0 return): the scene has no specular lobe, the condition is false at every vertex of these launches.
 // Measured on the allocation and not kept (128 VGPRs, spilled dwords; k_shade<1, .., 1>: 4): k_shade_split<2> with the two records loaded without the launch-uniform
 // select 25, with its queue view known at compile time 27, both 32; k_shade_split<1> without the scheduling barrier behind its record loads 27 - 31 (all with a per-lane
-// n_shaded, which alone cost both kernels three dwords). As they stand: 3 and 4.
+// n_shaded, which alone cost both kernels three dwords). As they stood: 3 and 4; with the arguments re-read per vertex (RT_SHADE_KARGS, round 10) 0 and 0, and of those forms
+// the unconditional loads and the barrier-free camera kernel then fit with nothing spilled but measure no gain (MEASUREMENTS R10).
 template <int SPLIT>
 __global__ void __launch_bounds__(256, RT_SHADE_MIN_WAVES) k_shade_split(DScene sc, FrameParams fp, PassState ps, const unsigned long long* __restrict__ hit_mask) {
   constexpr int MODE = 1, LDSREC = 1; constexpr bool GENERAL = false, LEAN = false, BOUNCED = false, QLIGHTS = false;
-  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{};
+  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{}; constexpr bool KARGS = RT_SHADE_KARGS != 0;
+#include "rtx_shade_body.inl"
+}
+template <int SPLIT>  // (the control, see k_shade_const_live)
+__global__ void __launch_bounds__(256, RT_SHADE_MIN_WAVES) k_shade_split_live(DScene sc, FrameParams fp, PassState ps, const unsigned long long* __restrict__ hit_mask) {
+  constexpr int MODE = 1, LDSREC = 1; constexpr bool GENERAL = false, LEAN = false, BOUNCED = false, QLIGHTS = false;
+  constexpr bool RAYDIFF = false; constexpr RayDiffSrc rdiff{}; constexpr bool KARGS = false;
 #include "rtx_shade_body.inl"
 }
 // Bounce 0 of a call or ray-frame step whose rays carry differentials (RT_FLAG_RAY_DIFFERENTIALS, rtx_shade_rays.hip): the plain / GENERAL, LDSREC = 0 form of k_shade<MODE>
@@ -365,7 +417,7 @@ __global__ void __launch_bounds__(256, RT_SHADE_MIN_WAVES) k_shade_split(DScene 
 // of regenerating the perspective camera's. MODE 0, 3, 5, 6: the forms that can see a camera vertex and read differentials.
 template <int MODE, bool GENERAL>
 __global__ void __launch_bounds__(256, MODE == 3 && !GENERAL ? RT_SHADE3_MIN_WAVES : ((MODE == 5 || MODE == 6) && !GENERAL ? RT_SHADE56_MIN_WAVES : (MODE != 0 && GENERAL ? RT_SHADE_GEN_MIN_WAVES : RT_SHADE0_MIN_WAVES))) k_shade_rays(DScene sc, FrameParams fp, PassState ps, RayDiffSrc rdiff) {
-  constexpr int SPLIT = RT_SPLIT_NONE, LDSREC = 0; constexpr bool LEAN = false, BOUNCED = false, QLIGHTS = false, RAYDIFF = true; const unsigned long long* const hit_mask = nullptr;
+  constexpr int SPLIT = RT_SPLIT_NONE, LDSREC = 0; constexpr bool LEAN = false, BOUNCED = false, QLIGHTS = false, RAYDIFF = true; const unsigned long long* const hit_mask = nullptr; constexpr bool KARGS = RT_SHADE_KARGS != 0;
 #include "rtx_shade_body.inl"
 }
 
