@@ -60,7 +60,7 @@ def lib():
         L.orc_scene_free.argtypes = [C.c_void_p]
         for name in ("orc_scene_set_mesh", "orc_scene_add_mipmap", "orc_scene_add_texture", "orc_scene_add_material",
                      "orc_scene_add_light", "orc_scene_add_object", "orc_scene_object_emitter", "orc_scene_object_quadric_emitter", "orc_scene_add_instance", "orc_scene_commit", "orc_scene_bvh_sizes", "orc_scene_bvh_get", "orc_trace",
-                     "orc_render", "orc_light_distrib", "orc_li_keyed", "orc_camera_film_setup"):
+                     "orc_render", "orc_light_distrib", "orc_li_keyed", "orc_li_keyed_range", "orc_camera_film_setup"):
             getattr(L, name).restype = C.c_int
         L.orc_radical_inverse.restype = C.c_float
         L.orc_radical_inverse.argtypes = [C.c_int, C.c_uint64]
@@ -259,10 +259,17 @@ class OracleScene:
         assert rc == 0
         return film, stats.as_dict()
 
-    def li_keyed(self, px, py, sample):
+    def li_keyed(self, px, py, sample, n=None, mis_mode=0):
+        """PathIntegrator::li of sample `sample` of pixel (px, py) in KEYED mode, (3,); with `n`: of the samples [sample, sample + n), (n, 3). mis_mode: the test
+        hook of `render` (1: light sampling alone, 2: BSDF sampling alone in estimate_direct)."""
         p = render_params(self.desc, 1)
-        out = np.zeros(3, np.float32)
-        lib().orc_li_keyed(self.h, C.byref(p), px, py, sample, _p(out))
+        p.mis_mode = int(mis_mode)
+        if n is None:
+            out = np.zeros(3, np.float32)
+            lib().orc_li_keyed(self.h, C.byref(p), px, py, sample, _p(out))
+            return out
+        out = np.zeros((int(n), 3), np.float32)
+        lib().orc_li_keyed_range(self.h, C.byref(p), int(px), int(py), int(sample), int(n), _p(out))
         return out
 
     def light_distrib(self, max_voxels=None):

@@ -666,8 +666,8 @@ int orc_film_to_rgb(const float* film_xyzw, int64_t n_pixels, float scale, float
   return 0;
 }
 
-// Single-path probe (tests/debug): radiance of one (pixel, sample) in KEYED mode.
-int orc_li_keyed(void* h, const orc_render_params* p, int px, int py, int sample, float* rgb_out) {
+// Single-path probe (tests/debug): radiance of samples [sample0, sample0 + n) of one pixel in KEYED mode, 3 floats each.
+int orc_li_keyed_range(void* h, const orc_render_params* p, int px, int py, int sample0, int n, float* rgb_out) {
   Scene* s = (Scene*)h;
   Filter f; f.kind = p->filter_kind; f.xw = p->filter_params[0]; f.yw = p->filter_params[1]; f.a = p->filter_params[2]; f.b = p->filter_params[3];
   Film film; film.init(p->xres, p->yres, p->crop, f, p->film_scale, p->max_sample_luminance);
@@ -676,20 +676,27 @@ int orc_li_keyed(void* h, const orc_render_params* p, int px, int py, int sample
   if (p->screen_window[1] > p->screen_window[0]) memcpy(sw, p->screen_window, 16);
   cam.init(c2w, sw, p->lens_radius, p->focal_distance, p->fov, p->xres, p->yres);
   LightDistribution distrib; distrib.init(s, p->light_strategy == 1 ? "uniform" : "spatial");
-  PathIntegrator integ; integ.scene = s; integ.distrib = &distrib; integ.max_depth = (int)(uint8_t)p->max_depth; integ.rr_threshold = p->rr_threshold;
+  PathIntegrator integ; integ.scene = s; integ.distrib = &distrib; integ.max_depth = (int)(uint8_t)p->max_depth; integ.rr_threshold = p->rr_threshold; integ.mis_mode = p->mis_mode;
   B2i sb = film.sample_bounds();
   ZeroTwoSequence sampler; sampler.init((uint32_t)p->spp, (uint32_t)p->sampler_dims, SAMPLER_KEYED);
   uint64_t pixel_index = (uint64_t)(py - sb.y0) * (uint64_t)(sb.x1 - sb.x0) + (uint64_t)(px - sb.x0);
   sampler.start_pixel(pixel_index);
-  for (int i = 0; i < sample; ++i) sampler.start_next_sample();
-  P2 o = sampler.get_2d(); P2 p_film{(float)px + o.x, (float)py + o.y};
-  (void)sampler.get_1d(); P2 p_lens = sampler.get_2d();
-  Ray ray = cam.generate_ray_differential(p_film, p_lens);
-  scale_differentials(ray, 1.0f / sqrtf((float)sampler.spp));
-  PathStats st;
-  RGB c = integ.li(ray, sampler, st);
-  rgb_out[0] = c.r; rgb_out[1] = c.g; rgb_out[2] = c.b;
+  for (int i = 0; i < sample0; ++i) sampler.start_next_sample();
+  for (int k = 0; k < n; ++k) {
+    if (k > 0) sampler.start_next_sample();
+    P2 o = sampler.get_2d(); P2 p_film{(float)px + o.x, (float)py + o.y};
+    (void)sampler.get_1d(); P2 p_lens = sampler.get_2d();
+    Ray ray = cam.generate_ray_differential(p_film, p_lens);
+    scale_differentials(ray, 1.0f / sqrtf((float)sampler.spp));
+    PathStats st;
+    RGB c = integ.li(ray, sampler, st);
+    rgb_out[3 * k] = c.r; rgb_out[3 * k + 1] = c.g; rgb_out[3 * k + 2] = c.b;
+  }
   return 0;
+}
+
+int orc_li_keyed(void* h, const orc_render_params* p, int px, int py, int sample, float* rgb_out) {
+  return orc_li_keyed_range(h, p, px, py, sample, 1, rgb_out);
 }
 
 }  // extern "C"
