@@ -400,6 +400,37 @@ enum { RT_BSDF_FRONT_AUTO = 0, RT_BSDF_FRONT_GENERIC = 1, RT_BSDF_FRONT_LAMBERT 
 int rt_bsdf_eval(rt_scene* scene, int32_t material, int32_t front_end, uint64_t n, const float* surface, const float* wo, const float* wi, const float* u,
                  float* out);
 
+/* The light half of the shade stage, on n queries: what estimate_direct's light-sampling half (rc/integrator/mod.rs:222-262) runs at a vertex, per query and
+ * without a surface - the light pick of uniform_sample_one_light (mod.rs:186-220), Light::sample_li, Light::pdf_li, Light::le and
+ * VisibilityTester::unoccluded (light/mod.rs:52-55) - run by the device functions the shade kernels call. Host pointers; one lane per query.
+ * ref: n x RT_LIGHT_REF_FLOATS floats p.xyz, n.xyz, p_error.xyz - the fields of the reference Interaction that lights read. n may be zero (a point in free
+ *   space) and so may p_error; Sphere::sample_si and the shadow segment offset their origins with them (spawn_ray_to_interaction, interaction.rs:69-74).
+ * u: n x 3 floats u_pick, u_light.x, u_light.y.
+ * light >= 0: that entry of the scene's light list for every query; the reported pick pdf is 1 and u_pick is not read. light == RT_LIGHT_PICK: chosen per query
+ *   as uniform_sample_one_light does - light_strategy 0: the spatial distribution looked up at p (rc/lightdistrib.rs), 1: uniform; uniform whenever the scene
+ *   has one light (path.rs:89). The tables are built on first use and kept (those of rt_light_distribution and of rt_render). The spatial tables hold the voxels
+ *   that can contain a surface point (all voxels once rt_light_distribution has been called): a p whose voxel has no table gives light -1, pick pdf 0 and zeros
+ *   in the rest of its record; so does a pick of pdf 0 (a voxel no light reaches), with the picked index in float 0.
+ * wi: n x 3 floats, world space, used as given (not normalised), or NULL.
+ * out: n x RT_LIGHT_OUT_FLOATS floats per query -
+ *   0 light index (as a float) | 1 discrete pick pdf | 2-4 Li rgb | 5-7 wi of the sample | 8 pdf of the sample | 9-11 p1.p, the far end of the visibility
+ *   segment | 12-14 p1.n | 15 visibility: 1 unoccluded, 0 occluded, -1 not traced | 16 Light::pdf_li(ref, wi query) | 17-19 Light::le along wi query (only an
+ *   infinite light has one). Floats 16-19 are zero when wi is NULL.
+ * flags: RT_LIGHT_EVAL_VISIBILITY - for the records with pdf > 0 and a non-black Li the segment spawn_ray_to_interaction(ref, p1) is traced by the scene's any-hit
+ *   launch, the route of rt_trace_any (Scene::intersect_p: shadow-alpha masks, quadrics and instances apply; the shadow sets, keyed to surface points, do not).
+ *   RT_LIGHT_EVAL_GENERAL - the GENERAL instantiation of the light functions (quadric and masked emitters); without it the one the scene's shade kernels use.
+ * Refused with RT_ERR_INVALID and a message before any device work, `out` untouched: a NULL scene, ref, u or out; n == 0; n > RT_LIGHT_EVAL_MAX (device buffers
+ *   are sized by n: 176 bytes per query, one pass, no chunks); a light that is neither RT_LIGHT_PICK nor an index of the light list; a scene without lights; a
+ *   light_strategy other than 0 / 1 (checked whether or not the pick reads it); unknown flag bits. */
+#define RT_LIGHT_PICK (-1)
+#define RT_LIGHT_REF_FLOATS 9
+#define RT_LIGHT_OUT_FLOATS 20
+#define RT_LIGHT_EVAL_VISIBILITY 1u
+#define RT_LIGHT_EVAL_GENERAL 2u
+#define RT_LIGHT_EVAL_MAX (1u << 24)
+int rt_light_eval(rt_scene* scene, int32_t light, int32_t light_strategy, uint64_t n, const float* ref, const float* u, const float* wi /* may be NULL */,
+                  uint32_t flags, float* out);
+
 /* The radiance of every sample of a pixel window: the frame of rt_render (same batches, passes, kernels and queues) for the pixels of path->pixel_bounds
  * intersected with the film's sample bounds, handed back unfiltered. radiance: n_pixels x spp x 4 floats, pixels row-major in that window, sample index s =
  * the pixel-keyed sampler's index: L rgb exactly as PathIntegrator::li returned it - before the renderer's scrubbing and the max_sample_luminance clamp -

@@ -21,6 +21,7 @@
 #include "rtx_ref_launch.h"
 #include "rtx_rays_launch.h"
 #include "rtx_cameras_launch.h"
+#include "rtx_light_eval_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -159,6 +160,7 @@ static void fill_ewa_lut() {
   rtx_shade_set_ewa_lut(lut);  // the shade kernels' translation unit has a copy of its own
   rtx_shade_rays_set_ewa_lut(lut);  // ... and so has k_shade_rays'
   rtx_ref_set_ewa_lut(lut);    // ... and the reference-stream kernel's
+  rtx_light_eval_set_ewa_lut(lut);  // ... and rt_light_eval's
 }
 
 #include "rtx_bvh_build.h"
@@ -811,6 +813,46 @@ static int trace_batch(rt_scene* s, const float* rays, uint64_t n, bool any, flo
 }
 extern "C" int rt_trace_closest(rt_scene* s, const float* rays, uint64_t n, float* hits, uint64_t counters[2]) { return trace_batch(s, rays, n, false, hits, nullptr, counters); }
 extern "C" int rt_trace_any(rt_scene* s, const float* rays, uint64_t n, uint32_t* occluded, uint64_t counters[2]) { return trace_batch(s, rays, n, true, nullptr, occluded, counters); }
+
+// rt_light_eval: the light functions of the shade kernels per query (k_light_eval, rtx_light_eval.hip), the visibility segments through the any-hit launch of
+// rt_trace_any, their answers folded into the records (k_light_eval_fold). Every refusal comes before the first device call.
+extern "C" int rt_light_eval(rt_scene* scene, int32_t light, int32_t light_strategy, uint64_t n, const float* ref, const float* u, const float* wi, uint32_t flags, float* out) {
+  if (!scene || !ref || !u || !out) return fail(RT_ERR_INVALID, "rt_light_eval: a NULL scene, ref, u or out");
+  if (n == 0) return fail(RT_ERR_INVALID, "rt_light_eval: no queries (n == 0)");
+  if (n > (uint64_t)RT_LIGHT_EVAL_MAX) return fail(RT_ERR_INVALID, "rt_light_eval: more than RT_LIGHT_EVAL_MAX (2^24) queries in one call");
+  if (scene->n_lights <= 0) return fail(RT_ERR_INVALID, "rt_light_eval: the scene has no lights");
+  if (light != RT_LIGHT_PICK && (light < 0 || light >= scene->n_lights)) return fail(RT_ERR_INVALID, std::string("rt_light_eval: light ") + std::to_string(light) + " is neither RT_LIGHT_PICK nor an index of the " + std::to_string(scene->n_lights) + " lights");
+  if (light_strategy != 0 && light_strategy != 1) return fail(RT_ERR_INVALID, "rt_light_eval: unknown light_strategy (0 spatial, 1 uniform)");
+  if (flags & ~(RT_LIGHT_EVAL_VISIBILITY | RT_LIGHT_EVAL_GENERAL)) return fail(RT_ERR_INVALID, "rt_light_eval: unknown flag bits");
+  std::lock_guard<std::mutex> lock(scene->render_mutex);  // (the table build rewrites the scene record; a frame shares it)
+  HIP_TRY(hipSetDevice(scene->device));
+  if (light == RT_LIGHT_PICK) { const int rc = build_light_distribution(scene, light_strategy, nullptr); if (rc != RT_OK) return rc; }
+  const bool vis = (flags & RT_LIGHT_EVAL_VISIBILITY) != 0u;
+  DevBuf b[7];  // ref, u, wi, out, ray origins, ray directions, any-hit answers
+  const size_t nref = (size_t)n * RT_LIGHT_REF_FLOATS * 4, n3 = (size_t)n * 12, no = (size_t)n * RT_LIGHT_OUT_FLOATS * 4;
+  HIP_TRY(b[0].ensure(nref)); HIP_TRY(b[1].ensure(n3)); HIP_TRY(b[3].ensure(no));
+  HIP_TRY(hipMemcpy(b[0].p, ref, nref, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b[1].p, u, n3, hipMemcpyHostToDevice));
+  if (wi) { HIP_TRY(b[2].ensure(n3)); HIP_TRY(hipMemcpy(b[2].p, wi, n3, hipMemcpyHostToDevice)); }
+  if (vis) { HIP_TRY(b[4].ensure((size_t)n * 16)); HIP_TRY(b[5].ensure((size_t)n * 16)); HIP_TRY(b[6].ensure((size_t)n * 4)); }
+  LightEvalArgs a{};
+  a.light = light == RT_LIGHT_PICK ? -1 : light; a.ref = b[0].as<float>(); a.u = b[1].as<float>(); a.wi = wi ? b[2].as<float>() : nullptr; a.n = (unsigned)n; a.out = b[3].as<float>();
+  a.ray_o = vis ? b[4].as<float4>() : nullptr; a.ray_d = vis ? b[5].as<float4>() : nullptr;
+  rtx_launch_light_eval((flags & RT_LIGHT_EVAL_GENERAL) != 0u || scene->masked_emitters, nullptr, scene->d, a);
+  HIP_TRY(hipGetLastError());
+  if (vis) {
+    DevBuf st;
+    HIP_TRY(st.ensure(ST_COUNT * 8)); HIP_TRY(hipMemset(st.p, 0, ST_COUNT * 8));
+    const TraceIO io = trace_io_planar(b[4].as<float4>(), b[5].as<float4>(), nullptr, b[6].as<unsigned>());
+    launch_trace<true>(scene, false, io, nullptr, nullptr, 0, (unsigned)n, st.as<unsigned long long>(), ST_RAYS_SHADOW, ST_NODES_SHADOW, ST_TRIS_SHADOW, nullptr);
+    HIP_TRY(hipGetLastError());
+    rtx_launch_light_eval_fold(nullptr, b[6].as<unsigned>(), (unsigned)n, b[3].as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());  // (st is freed on return)
+  }
+  HIP_TRY(hipMemcpy(out, b[3].p, no, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
 
 extern "C" int rt_trace_closest_device(rt_scene* s, const void* d_rays, uint64_t n, void* d_hits, int reps, void* stream_, float* ms_per_launch) {
   if (!s || !d_rays || !d_hits || n == 0 || reps <= 0) return fail(RT_ERR_INVALID, "bad arguments");

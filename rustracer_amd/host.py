@@ -38,6 +38,12 @@ RT_FEATURE_SAMPLES_MAX = 1 << 25
 RT_BSDF_FRONT_AUTO, RT_BSDF_FRONT_GENERIC, RT_BSDF_FRONT_LAMBERT, RT_BSDF_FRONT_TWO_LOBE, RT_BSDF_FRONT_TWO_LOBE_WIDE = range(5)
 RT_BSDF_SURFACE_FLOATS = 40
 RT_BSDF_OUT_FLOATS = 13
+RT_LIGHT_PICK = -1            # rt_light_eval: the light is picked per query as uniform_sample_one_light does
+RT_LIGHT_REF_FLOATS = 9
+RT_LIGHT_OUT_FLOATS = 20
+RT_LIGHT_EVAL_VISIBILITY, RT_LIGHT_EVAL_GENERAL = 1, 2
+RT_LIGHT_EVAL_MAX = 1 << 24   # queries per call
+LIGHT_STRATEGIES = dict(spatial=0, uniform=1)
 RT_SAMPLES_MAX = 1 << 27
 RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
 RT_QUERY_LDS_SPEC = 7  # rt_scene_query: the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC: 0, 1)
@@ -516,6 +522,71 @@ class HostScene:
         if rc != 0:
             raise BackendError(f"rt_bsdf_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
         return dict(f=out[:, 0:3], pdf=out[:, 3], sf=out[:, 4:7], swi=out[:, 7:10], spdf=out[:, 10], stype=out[:, 11].astype(np.int32), n_lobes=out[:, 12].astype(np.int32), raw=out)
+
+    def light_eval(self, p, n, u, light=None, strategy="spatial", wi=None, visibility=False, p_error=None, general=False):
+        """The light half of the shade stage per query (rt_light_eval), run by the shade kernels' own light functions: p (q, 3) reference points, n (q, 3) their
+        normals or None (zero: points in free space), u (q, 3) = u_pick, u_light.x, u_light.y, p_error (q, 3) or None (zero). light: an index of the scene's light
+        list for every query, or None = picked per query as uniform_sample_one_light does, from the "spatial" or "uniform" distribution (a point whose voxel has no
+        table row: light -1, pick pdf 0, zeros elsewhere). wi (q, 3) world space or None: the direction Light::pdf_li and Light::le are asked about.
+        visibility: trace the segments of the records with pdf > 0 and a non-black Li by the any-hit launch. general: the GENERAL light functions.
+        Returns dict(light=(q,) int, pick_pdf=(q,), li=(q, 3), wi=(q, 3), pdf=(q,), p1=(q, 3), n1=(q, 3), visible=(q,) 1 / 0 / -1 not traced, pdf_li=(q,), le=(q, 3),
+        raw=(q, 20) float32). Uploads the scene first if need be."""
+        p = np.asarray(p, np.float32).reshape(-1, 3)
+        q = p.shape[0]
+        col = lambda v: np.zeros((q, 3), np.float32) if v is None else np.broadcast_to(np.asarray(v, np.float32).reshape(-1, 3), (q, 3))
+        ref = np.ascontiguousarray(np.concatenate([p, col(n), col(p_error)], axis=1), np.float32)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 3)
+        assert u.shape[0] == q
+        if wi is not None:
+            wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+            assert wi.shape[0] == q
+        dev = C.c_void_p()
+        _check(lib().rtxh_scene_device(self.h, C.byref(dev)), "scene_device")
+        out = np.zeros((q, RT_LIGHT_OUT_FLOATS), np.float32)
+        flags = (RT_LIGHT_EVAL_VISIBILITY if visibility else 0) | (RT_LIGHT_EVAL_GENERAL if general else 0)
+        rc = hip_lib().rt_light_eval(dev, C.c_int32(RT_LIGHT_PICK if light is None else int(light)), C.c_int32(LIGHT_STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)),
+                                     C.c_uint64(q), _p(ref), _p(u), _p(wi), C.c_uint32(flags), _p(out))
+        if rc != 0:
+            raise BackendError(f"rt_light_eval failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+        return dict(light=out[:, 0].astype(np.int32), pick_pdf=out[:, 1], li=out[:, 2:5], wi=out[:, 5:8], pdf=out[:, 8], p1=out[:, 9:12], n1=out[:, 12:15],
+                    visible=out[:, 15].astype(np.int32), pdf_li=out[:, 16], le=out[:, 17:20], raw=out)
+
+    def direct_irradiance(self, points, normals, blocks=64, grid=8, seed=0):
+        """Direct irradiance E rgb at arbitrary points with unit normals - no surface, no BSDF, no path (a light probe, a lightmap bake): for every light of the scene
+        the estimator Li max(0, n . wi) V / pdf of `light_eval` with visibility. A delta light (point, distant) takes one query per point; any other takes `blocks`
+        independent jittered `grid` x `grid` sets of u_light per point, and the standard error comes from the `blocks` block means (float64 on the host).
+        Returns (E (P, 3), its standard error (P, 3)) as float64."""
+        x = np.asarray(points, np.float64).reshape(-1, 3)
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        assert nrm.shape == x.shape and blocks >= 2 and grid >= 1
+        P, cells = x.shape[0], grid * grid
+        kinds = self.table("lights")["kind"]
+        rng = np.random.default_rng(seed)
+        e, var = np.zeros((P, 3)), np.zeros((P, 3))
+        gx, gy = np.meshgrid(np.arange(grid), np.arange(grid), indexing="ij")
+
+        def estimate(r, n_rep):
+            w = np.maximum((np.float64(r["wi"]) * n_rep).sum(-1), 0.0) * (r["visible"] == 1)
+            pdf = np.float64(r["pdf"])
+            return np.where((pdf > 0)[:, None], np.float64(r["li"]) * (w / np.where(pdf > 0, pdf, 1.0))[:, None], 0.0)
+        for k, kind in enumerate(kinds):
+            if int(kind) in (1, 2):      # RT_LIGHT_POINT, RT_LIGHT_DISTANT: sample_li does not read u
+                e += estimate(self.light_eval(x, nrm, np.zeros((P, 3), np.float32), light=k, visibility=True), nrm)
+                continue
+            per_call = max(1, (1 << 20) // (blocks * cells))     # points per call: about 2^20 queries
+            for p0 in range(0, P, per_call):
+                p1 = min(P, p0 + per_call)
+                m = p1 - p0
+                u = np.zeros((m, blocks, cells, 3), np.float32)
+                jit = rng.random((m, blocks, cells, 2))
+                u[..., 1] = np.minimum((gx.reshape(-1) + jit[..., 0]) / grid, np.float32(1.0) - np.float32(2.0 ** -24))
+                u[..., 2] = np.minimum((gy.reshape(-1) + jit[..., 1]) / grid, np.float32(1.0) - np.float32(2.0 ** -24))
+                rep = lambda a: np.repeat(a[p0:p1], blocks * cells, axis=0)
+                r = self.light_eval(rep(x), rep(nrm), u.reshape(-1, 3), light=k, visibility=True)
+                bm = estimate(r, rep(nrm)).reshape(m, blocks, cells, 3).mean(axis=2)      # block means
+                e[p0:p1] += bm.mean(axis=1)
+                var[p0:p1] += bm.var(axis=1, ddof=1) / blocks
+        return e, np.sqrt(var)
 
     def samples_window(self):
         """(x0, y0, x1, y1) of the pixels render_samples returns: the integrator's "pixelbounds" inside the film's sample bounds (PathIntegrator::create, path.rs:53-69)."""
