@@ -1251,6 +1251,29 @@ def sampler_tables(spp, dims, pixel0, n_pixels, plain=False):
     return sc, pm
 
 
+def frame_plan(owned_pixels, spp, dims, pass_log2=29, batch_log2=19, lead_on=None, fixed_cut=None, n_cu=256):
+    """rt_frame_plan (host only, no device): the cut of `owned_pixels` pixels x `spp` samples into batches and passes, as
+    dict(batch_pixels, lead_pixels, pass_samples, cap, shard_cap, n_slots, multi_batch, batches=[(first pixel, pixels, samples per pass)]).
+    lead_on None: the default (on at 1024 spp); fixed_cut: (batch_pixels, lead_pixels) of a frame with resident sampler tables. Raises BackendError
+    with the entry point's code in `.code`."""
+    fixed = fixed_cut or (0, 0)
+    args = [C.c_uint64(owned_pixels), C.c_int32(spp), C.c_int32(dims), C.c_int32(pass_log2), C.c_int32(batch_log2), C.c_int32((spp == 1024) if lead_on is None else bool(lead_on)),
+            C.c_uint64(fixed[0]), C.c_uint64(fixed[1]), C.c_int32(n_cu)]
+    plan, n = np.zeros(7, np.uint64), C.c_uint64(0)
+    rc = hip_lib().rt_frame_plan(*args, _p(plan, C.c_uint64), None, C.c_uint64(0), C.byref(n))
+    batches = np.zeros((n.value, 3), np.uint64)
+    if rc == 0:
+        rc = hip_lib().rt_frame_plan(*args, _p(plan, C.c_uint64), _p(batches, C.c_uint64), C.c_uint64(n.value), C.byref(n))
+    if rc < 0:
+        err = BackendError(f"rt_frame_plan failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+        err.code = rc
+        raise err
+    out = {k: int(v) for k, v in zip(("batch_pixels", "lead_pixels", "pass_samples", "cap", "shard_cap", "n_slots"), plan)}
+    out["multi_batch"] = bool(plan[6])
+    out["batches"] = [tuple(int(x) for x in b) for b in batches]
+    return out
+
+
 def offset_ray_origin(p, p_error, n, w):
     """offset_ray_origin (rc/geometry/mod.rs:203-220) on the device for (k, 3) float32 arrays: the parity hook of the ulp stepping every spawned ray goes through."""
     a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (p, p_error, n, w)]
