@@ -498,6 +498,40 @@ int rt_render_rays(rt_scene* scene, const float* rays, int32_t width, int32_t he
                    const rt_sampler_desc* sampler, const rt_path_desc* path, uint32_t flags, void* stream,
                    float* radiance, rt_stats* stats /* may be NULL */);
 
+/* The ambient-occlusion and normal integrators (integrator/ao.rs, integrator/normal.rs): one closest-hit ray per camera sample (scene.intersect: alpha masks), then
+ * n_samples occlusion rays from the hit - w = uniform_sample_sphere(get_2d()), negated where dot(w, n) < 0 against the GEOMETRIC normal hit.n (no shading normal, no bump
+ * map), spawn_ray(hit, w) - traced by the scene's any-hit kernels with scene.intersect_p's masks (alpha and shadowalpha). No BSDF, no light, no light distribution.
+ * The value of a sample is exact: ao = float32(n_clear) / float32(n_samples), one IEEE divide; 0 on a miss.
+ * Sampler: the counters start where get_camera_sample leaves them (cur_1d = 1, cur_2d = 2). Occlusion sample k is the k-th get_2d(): while 2 + k < dimensions the table
+ * value 2D#(2 + k) at the sample's index, after that two draws of the sample's keyed stream (pixel_index * spp + s + 2^32) in the reference's (second, first) order.
+ * rt_ao_desc: n_samples in [1, 1024] (AmbientOcclusion::new(n)); max_distance > 0 - the occlusion rays' t_max, +inf = the reference.
+ * (Declared as a struct and a typedef of it: 8 bytes, rt_sizeof("rt_ao_desc").)
+ *
+ * rt_render_rays_ao: AmbientOcclusion::li and Normal::li along the caller's rays. rays, width, height, sample0, n_samples and the sampler are rt_render_rays' - records of 8
+ * floats, or RT_RAY_DIFF_FLOATS with RT_FLAG_RAY_DIFFERENTIALS (the differentials are not read), the virtual film keying, RT_RAYS_MAX, calls over sample ranges that add
+ * up to a range give that range's call bit for bit.
+ *   out      [H][W][n_samples][RT_AO_FLOATS] floats: ao, |dot(ray.d, hit.n)| (Normal::li: ray.d as given, not normalised), t = length(p - o) of the hit (0 on a miss),
+ *            status - 0 hit, 1 miss, 2 not traced (t_max not > 0: nothing consumed, not counted in camera_rays).
+ *   ao_rays  NULL, or [H][W][n_samples][ao->n_samples][8] floats: each occlusion ray as cast - o.xyz, t_max, d.xyz, then 1.0 occluded / 0.0 clear; zeros for a miss or a
+ *            skipped ray. Refused when it would hold more than 2^27 records.
+ * rt_stats: camera_rays, rays_closest, rays_shadow = the occlusion rays cast, the nodes_ / tris_ counters under RT_FLAG_COUNT_TRAVERSAL, and under RT_FLAG_TIME_KERNELS
+ * ms_trace_closest, ms_trace_any and ms_shade = the kernels that generate the occlusion rays and finish the samples. RT_FLAG_FILM_ON_DEVICE: rays, out and ao_rays are
+ * device pointers. RT_ERR_INVALID with a message before any device work: what rt_render_rays refuses; a NULL ao, ao->n_samples < 1 or > 1024, a max_distance not > 0;
+ * RT_FLAG_REF_STREAM. Single device.
+ *
+ * rt_render_ao: the perspective camera's frame of this integrator, L = Spectrum::grey(ao), into rt_render's (X, Y, Z, weight) film - the same camera rays, film
+ * positions, pixel filter, max_sample_luminance, rt_shard bands and scrubbing; rt_camera_rays' records fed to rt_render_rays_ao give its samples. Every sample of the
+ * film's sample bounds is rendered (AmbientOcclusion::new leaves its pixel_bounds at the empty default, ao.rs:19-24; taken here as "no crop"). Refusals as above and as rt_render's. */
+#define RT_AO_FLOATS 4
+#define RT_AO_SAMPLES_MAX 1024
+struct rt_ao_desc { int32_t n_samples; float max_distance; };
+typedef struct rt_ao_desc rt_ao_desc;
+int rt_render_rays_ao(rt_scene* scene, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples,
+                      const rt_sampler_desc* sampler, const rt_ao_desc* ao, uint32_t flags, void* stream,
+                      float* out, float* ao_rays /* may be NULL */, rt_stats* stats /* may be NULL */);
+int rt_render_ao(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_ao_desc* ao,
+                 const rt_shard* shard /* may be NULL */, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats /* may be NULL */);
+
 /* The perspective camera's rays, as a camera frame generates them - what k_raygen and bounce 0's shade kernels compute - for samples [sample0, sample0 + n_samples) of every
  * pixel of the film's sample bounds (W x H pixels, pixel_index = row * W + column): for a caller who bends them (lens distortion, a stereo offset, a rolling shutter) and
  * feeds them to rt_render_rays or a ray frame, and as the exact source of the camera's differentials.

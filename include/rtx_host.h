@@ -160,6 +160,15 @@ int rtxh_render_rays(rtxh_scene*, const rtxh_render_params*, const float* rays, 
  * `flags`; p_film: H x W x n_samples x 2 or NULL; device pointers with RT_FLAG_FILM_ON_DEVICE. Of the parameters' own flags none is read. Sizes rt_camera_rays refuses are
  * refused before the scene is uploaded for it. */
 int rtxh_camera_rays(rtxh_scene*, const rtxh_render_params*, int32_t sample0, int32_t n_samples, uint32_t flags, void* hip_stream, float* rays, float* p_film /* may be NULL */);
+/* The ambient-occlusion and normal integrators along the caller's rays (rt_render_rays_ao in rtx_hip.h): rays as for rtxh_render_rays; out height x width x n_samples x
+ * RT_AO_FLOATS floats (ao, |d . n|, t, status); ao_rays NULL or height x width x n_samples x ao_samples x 8 floats; host pointers, or all three device pointers with
+ * RT_FLAG_FILM_ON_DEVICE. Of the parameters only the sampler (spp, sampler_dims) and the flags are read. What rt_render_rays_ao refuses is refused before the scene is
+ * uploaded for it. */
+int rtxh_render_rays_ao(rtxh_scene*, const rtxh_render_params*, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, int32_t ao_samples,
+                        float ao_max_distance, void* hip_stream, float* out, float* ao_rays /* may be NULL */, rt_stats* stats);
+/* The frame rtxh_render would render, with the ambient-occlusion integrator (rt_render_ao in rtx_hip.h): camera, film, sampler, rank / world_size and flags as for
+ * rtxh_render; the path integrator's parameters and the pixel bounds are not read. */
+int rtxh_render_ao(rtxh_scene*, const rtxh_render_params*, int32_t ao_samples, float ao_max_distance, void* hip_stream, float* film_xyzw, rt_stats* stats);
 /* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
  * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
  * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */

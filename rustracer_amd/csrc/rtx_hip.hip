@@ -22,6 +22,7 @@
 #include "rtx_rays_launch.h"
 #include "rtx_cameras_launch.h"
 #include "rtx_light_eval_launch.h"
+#include "rtx_ao_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -106,6 +107,7 @@ struct rt_scene {
   DevBuf samples_rad, samples_pf;  // rt_render_samples with host outputs: [window pixel][sample] radiance (float4) and film position (float2)
   DevBuf pfilm_in;                 // rt_frame_advance_rays*: the caller's host film positions in device memory ([pixel][sample of the step] 8 B)
   DevBuf rays_in, rays_skipped;    // rt_render_rays: the caller's host rays in device memory ([pixel][sample] 32 B), and the word k_rays_scan leaves (1: some ray is skipped)
+  DevBuf ao_rays;                  // rt_render_rays_ao with a host ao_rays: [pixel][sample][occlusion sample] 32 B
   DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
   DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
   DevBuf bsdf_self, bsdf_tris;     // rt_bsdf_eval: a copy of `d` whose tri_p names two primitive records that carry nothing but the orientation flag (0, 1) - what a bump map reads of si.prim
@@ -134,7 +136,7 @@ extern "C" int rt_sizeof(const char* name) {
   if (!name) return -1;
 #define RT_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);
   RT_SZ(rt_bvh_node) RT_SZ(rt_tri_meta) RT_SZ(rt_sphere) RT_SZ(rt_instance) RT_SZ(rt_texture) RT_SZ(rt_image) RT_SZ(rt_material) RT_SZ(rt_light) RT_SZ(rt_scene_desc)
-  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats)
+  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats) RT_SZ(rt_ao_desc)
 #undef RT_SZ
   return -1;
 }
@@ -1120,7 +1122,9 @@ enum FrameKind {
   FRAME_CAMERA_RAYS,      // rt_camera_rays, rt_camera_model_rays (model != NULL): the camera's rays handed out, no path work at all
   FRAME_STEP,             // rt_frame_advance*: a step of a progressive frame
   FRAME_RAY_STEP,         // rt_frame_advance_rays*: ... of a ray frame, on the caller's rays and film positions
-  FRAME_MODEL_STEP        // rt_frame_advance* of a model frame: ... on the rays the frame's camera model generates
+  FRAME_MODEL_STEP,       // rt_frame_advance* of a model frame: ... on the rays the frame's camera model generates
+  FRAME_AO,               // rt_render_ao: rt_render's film of the ambient-occlusion integrator - bounce 0's trace, then run_ao in place of the shade launches
+  FRAME_RAYS_AO           // rt_render_rays_ao: that integrator (and Normal::li) along the caller's rays, per sample
 };
 struct FrameJob {
   FrameKind kind = FRAME_FILM;
@@ -1136,12 +1140,15 @@ struct FrameJob {
   const CameraModel* model = nullptr;                       // FRAME_CAMERA_RAYS of a model, FRAME_MODEL_STEP
   rt_frame* frame = nullptr; unsigned step_end = 0;         // the steps
   const unsigned char* active_mask = nullptr; bool have_lock = false;
+  const rt_ao_desc* ao = nullptr; float* ao_rays = nullptr;  // FRAME_AO, FRAME_RAYS_AO (the occlusion rays handed out, or NULL)
 
   bool is_step() const { return kind == FRAME_STEP || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP; }
-  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP; }  // bounce 0 comes from ray records, not from the camera
+  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP || kind == FRAME_RAYS_AO; }  // bounce 0 comes from ray records, not from the camera
   bool traces_paths() const { return kind != FRAME_CAMERA_RAYS; }
   bool masked() const { return active_mask != nullptr; }
-  bool owns_film() const { return kind == FRAME_FILM || kind == FRAME_SAMPLES; }  // the scene's film sums, own sums and filter table are reserved (a step has the frame's)
+  bool is_ao() const { return kind == FRAME_AO || kind == FRAME_RAYS_AO; }  // no shade launches, no light distribution: run_ao
+  bool to_film() const { return kind == FRAME_FILM || kind == FRAME_AO; }  // the filtered film is the call's output
+  bool owns_film() const { return to_film() || kind == FRAME_SAMPLES; }  // the scene's film sums, own sums and filter table are reserved (a step has the frame's)
   bool stages_to_host() const { return !(flags & RT_FLAG_FILM_ON_DEVICE) && !is_step(); }  // the output goes through a device buffer of the scene's and is copied out
   bool frame_features() const { return is_step() && frame->features; }  // RT_FLAG_FRAME_FEATURES: the pass's features are summed into the frame's plane
   bool wants_features() const { return kind == FRAME_SAMPLE_FEATURES || frame_features(); }
@@ -1161,6 +1168,7 @@ struct FrameRun {
   bool all_in_bounds, has_infinite, count, shade_split, shade_live_args, ray_diff, resident, build_tables;
   ShadeRoute route; unsigned n_bins, pgrid; size_t counter_words, bin_stride; int lds_shade;
   FramePlan plan; std::vector<FrameBatch> batches;
+  double ms_ao = 0.0; float4* d_ao_rays = nullptr;  // the time of run_ao's own kernels (ms_shade of an AO call); where the occlusion rays go on the device
   // the workspace and the outputs, bound
   float4 *d_out, *d_samples_rad, *d_cam_rays; float2 *d_samples_pf, *d_cam_pf; FeatureOut fo;
   const float4* d_rays; const float2* d_pfilm;  // (a ray step's film positions; NULL: pixel centres)
@@ -1245,7 +1253,7 @@ static int frame_setup(FrameRun& r) {
   r.tm = KTimer{(job.flags & RT_FLAG_TIME_KERNELS) != 0, r.stream, &s->event_pool};
   // integrator.preprocess (renderer.rs:30)
   r.tm.begin(&r.stats.ms_lightdist);
-  const int rc = job.traces_paths() ? build_light_distribution(s, job.path->light_strategy, r.stream) : RT_OK;
+  const int rc = (job.traces_paths() && !job.is_ao()) ? build_light_distribution(s, job.path->light_strategy, r.stream) : RT_OK;
   if (rc != RT_OK) return rc;
   r.tm.end();
   return RT_OK;
@@ -1304,7 +1312,7 @@ static void frame_route(FrameRun& r) {
   // A Lambert-only scene with its records in LDS (S1, C1) whose closest hits come from k_trace: that launch leaves a hit bit per queue entry (TraceIO::hit_mask), bounce 0
   // of a pass that traces every sample is shaded by k_shade_split<1> - k_raygen then writes neither the throughput nor the state record - and every later bounce by
   // k_shade_split<2>. RTX_SHADE_SPLIT=0 (measurement knob, read per call): k_shade<1, .., 1> for every bounce, no masks, raygen as before.
-  r.shade_split = s->lambert_only && s->lds_records && closest_is_k_trace(s, r.count) && !env_is("RTX_SHADE_SPLIT", '0');
+  r.shade_split = s->lambert_only && s->lds_records && closest_is_k_trace(s, r.count) && !job.is_ao() && !env_is("RTX_SHADE_SPLIT", '0');
   // RTX_SHADE_KARGS=0 (measurement knob, read per call): such a scene's three shade kernels in the form that keeps the kernel arguments live through the vertex (the
   // control of round 10: k_shade_const_live, k_shade_split_live); the other front-ends have one form, chosen at compile time (RT_SHADE_KARGS)
   r.shade_live_args = env_is("RTX_SHADE_KARGS", '0');
@@ -1349,8 +1357,9 @@ static int reserve_workspace(FrameRun& r) {
     if (job.stages_to_host()) {
       if (job.kind == FRAME_SAMPLE_FEATURES) want.push_back({&s->samples_feat, (size_t)nws * RT_FEATURE_FLOATS * 4});
       else if (job.kind == FRAME_CAMERA_RAYS) { want.push_back({&s->rays_in, (size_t)nws * r.rec_floats * 4}); if (job.cam_out->p_film) want.push_back({&s->pfilm_in, (size_t)nws * 8}); }  // (staged for the copy to the host)
-      else if (job.kind == FRAME_FILM) want.push_back({&s->film_out, (size_t)r.cw * r.ch * 16});
+      else if (job.to_film()) want.push_back({&s->film_out, (size_t)r.cw * r.ch * 16});
       else { want.push_back({&s->samples_rad, (size_t)nws * 16}); if (job.samples_pf) want.push_back({&s->samples_pf, (size_t)nws * 8}); }
+      if (job.ao_rays) want.push_back({&s->ao_rays, (size_t)nws * (size_t)job.ao->n_samples * 32});
     }
     if (job.from_rays() && !r.src.on_device) {
       want.push_back({&s->rays_in, (size_t)nws * r.rec_floats * 4});
@@ -1389,7 +1398,11 @@ static int bind_outputs(FrameRun& r) {
   r.d_cam_pf = !(job.cam_out && job.cam_out->p_film) ? nullptr : (on_device ? (float2*)job.cam_out->p_film : s->pfilm_in.as<float2>());
   if (job.kind == FRAME_SAMPLE_FEATURES) { r.fo.samples = on_device ? (float4*)job.samples_feat : s->samples_feat.as<float4>(); r.fo.wx0 = r.wx0; r.fo.wy0 = r.wy0; r.fo.ww = r.wx1 - r.wx0; }
   else if (job.frame_features()) { r.fo.nd = s->feat.as<float4>(); r.fo.ah = r.fo.nd + r.plan.cap; }
-  if (job.kind == FRAME_FILM) {  // (no kernel of a per-sample kind reads the filter table or the film sums; a progressive frame keeps its own)
+  if (job.ao_rays) {  // zeros for the rays of a miss or a skipped ray
+    r.d_ao_rays = on_device ? (float4*)job.ao_rays : s->ao_rays.as<float4>();
+    HIP_TRY(hipMemsetAsync(r.d_ao_rays, 0, (size_t)r.n_window_samples * (size_t)job.ao->n_samples * 32, r.stream));
+  }
+  if (job.to_film()) {  // (no kernel of a per-sample kind reads the filter table or the film sums; a progressive frame keeps its own)
     HIP_TRY(hipMemcpyAsync(s->filter_table.p, job.film->filter_table, 1024, hipMemcpyHostToDevice, r.stream));
     HIP_TRY(hipMemsetAsync(s->film_acc.p, 0, (size_t)r.cw * r.ch * 16, r.stream));
   }
@@ -1549,6 +1562,52 @@ static int run_bounce(FrameRun& r, int buf, int bounce, int fresh_planes, int sk
   stats.launches_trace_closest += 2; stats.launches_trace_path += 1; stats.launches_trace_mis += 1; stats.launches_trace_shadow += 1; stats.launches_trace_mis_any += ps.mis_any ? 1 : 0;
   return RT_OK;
 }
+// The ambient-occlusion integrators' pass after ray generation (AmbientOcclusion::li, integrator/ao.rs:41-54): bounce 0's closest-hit trace as in run_bounce, then
+// n_samples rounds of k_ao_rays - one occlusion ray per hit path into the shadow-ray records and the shadow queue - and the scene's any-hit launch, whose epilogue adds
+// (1, 0, 0) into lacc[path] for a clear ray (one ray per path and round: the read-modify-write is race-free); a call that hands its rays out takes the launch's bytes
+// instead and adds in k_ao_fold. k_ao_finish divides. The queue's counter block is zeroed between rounds; nothing of the scene's workspace is read by a later call.
+static int run_ao(FrameRun& r, int buf) {
+  const FrameJob& job = r.job; rt_scene* const s = r.s; hipStream_t stream = r.stream; KTimer& tm = r.tm; rt_stats& stats = r.stats; PassState& ps = r.ps;
+  const unsigned pgrid = r.pgrid; const bool count = r.count;
+  unsigned* const cb = s->counters.as<unsigned>(); unsigned long long* const dstats = s->stats.as<unsigned long long>();
+  const size_t block_words = (size_t)RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;
+  ps.cnt_in = cb; ps.cnt_out = cb + block_words;
+  std::swap(ps.in, ps.out);  // what raygen appended is the pass's input
+  if (r.all_in_bounds) ps.cnt_in = nullptr;  // identity: entry i is slot i is path i
+  ps.fresh = 0; ps.skip_dead_tail = 0;
+  r.io_path.ray_o = ps.in.o; r.io_path.ray_d = ps.in.d; r.io_path.hit_mask = nullptr;
+  tm.begin(&stats.ms_trace_closest);
+  launch_trace<false>(s, count, r.io_path, ps.cnt_in, ps.cnt_in, ps.shard_cap, ps.cap, dstats, ST_RAYS_CLOSEST, ST_NODES_CLOSEST, ST_TRIS_CLOSEST, stream);
+  tm.end();
+  stats.launches_trace_closest += 1; stats.launches_trace_path += 1;
+  if (r.build_tables) for (int g = 1; g < 3; ++g) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][g], 0));  // 2-D tables 2 ...: the first rounds' samples
+  const bool rays_mode = job.kind == FRAME_RAYS_AO;
+  AoArgs a{};
+  a.n_ao = (unsigned)job.ao->n_samples; a.max_distance = job.ao->max_distance; a.flag = r.d_ao_rays ? 0u : 0x80000000u;
+  a.aux = rays_mode ? sraw(ps.mi.a) : nullptr; a.rays_out = r.d_ao_rays;
+  a.ray_s0 = rays_mode ? r.src.sample0 : 0u; a.ray_ns = rays_mode ? r.src.n_samples : 0u;
+  const bool general = s->has_spheres || s->has_instances;
+  for (unsigned k = 0; k < a.n_ao; ++k) {
+    a.round = k;
+    if (k) HIP_TRY(hipMemsetAsync(ps.cnt_out, 0, block_words * 4, stream));
+    tm.begin(&r.ms_ao);
+    rtx_launch_ao_rays(general, pgrid, stream, *r.dsc, r.fp, ps, a);
+    tm.end();
+    tm.begin(&stats.ms_trace_any);
+    launch_trace<true>(s, count, r.io_shadow, ps.q_shadow, ps.cnt_out + RT_QSHARDS * RT_CNT_STRIDE, ps.shard_cap, 0, dstats, ST_RAYS_SHADOW, ST_NODES_SHADOW, ST_TRIS_SHADOW, stream);
+    tm.end();
+    if (r.d_ao_rays) { tm.begin(&r.ms_ao); rtx_launch_ao_fold(pgrid, stream, r.fp, ps, a); tm.end(); }
+    stats.launches_shade += 1; stats.launches_trace_shadow += 1;
+  }
+  tm.begin(&r.ms_ao);
+  if (rays_mode) {  // k_sample_store's indexing: the call's samples per pixel as the row length, its first sample as sample 0
+    PassState po = ps; po.spp = r.src.n_samples; po.s0 = ps.s0 - r.src.sample0;
+    rtx_launch_ao_finish(pgrid, stream, r.fp, po, a, r.wx0, r.wy0, r.wx1 - r.wx0, r.d_samples_rad);
+  } else rtx_launch_ao_finish(pgrid, stream, r.fp, ps, a, 0, 0, 0, nullptr);
+  tm.end();
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
 // tiles of 2^(8 - ts) pixels x 2^ts samples of k_raygen_rays / k_raygen_rays_film: ts = log2(min(16, the pass's samples rounded up))
 static unsigned ray_tile_samples_log2(unsigned n_samples) { unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < n_samples) ++ts_log2; return ts_log2; }
 // One pass - samples [s0, s0 + n_samples) of the batch's pixels: ray generation by kind, the bounces, and the pass's film or store kernel by kind
@@ -1561,7 +1620,7 @@ static int run_pass(FrameRun& r, int buf, unsigned s0, unsigned n_samples, unsig
   if (r.route.use_bins) HIP_TRY(hipMemsetAsync(s->bin_words.p, 0, (size_t)(fp.max_depth + 1) * r.bin_stride * 4, stream));
   ps.cnt_in = nullptr; ps.cnt_out = s->counters.as<unsigned>();  // raygen appends to block 0's `out` queue
   ps.all_in_bounds = r.all_in_bounds ? 1 : 0;
-  const int fresh_planes = r.all_in_bounds ? ((s->lambert_only && s->lds_records) ? (r.shade_split ? 3 : RT_FRESH_RECORDS_LDS) : RT_FRESH_RECORDS) : 0;  // which records k_raygen leaves out (PassState::fresh; k_shade_split<1> reads neither)
+  const int fresh_planes = (r.all_in_bounds && !job.is_ao()) ? ((s->lambert_only && s->lds_records) ? (r.shade_split ? 3 : RT_FRESH_RECORDS_LDS) : RT_FRESH_RECORDS) : 0;  // which records k_raygen leaves out (PassState::fresh; k_shade_split<1> reads neither)
   ps.fresh = fresh_planes;
   // a frame that counts node visits keeps the reference's closest-hit walk for every MIS ray, unless it is asked to count what a production frame walks
   const bool as_rendered = !r.count || (job.flags & RT_FLAG_COUNT_AS_RENDERED);
@@ -1590,16 +1649,17 @@ static int run_pass(FrameRun& r, int buf, unsigned s0, unsigned n_samples, unsig
     rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, r.d_rays, r.d_pfilm, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), job.active_mask);
   }
   else if (job.masked()) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, job.active_mask);
-  else if (job.kind == FRAME_RAYS) rtx_launch_raygen_rays(pgrid, stream, fp, ps, r.d_rays, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), r.d_samples_rad);
+  else if (job.kind == FRAME_RAYS || job.kind == FRAME_RAYS_AO) rtx_launch_raygen_rays(pgrid, stream, fp, ps, r.d_rays, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), r.d_samples_rad);
   else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
   tm.end();
-  const int last_bounce = job.kind == FRAME_SAMPLE_FEATURES ? 0 : fp.max_depth;
+  if (job.is_ao()) { const int rc = run_ao(r, buf); if (rc != RT_OK) return rc; }
+  const int last_bounce = job.is_ao() ? -1 : (job.kind == FRAME_SAMPLE_FEATURES ? 0 : fp.max_depth);
   for (int bounce = 0; bounce <= last_bounce; ++bounce) {
     const int rc = run_bounce(r, buf, bounce, fresh_planes, skip_dead_tail);
     if (rc != RT_OK) return rc;
   }
   tm.begin(&stats.ms_film);
-  if (job.kind == FRAME_SAMPLE_FEATURES) { }  // (the feature kernels wrote the output)
+  if (job.kind == FRAME_SAMPLE_FEATURES || job.kind == FRAME_RAYS_AO) { }  // (the feature kernels / k_ao_finish wrote the output)
   else if (job.kind == FRAME_RAYS) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
     PassState po = ps; po.spp = r.src.n_samples; po.s0 = ps.s0 - r.src.sample0;
     hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, po, r.wx0, r.wy0, r.wx1 - r.wx0, r.d_samples_rad, (float2*)nullptr);
@@ -1679,7 +1739,7 @@ static int finish_frame(FrameRun& r) {
       HIP_TRY(hipStreamSynchronize(r.aux));
       fr->tables_built = true; fr->batch_pixels = r.plan.batch_pixels; fr->lead_pixels = r.plan.lead_pixels;
     }
-  } else if (job.kind == FRAME_FILM) {
+  } else if (job.to_film()) {
     r.tm.begin(&stats.ms_film);
     {
       unsigned long long n = (unsigned long long)r.cw * r.ch;
@@ -1697,10 +1757,11 @@ static int finish_frame(FrameRun& r) {
   } else {
     HIP_TRY(hipMemcpyAsync(job.samples_rad, r.d_samples_rad, nws * 16, hipMemcpyDeviceToHost, stream));
     if (job.samples_pf) HIP_TRY(hipMemcpyAsync(job.samples_pf, r.d_samples_pf, nws * 8, hipMemcpyDeviceToHost, stream));
+    if (job.ao_rays) HIP_TRY(hipMemcpyAsync(job.ao_rays, r.d_ao_rays, nws * (size_t)job.ao->n_samples * 32, hipMemcpyDeviceToHost, stream));
   }
   HIP_TRY(hipStreamSynchronize(stream));
   r.tm.collect();
-  stats.ms_shade = stats.ms_shade_lambert_const + stats.ms_shade_lambert + stats.ms_shade_two_lobe + stats.ms_shade_generic + stats.ms_shade_bin + stats.ms_shade_miss;
+  stats.ms_shade = stats.ms_shade_lambert_const + stats.ms_shade_lambert + stats.ms_shade_two_lobe + stats.ms_shade_generic + stats.ms_shade_bin + stats.ms_shade_miss + r.ms_ao;
   unsigned long long h[ST_COUNT];
   HIP_TRY(hipMemcpy(h, s->stats.p, sizeof(h), hipMemcpyDeviceToHost));
   { unsigned ovf = 0; HIP_TRY(hipMemcpy(&ovf, s->sampler_plan.dirty.as<unsigned>() + 1 + RT_DIRTY_CAP, 4, hipMemcpyDeviceToHost));
@@ -1834,6 +1895,48 @@ extern "C" int rt_render_rays(rt_scene* s, const float* rays, int32_t width, int
   const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, ray_rec_floats(flags)};
   FrameJob job = frame_job(FRAME_RAYS, s, &cam, &film, smp, &p, flags, stream_);
   job.ray_src = &src; job.samples_rad = radiance; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// What both ambient-occlusion entry points refuse of their descriptor
+static int ao_desc_check(const char* who, const rt_ao_desc* ao) {
+  const std::string w(who);
+  if (ao->n_samples < 1 || ao->n_samples > RT_AO_SAMPLES_MAX) return fail(RT_ERR_INVALID, w + ": ao->n_samples must be in [1, 1024]");
+  if (!(ao->max_distance > 0.0f)) return fail(RT_ERR_INVALID, w + ": ao->max_distance must be > 0 (+inf: the reference's rays)");
+  return RT_OK;
+}
+// a path descriptor of an AO call: depth 0 (one block of queue counters past raygen's), nothing else of it is read
+static rt_path_desc ao_path_desc(const rt_film_desc& film) { rt_path_desc p{}; memcpy(p.pixel_bounds, film.sample_bounds, 16); return p; }
+// AmbientOcclusion::li and Normal::li along the caller's rays, over the virtual film of the batch.
+extern "C" int rt_render_rays_ao(rt_scene* s, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, const rt_sampler_desc* smp,
+                                 const rt_ao_desc* ao, uint32_t flags, void* stream_, float* out, float* ao_rays, rt_stats* stats_out) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  if (!s || !rays || !smp || !ao || !out) return fail(RT_ERR_INVALID, "rt_render_rays_ao: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_rays_ao: the reference-stream frame has no per-sample output");
+  if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rt_render_rays_ao: width, height and n_samples must be positive");
+  int rc = sample_range_check("rt_render_rays_ao", smp, sample0, n_samples, (unsigned long long)width, (unsigned long long)height, "must lie inside");
+  if (rc != RT_OK) return rc;
+  if ((rc = ao_desc_check("rt_render_rays_ao", ao)) != RT_OK) return rc;
+  if (ao_rays && (unsigned long long)width * (unsigned long long)height * (unsigned long long)n_samples * (unsigned long long)ao->n_samples > (unsigned long long)RT_RAYS_MAX)
+    return fail(RT_ERR_INVALID, "rt_render_rays_ao: ao_rays would hold more than 2^27 records - cut the call by sample range");
+  const rt_camera cam{};
+  const rt_film_desc film = virtual_film(width, height);
+  const rt_path_desc p = ao_path_desc(film);
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, ray_rec_floats(flags)};
+  FrameJob job = frame_job(FRAME_RAYS_AO, s, &cam, &film, smp, &p, flags, stream_);
+  job.ray_src = &src; job.samples_rad = out; job.ao = ao; job.ao_rays = ao_rays; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// The perspective camera's frame of the ambient-occlusion integrator: rt_render's film with L = Spectrum::grey(ao).
+extern "C" int rt_render_ao(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_ao_desc* ao, const rt_shard* shard,
+                            uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out) {
+  if (!s || !cam || !film || !smp || !ao || !film_xyzw) return fail(RT_ERR_INVALID, "rt_render_ao: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_ao: the reference-stream frame renders the path integrator only");
+  int rc = sampler_check("rt_render_ao", smp);
+  if (rc != RT_OK) return rc;
+  if ((rc = ao_desc_check("rt_render_ao", ao)) != RT_OK) return rc;
+  const rt_path_desc p = ao_path_desc(*film);
+  FrameJob job = frame_job(FRAME_AO, s, cam, film, smp, &p, flags, stream_);
+  job.shard = shard; job.film_xyzw = film_xyzw; job.ao = ao; job.stats_out = stats_out;
   return render_frame(job);
 }
 // The perspective camera's rays (and film positions) of samples [sample0, sample0 + n_samples) of every pixel of the film's sample bounds, as a camera frame generates

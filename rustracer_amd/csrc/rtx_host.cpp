@@ -1346,6 +1346,46 @@ int rtxh_camera_rays(rtxh_scene* s, const rtxh_render_params* p, int32_t sample0
   if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
   return rt_camera_rays(s->dev, &cf.cam, &cf.film, &smp, sample0, n_samples, flags, stream, rays, p_film);
 }
+// what rt_render_rays_ao / rt_render_ao refuse of the integrator's parameters, before the scene is uploaded
+static int ao_params_check(const char* who, int32_t ao_samples, float ao_max_distance) {
+  if (ao_samples < 1 || ao_samples > RT_AO_SAMPLES_MAX) return fail(RT_ERR_INVALID, std::string(who) + ": ao_samples must be in [1, 1024]");
+  if (!(ao_max_distance > 0.0f)) return fail(RT_ERR_INVALID, std::string(who) + ": ao_max_distance must be > 0 (+inf: the reference's rays)");
+  return RT_OK;
+}
+// AmbientOcclusion::li / Normal::li along the caller's rays (rt_render_rays_ao)
+int rtxh_render_rays_ao(rtxh_scene* s, const rtxh_render_params* p, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, int32_t ao_samples,
+                        float ao_max_distance, void* stream, float* out, float* ao_rays, rt_stats* stats) {
+  if (!s || !p || !rays || !out) return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: null argument");
+  g_err.clear();
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_ao_desc ao{ao_samples, ao_max_distance};
+  {  // what rt_render_rays_ao refuses, before the scene is uploaded for it
+    long long spp = 1; while (spp < (long long)std::max(p->spp, 1)) spp <<= 1;
+    if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: width, height and n_samples must be positive");
+    if (sample0 < 0 || (long long)sample0 + (long long)n_samples > spp) return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: [sample0, sample0 + n_samples) must lie inside [0, spp)");
+    if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX / (unsigned long long)n_samples)
+      return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+    int rc = ao_params_check("rtxh_render_rays_ao", ao_samples, ao_max_distance); if (rc != RT_OK) return rc;
+    if (ao_rays && (unsigned long long)width * (unsigned long long)height * (unsigned long long)n_samples > (unsigned long long)RT_RAYS_MAX / (unsigned long long)ao_samples)
+      return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: ao_rays would hold more than 2^27 records - cut the call by sample range");
+    if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_rays_ao: the reference-stream frame has no per-sample output");
+  }
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_rays_ao(s->dev, rays, width, height, sample0, n_samples, &smp, &ao, p->flags, stream, out, ao_rays, stats);
+}
+// The frame of rtxh_render with the ambient-occlusion integrator (rt_render_ao): camera and film exactly as rtxh_render sets them up.
+int rtxh_render_ao(rtxh_scene* s, const rtxh_render_params* p, int32_t ao_samples, float ao_max_distance, void* stream, float* film_xyzw, rt_stats* stats) {
+  if (!s || !p || !film_xyzw) return fail(RT_ERR_INVALID, "rtxh_render_ao: null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  if ((rc = ao_params_check("rtxh_render_ao", ao_samples, ao_max_distance)) != RT_OK) return rc;
+  if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_ao: the reference-stream frame renders the path integrator only");
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_ao_desc ao{ao_samples, ao_max_distance};
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  return rt_render_ao(s->dev, &cf.cam, &cf.film, &smp, &ao, &shard, p->flags, stream, film_xyzw, stats);
+}
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
 int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {

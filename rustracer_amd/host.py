@@ -46,6 +46,8 @@ RT_LIGHT_EVAL_MAX = 1 << 24   # queries per call
 LIGHT_STRATEGIES = dict(spatial=0, uniform=1)
 RT_SAMPLES_MAX = 1 << 27
 RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
+RT_AO_FLOATS = 4            # rt_render_rays_ao: floats per ray of its output (ao, |d . n|, t, status)
+RT_AO_SAMPLES_MAX = 1024    # ... and the most occlusion rays per hit
 RT_QUERY_LDS_SPEC = 7  # rt_scene_query: the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC: 0, 1)
 RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
 RT_QUERY_BSDF_LAUNCHED = 5# rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
@@ -103,6 +105,11 @@ class RenderParams(C.Structure):
         ("pixel_bounds", C.c_int32 * 4), ("rank", C.c_int32), ("world_size", C.c_int32), ("flags", C.c_uint32),
         ("screen_window", C.c_float * 4), ("has_pixel_bounds", C.c_int32),
     ]
+
+
+class AoDesc(C.Structure):
+    """rt_ao_desc (rtx_hip.h): the ambient-occlusion integrators' parameters."""
+    _fields_ = [("n_samples", C.c_int32), ("max_distance", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -794,6 +801,76 @@ class HostScene:
         rad = np.zeros((h, w, ns, 4), np.float32)
         _check(L.rtxh_render_rays(self.h, C.byref(p), rays.ctypes.data_as(C.c_void_p), w, h, int(sample0), ns, C.c_void_p(stream), rad.ctypes.data_as(C.c_void_p), C.byref(stats)), "render_rays")
         return rad, stats.as_dict()
+
+    def render_rays_ao(self, rays, n_samples, max_distance=float("inf"), sample0=0, spp=None, with_rays=False, device_out=None, stream=0, count_traversal=False,
+                       time_kernels=False, device_rays_out=None):
+        """The ambient-occlusion and normal integrators along caller-supplied rays (rt_render_rays_ao: AmbientOcclusion::li, Normal::li). `rays` as in `render_rays` -
+        (H, W, ns, 8) float32, or 20 floats whose differentials are not read; ray (x, y, sl) is sample sample0 + sl of pixel y * W + x of a virtual W x H film. Each hit
+        casts `n_samples` occlusion rays of t_max `max_distance` (inf: the reference) over the hemisphere of its geometric normal. Returns (out (H, W, ns, 4), stats):
+        ao = n_clear / n_samples, |dot(d, n)| with d as given, t of the hit, status 0 hit / 1 miss / 2 not traced (t_max not > 0). `with_rays`: returns
+        (out, ao_rays (H, W, ns, n_samples, 8), stats) - every occlusion ray as cast, o.xyz, t_max, d.xyz, 1.0 occluded / 0.0 clear; zeros for a miss or a skipped ray.
+        `rays` may be a contiguous torch CUDA float32 tensor: `device_out` must then be one of shape (H, W, ns, 4), and with `with_rays` `device_rays_out` one of shape
+        (H, W, ns, n_samples, 8) (RT_FLAG_FILM_ON_DEVICE: all stay in HBM); they are returned."""
+        p = self._render_params()
+        if spp is not None:
+            p.spp = int(spp)
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        on_device = hasattr(rays, "data_ptr")
+        if not on_device:
+            rays = np.ascontiguousarray(rays, np.float32)
+        if len(rays.shape) != 4 or rays.shape[3] not in (8, RT_RAY_DIFF_FLOATS):
+            raise BackendError(f"render_rays_ao: rays must have shape (H, W, ns, 8 | {RT_RAY_DIFF_FLOATS}), not {tuple(rays.shape)}")
+        if rays.shape[3] == RT_RAY_DIFF_FLOATS:
+            p.flags |= RT_FLAG_RAY_DIFFERENTIALS
+        h, w, ns = (int(v) for v in rays.shape[:3])
+        n_ao = int(n_samples)
+        if h * w * ns > RT_RAYS_MAX or (with_rays and n_ao > 0 and h * w * ns * n_ao > RT_RAYS_MAX):
+            raise BackendError(f"render_rays_ao: {h} x {w} x {ns} rays (x {n_ao} occlusion rays handed out) are more than RT_RAYS_MAX - cut the job by sample range")
+        L = lib()
+        L.rtxh_render_rays_ao.restype = C.c_int
+        L.rtxh_render_rays_ao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        stats = Stats()
+        if on_device:
+            ok = device_out is not None and tuple(device_out.shape) == (h, w, ns, RT_AO_FLOATS) and rays.is_contiguous() and device_out.is_contiguous() and rays.element_size() == 4 and device_out.element_size() == 4
+            if with_rays:
+                ok = ok and device_rays_out is not None and tuple(device_rays_out.shape) == (h, w, ns, n_ao, 8) and device_rays_out.is_contiguous() and device_rays_out.element_size() == 4
+            if not ok:
+                raise BackendError("render_rays_ao: device rays need a contiguous float32 device_out of shape (H, W, ns, 4), and with_rays a device_rays_out of shape (H, W, ns, n_samples, 8)")
+            p.flags |= RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_rays_ao(self.h, C.byref(p), C.c_void_p(rays.data_ptr()), w, h, int(sample0), ns, n_ao, float(max_distance), C.c_void_p(stream),
+                                         C.c_void_p(device_out.data_ptr()), C.c_void_p(device_rays_out.data_ptr()) if with_rays else None, C.byref(stats)), "render_rays_ao")
+            return (device_out, device_rays_out, stats.as_dict()) if with_rays else (device_out, stats.as_dict())
+        if device_out is not None or device_rays_out is not None:
+            raise BackendError("render_rays_ao: device outputs need device rays (RT_FLAG_FILM_ON_DEVICE names every pointer)")
+        out = np.zeros((h, w, ns, RT_AO_FLOATS), np.float32)
+        ao_rays = np.zeros((h, w, ns, max(n_ao, 0), 8), np.float32) if with_rays else None
+        _check(L.rtxh_render_rays_ao(self.h, C.byref(p), rays.ctypes.data_as(C.c_void_p), w, h, int(sample0), ns, n_ao, float(max_distance), C.c_void_p(stream),
+                                     out.ctypes.data_as(C.c_void_p), ao_rays.ctypes.data_as(C.c_void_p) if with_rays else None, C.byref(stats)), "render_rays_ao")
+        return (out, ao_rays, stats.as_dict()) if with_rays else (out, stats.as_dict())
+
+    def render_ao(self, n_samples, max_distance=float("inf"), rank=0, world_size=1, count_traversal=False, time_kernels=False, device_out=None, stream=0):
+        """The frame of `render` with the ambient-occlusion integrator (rt_render_ao): the same camera rays, film positions, pixel filter and shard bands, every sample's
+        L = grey(n_clear / n_samples) over `n_samples` occlusion rays of t_max `max_distance`. Returns (film_xyzw (H, W, 4) over the cropped bounds, stats dict).
+        `device_out`: optional torch CUDA tensor (H, W, 4) float32 that receives the film in HBM."""
+        flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        st = self.setup(rank=rank, world_size=world_size)
+        cr = st["cropped"]
+        w, h = int(cr[2] - cr[0]), int(cr[3] - cr[1])
+        p = st["params"]
+        L = lib()
+        L.rtxh_render_ao.restype = C.c_int
+        L.rtxh_render_ao.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if device_out is not None:
+            assert tuple(device_out.shape) == (h, w, 4) and device_out.is_contiguous()
+            p.flags = flags | RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_ao(self.h, C.byref(p), int(n_samples), float(max_distance), C.c_void_p(stream), C.c_void_p(device_out.data_ptr()), C.byref(stats)), "render_ao")
+            return device_out, stats.as_dict()
+        p.flags = flags
+        film = np.zeros((h, w, 4), np.float32)
+        _check(L.rtxh_render_ao(self.h, C.byref(p), int(n_samples), float(max_distance), C.c_void_p(stream), _p(film), C.byref(stats)), "render_ao")
+        return film, stats.as_dict()
 
     def texture_words(self, tex):
         """The word block of texture `tex` as the host holds it (float32), or an empty array for a texture that names none."""

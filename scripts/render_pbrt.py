@@ -3,6 +3,7 @@
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
                                   [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials] [--device-camera]]
+                                  [--ao N [--ao-distance D]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -33,7 +34,11 @@ file's perspective camera. Opt-in: without it the rays have none and textures ar
 --device-camera (with --camera-model): the camera's rays are generated on the device (rt_frame_begin_model) from the file's ZeroTwoSequence tables - film positions
 pixel + the sampler's 2D#0 instead of the script's seeded jitter (--seed is unused), the orthographic camera's "lensradius" / "focaldistance" as a thin lens from 2D#1 -
 and rendered through a model frame: nothing per sample crosses the host bus. Filtered as under --ray-frame (the file's PixelFilter, clamp and film scale; the PNG is
-RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights); honours --preview-every, --adaptive with its options, --features and --ray-differentials."""
+RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights); honours --preview-every, --adaptive with its options, --features and --ray-differentials.
+--ao N [--ao-distance D]: the file's camera, film, filter and sampler with the reference's ambient-occlusion integrator (rt_render_ao; integrator/ao.rs) in place of the
+file's Integrator: every camera sample's value is the clear fraction of N occlusion rays over the hemisphere of the first hit's geometric normal, rays of length D
+(default: infinite, the reference). A choice of this command line: the loader's Integrator handling is unchanged (it refuses "ambientocclusion" as it refuses
+"whitted"). One call, one device: --preview-every, --adaptive, --features, --samples, --devices and --camera-model do not combine with it."""
 import argparse
 import os
 import sys
@@ -178,7 +183,13 @@ def main():
     ap.add_argument("--sample-map", metavar="OUT.npy", default=None, help="with --adaptive: write the per-pixel sample counts")
     ap.add_argument("--features", metavar="OUT.npy", default=None, help="write the per-pixel first-hit feature planes (albedo, normal, depth, coverage) beside the image")
     ap.add_argument("--devices", default=None, metavar="0,1,...", help="with --preview-every / --adaptive: render the frame on these GPUs of this process")
+    ap.add_argument("--ao", type=int, default=0, metavar="N", help="render with the ambient-occlusion integrator: N occlusion rays per camera sample")
+    ap.add_argument("--ao-distance", type=float, default=float("inf"), metavar="D", help="with --ao: the length of the occlusion rays (default: infinite)")
     a = ap.parse_args()
+    if a.ao and (a.samples or a.preview_every > 0 or a.adaptive is not None or a.features or a.devices or a.camera_model):
+        raise SystemExit("--ao renders the file's camera in one call: it does not combine with --samples, --preview-every, --adaptive, --features, --devices or --camera-model")
+    if a.ao_distance != float("inf") and not a.ao:
+        raise SystemExit("--ao-distance goes with --ao")
     host.build()
     s = host.PbrtScene(a.scene)
     if a.spp:
@@ -301,6 +312,10 @@ def main():
                 write(film)
                 print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
             save_features(frame)
+    elif a.ao:
+        film, stats = s.render_ao(a.ao, a.ao_distance)
+        write(film)
+        print(f"{out}: ambient occlusion, {a.ao} occlusion rays per sample, {stats['rays_shadow']} cast from {stats['camera_rays']} camera samples")
     else:
         film, stats = s.render()
         write(film)
