@@ -208,6 +208,21 @@ class OracleScene:
         lib().orc_tex_probe(self.h, int(tex), f(uv), f(p), f(duv), f(dpdx), f(dpdy), _p(out))
         return out
 
+    def bsdf_probe_surface(self, material, surface, wo, wi, u):
+        """orc_bsdf_probe_surface query by query: surface (n, 40) records in rt_bsdf_eval's order or None (the canonical hit), wo, wi (n, 3) world space, u (n, 2).
+        Returns (n, 13) float32 in rt_bsdf_eval's output order: f rgb, pdf, sampled f rgb, wi xyz, pdf, type flags, lobe count."""
+        wo, wi, u = (np.ascontiguousarray(a, np.float32) for a in (wo, wi, u))
+        n = wo.shape[0]
+        if surface is not None:
+            surface = np.ascontiguousarray(surface, np.float32).reshape(n, 40)
+        out = np.zeros((n, 13), np.float32)
+        f, smp, pdf = np.zeros(3, np.float32), np.zeros(8, np.float32), C.c_float()
+        probe = lib().orc_bsdf_probe_surface
+        for i in range(n):
+            nl = probe(self.h, int(material), None if surface is None else _p(surface[i]), _p(wo[i]), _p(wi[i]), _p(u[i]), _p(f), C.byref(pdf), _p(smp))
+            out[i, 0:3], out[i, 3], out[i, 4:12], out[i, 12] = f, pdf.value, smp, nl
+        return out
+
     def mip_levels(self, mip):
         L = lib()
         w, h = C.c_int32(), C.c_int32()

@@ -507,6 +507,28 @@ int orc_bsdf_probe(void* h, int material, const float* wo3, const float* wi3, co
   sample_out8[6] = sf.pdf; sample_out8[7] = (float)sf.type;
   return b.n;
 }
+// ... and at a hand-made hit: surface40 = one record in the order rtx_hip.h documents for rt_bsdf_eval (p, n, shading n, dpdu, dpdv, shading dpdu, shading dpdv,
+// dndu, dndv - read as zero, as Scene::bump does -, u v, dudx dvdx dudy dvdy, dpdx, dpdy, flip); NULL = the canonical hit of orc_bsdf_probe. flip != 0 is the
+// orientation bit Scene::bump negates the bumped normal by (interaction.rs:228); the record belongs to no primitive of the scene.
+int orc_bsdf_probe_surface(void* h, int material, const float* surface40, const float* wo3, const float* wi3, const float* u2, float* f3_out, float* pdf_out,
+                           float* sample_out8) {
+  if (!surface40) return orc_bsdf_probe(h, material, wo3, wi3, u2, f3_out, pdf_out, sample_out8);
+  Scene* s = (Scene*)h;
+  const float* r = surface40;
+  auto v = [r](int i) { return v3(r[i], r[i + 1], r[i + 2]); };
+  SurfaceInteraction si; si.hit = Interaction{v(0), v3(0, 0, 0), v3(wo3[0], wo3[1], wo3[2]), v(3)}; si.uv = P2{r[27], r[28]};
+  si.dpdu = v(9); si.dpdv = v(12); si.shading.n = v(6); si.shading.dpdu = v(15); si.shading.dpdv = v(18);
+  si.dudx = r[29]; si.dvdx = r[30]; si.dudy = r[31]; si.dvdy = r[32]; si.dpdx = v(33); si.dpdy = v(36);
+  si.flip = r[39] != 0.0f ? 1 : 0;
+  Bsdf b; s->build_bsdf(material, si, &b);
+  V3 wo = v3(wo3[0], wo3[1], wo3[2]), wi = v3(wi3[0], wi3[1], wi3[2]);
+  RGB f = b.f(wo, wi, BSDF_ALL); f3_out[0] = f.r; f3_out[1] = f.g; f3_out[2] = f.b;
+  *pdf_out = b.pdf(wo, wi, BSDF_ALL);
+  SampleF sf = b.sample_f(wo, P2{u2[0], u2[1]}, BSDF_ALL);
+  sample_out8[0] = sf.f.r; sample_out8[1] = sf.f.g; sample_out8[2] = sf.f.b; sample_out8[3] = sf.wi.x; sample_out8[4] = sf.wi.y; sample_out8[5] = sf.wi.z;
+  sample_out8[6] = sf.pdf; sample_out8[7] = (float)sf.type;
+  return b.n;
+}
 float orc_next_float_up(float v) { return next_float_up(v); }
 float orc_next_float_down(float v) { return next_float_down(v); }
 float orc_gamma(int n) { return gamma_n((uint32_t)n); }

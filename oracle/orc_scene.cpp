@@ -672,7 +672,8 @@ void Scene::bump(int tex, SurfaceInteraction& si) const {
   V3 dpdv = si.shading.dpdv + (v_displace - displace) / dv * si.shading.n + displace * dndv;
   // set_shading_geometry(dpdu, dpdv, dndu, dndv, false), interaction.rs:218-242
   si.shading.n = normalize(cross(dpdu, dpdv));
-  if (si.prim >= 0) {  // reverse_orientation ^ transform_swaps_handedness of si.shape: the object's shape for a hit inside an instance
+  if (si.flip >= 0) { if (si.flip) si.shading.n = si.shading.n * -1.0f; }
+  else if (si.prim >= 0) {  // reverse_orientation ^ transform_swaps_handedness of si.shape: the object's shape for a hit inside an instance
     int tri; const Scene& o = owner_of(si, &tri);
     if (o.tri_flags[tri] & 1) si.shading.n = si.shading.n * -1.0f;
   }

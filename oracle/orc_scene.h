@@ -47,6 +47,7 @@ struct SurfaceInteraction {  // rc/interaction.rs:78-104
   float dudx = 0, dvdx = 0, dudy = 0, dvdy = 0;
   int prim = -1;  // index into ordered primitive list
   int sub = -1;   // hit inside an object instance (prim names the TransformedPrimitive): index into the OBJECT's ordered primitive list
+  int flip = -1;  // >= 0: a hand-made record (orc_bsdf_probe_surface) states reverse_orientation ^ transform_swaps_handedness itself; prim names no shape
   struct { V3 n, dpdu, dpdv; } shading;
 };
 
