@@ -362,6 +362,11 @@ int rt_sampler_tables(int32_t spp, int32_t dimensions, uint64_t pixel0, uint64_t
 /* Same result from the single-kernel statement of the algorithm (one lane walks a pixel's whole RNG stream in
  * order). Not used by rt_render; it is the on-device cross-check of the segmented sampler over large pixel ranges. */
 int rt_sampler_tables_plain(int32_t spp, int32_t dimensions, uint64_t pixel0, uint64_t n_pixels, uint32_t* scrambles, uint16_t* perms);
+/* The shuffle replay alone, on caller-supplied swap partners: chain c does swap(a[i], a[partners[c * spp + i]]) for i = 0 .. spp - 1 on the identity and
+ * perms[c * spp + i] receives a[i]. kernel 0: the chain kernel (one lane per chain, spp a power of two up to 16384), 1: the parallel replay (one wave per chain,
+ * spp a power of two in [64, 1024]). Every partner must lie in [i, spp). Host pointers; the random streams of rt_sampler_tables never produce the rows that are
+ * hardest on the parallel replay, this entry point takes any. */
+int rt_sampler_replay(int32_t spp, int32_t n_chains, const uint16_t* partners, uint16_t* perms, int32_t kernel);
 
 /* offset_ray_origin (rc/geometry/mod.rs:203-220) with its next_float_up / next_float_down steps (rc/lib.rs:227-262) on n points: p, p_error, normal and
  * direction w as n x 3 floats each, out n x 3. The device function every spawned ray goes through (Interaction::spawn_ray / spawn_ray_to, rc/interaction.rs:

@@ -971,14 +971,19 @@ static int launch_sampler_tables(SamplerPlan& pl, const FrameParams& fp, unsigne
   // but a frame builds all tables except its first batch's UNDER path kernels, where the chain kernel (one latency-bound wave per CU) takes almost nothing from them
   // and the parallel one competes for issue slots and LDS. Measured in round 4, frame times: at 256 / 512 spp the parallel replay loses (S2 167.3 -> 169.5 ms, S3 323.5 ->
   // 324.6); at 1024 spp, with a short leading batch (lead_pixels in rt_render), it wins for EVERY batch (S1 679.5 -> 667.5 ms, S4 5280 -> 5242).
+  // Round 11 (MEASUREMENTS R11; rocprofv3 totals over one S1 frame with K0 on the render stream, nine replays and three draws launches): the replay without its
+  // counting sort 23.6 -> 14.4 ms against the chain kernel's 34.8; the chain-major draws, written out as whole lines through an LDS stage, 16.1 -> 7.35 ms against 6.9 -
+  // 7.0 for the pixel-minor layout - the layout costs the draws kernel next to nothing now.
   // DEFAULT therefore: parallel replay at spp == 1024, chain kernel otherwise. RTX_K0_PARALLEL=1 forces the parallel replay (64 <= spp <= 1024), =0 the chain kernel.
   static const bool par_on = env_is("RTX_K0_PARALLEL", '1');
   static const bool par_never = env_is("RTX_K0_PARALLEL", '0');
-  // RTX_K0_FORCE_RESORT=1 (test knob, read per call): the parallel replay is handed descending ranks, so every wave takes the branch that re-sorts its groups
+  // RTX_K0_FORCE_RESORT=1 (test knob, read per call): every wave of the parallel replay takes the branch that replays its chain sequentially
   const unsigned force_resort = (env_is("RTX_K0_FORCE_RESORT", '1')) ? 1u : 0u;
   const bool par = (par_on || (!par_never && spp == 1024u)) && spp >= 64u && spp <= 1024u;
-  hipLaunchKernelGGL(k_sampler_draws, dim3((n_pixels + 255u) / 256u, pl.n_segs), dim3(256), 0, stream, fp, n_pixels, spp, dims, pl.seg_len, explicit_pixel0, use_explicit,
-                     pl.segs.as<SamplerSeg>(), pl.magic.as<unsigned>(), scrambles, partners, pl.dirty.as<unsigned>(), par ? 1 : 0);
+  if (par) hipLaunchKernelGGL(k_sampler_draws<true>, dim3((n_pixels + 255u) / 256u, pl.n_segs), dim3(256), RT_DRAWS_STAGE_BYTES, stream, fp, n_pixels, spp, dims, pl.seg_len, explicit_pixel0, use_explicit,
+                              pl.segs.as<SamplerSeg>(), pl.magic.as<unsigned>(), scrambles, partners, pl.dirty.as<unsigned>());
+  else hipLaunchKernelGGL(k_sampler_draws<false>, dim3((n_pixels + 255u) / 256u, pl.n_segs), dim3(256), 0, stream, fp, n_pixels, spp, dims, pl.seg_len, explicit_pixel0, use_explicit,
+                          pl.segs.as<SamplerSeg>(), pl.magic.as<unsigned>(), scrambles, partners, pl.dirty.as<unsigned>());
   hipLaunchKernelGGL(k_sampler_redo, dim3(RT_DIRTY_CAP / 64u), dim3(64), 0, stream, fp, n_pixels, spp, dims, explicit_pixel0, use_explicit, pl.dirty.as<unsigned>(), pl.magic.as<unsigned>(), scrambles, partners, par ? 1 : 0);
   unsigned* const resorted = pl.dirty.as<unsigned>() + 1 + RT_DIRTY_CAP + 1;  // waves whose groups did not come out sorted (diagnostic; the result is exact either way)
   for (int g = 0; g < groups.n_groups; ++g) {
@@ -1044,6 +1049,46 @@ static int sampler_tables_host(int32_t spp_, int32_t dims, uint64_t pixel0, uint
     for (uint64_t t = 0; t < 2ull * dims; ++t)
       for (uint64_t i = 0; i < spp; ++i) perms[(p * 2 * dims + t) * spp + i] = hp[(t * spp + i) * n_pixels + p];
   }
+  return RT_OK;
+}
+// The replay kernels alone on caller-supplied partner rows (one table of n_chains "pixels"): what launch_sampler_tables launches after the draws.
+extern "C" int rt_sampler_replay(int32_t spp_, int32_t n_chains, const uint16_t* partners, uint16_t* perms, int32_t kernel) {
+  if (!rt_device_available()) return fail(RT_ERR_NO_DEVICE, "no HIP device visible; this backend has no CPU fallback");
+  if (spp_ <= 0 || spp_ > 16384 || (spp_ & (spp_ - 1)) != 0 || n_chains <= 0 || !partners || !perms) return fail(RT_ERR_INVALID, "rt_sampler_replay: spp must be a power of two up to 16384, n_chains positive");
+  if (kernel != 0 && kernel != 1) return fail(RT_ERR_INVALID, "rt_sampler_replay: kernel must be 0 (chain kernel) or 1 (parallel replay)");
+  const unsigned spp = (unsigned)spp_, n = (unsigned)n_chains;
+  if (kernel == 1 && (spp < 64u || spp > 1024u)) return fail(RT_ERR_INVALID, "rt_sampler_replay: the parallel replay takes 64 <= spp <= 1024");
+  for (size_t c = 0; c < n; ++c)
+    for (unsigned i = 0; i < spp; ++i) { const unsigned p = partners[c * spp + i]; if (p < i || p >= spp) return fail(RT_ERR_INVALID, "rt_sampler_replay: partner outside [i, spp)"); }
+  // device layouts: partners [pixel][i] for the parallel replay, [i][pixel] for the chain kernel; perms [sample][pixel] from both
+  std::vector<uint16_t> hin((size_t)n * spp), hout((size_t)n * spp);
+  for (size_t c = 0; c < n; ++c)
+    for (unsigned i = 0; i < spp; ++i) hin[kernel == 1 ? c * spp + i : (size_t)i * n + c] = partners[c * spp + i];
+  DevBuf din, dout, cnt; int rc;
+  if ((rc = upload(din, hin.data(), hin.size() * 2)) != RT_OK) return rc;
+  HIP_TRY(dout.ensure(hout.size() * 2)); HIP_TRY(cnt.ensure(4)); HIP_TRY(hipMemset(cnt.p, 0, 4));
+  if (kernel == 1) {
+    const dim3 grid((n + RT_SHUF_PIX - 1) / RT_SHUF_PIX, 1);
+    const unsigned force_resort = env_is("RTX_K0_FORCE_RESORT", '1') ? 1u : 0u;
+    unsigned short* const i16 = din.as<unsigned short>(); unsigned short* const o16 = dout.as<unsigned short>(); unsigned* const res = cnt.as<unsigned>();
+    switch (spp) {
+      case 64: hipLaunchKernelGGL(k_sampler_shuffle_par<1>, grid, dim3(256), 0, nullptr, n, i16, o16, res, 0ull, force_resort); break;
+      case 128: hipLaunchKernelGGL(k_sampler_shuffle_par<2>, grid, dim3(256), 0, nullptr, n, i16, o16, res, 0ull, force_resort); break;
+      case 256: hipLaunchKernelGGL(k_sampler_shuffle_par<4>, grid, dim3(256), 0, nullptr, n, i16, o16, res, 0ull, force_resort); break;
+      case 512: hipLaunchKernelGGL(k_sampler_shuffle_par<8>, grid, dim3(256), 0, nullptr, n, i16, o16, res, 0ull, force_resort); break;
+      default: hipLaunchKernelGGL(k_sampler_shuffle_par<16>, grid, dim3(256), 0, nullptr, n, i16, o16, res, 0ull, force_resort); break;
+    }
+  } else {
+    if ((rc = sampler_set_lds_limits(spp)) != RT_OK) return rc;
+    const unsigned lpb = shuffle_lanes_per_block(spp);
+    hipLaunchKernelGGL(k_sampler_shuffle, dim3((n + lpb - 1) / lpb, 1), dim3(lpb), (size_t)lpb * spp * 2, nullptr, n, spp, din.as<unsigned short>(), dout.as<unsigned short>(), 0ull);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  if (kernel == 1 && getenv("RTX_K0_REPORT")) { unsigned r = 0; HIP_TRY(hipMemcpy(&r, cnt.p, 4, hipMemcpyDeviceToHost)); fprintf(stderr, "k_sampler_shuffle_par: %u wave(s) re-sorted their groups\n", r); }
+  HIP_TRY(hipMemcpy(hout.data(), dout.p, hout.size() * 2, hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < n; ++c)
+    for (unsigned i = 0; i < spp; ++i) perms[c * spp + i] = hout[(size_t)i * n + c];
   return RT_OK;
 }
 

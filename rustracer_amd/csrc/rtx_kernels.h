@@ -322,12 +322,26 @@ RT_DEV void mark_dirty(unsigned* dirty, unsigned pix) {  // dirty[0] = count, di
   if (k < RT_DIRTY_CAP) dirty[1 + k] = pix;
 }
 
+// the lanes of ONE wave hand each other values through LDS: writes before, reads after
+RT_DEV void wave_sync_lds() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+#define RT_DRAWS_STAGE_BYTES 36864u  // k_sampler_draws, chain_major: 4 waves x 64 lanes x (128 + 16) B
+static_assert(RT_DRAWS_STAGE_BYTES == 4u * 64u * 9u * 16u && RT_DRAWS_STAGE_BYTES <= 40960u, "the draws kernel's stage: at most 40 KB per 256 lanes");
+
+// (CHAIN_MAJOR is a template parameter, so that a launch with pixel-minor rows runs a kernel that holds nothing of the staged form: 14 registers against 57. Seen with the
+// layout as a launch argument, one kernel for both: instances-10k, which never writes chain-major rows, 886.6 -> 853.9 Msamples/s against the parent's library, although
+// the kernel's own time had not moved. That the allocation beside the path kernels is the cause is a supposition; what was measured of this form: MEASUREMENTS R11)
+template <bool CHAIN_MAJOR>
 static __global__ void __launch_bounds__(256) k_sampler_draws(FrameParams fp, unsigned n_pixels, unsigned spp, unsigned dims, unsigned seg_len,
                                                        unsigned long long explicit_pixel0, int use_explicit, const SamplerSeg* __restrict__ segs,
                                                        const unsigned* __restrict__ magic, unsigned* __restrict__ scrambles, unsigned short* __restrict__ partners,
-                                                       unsigned* dirty, int chain_major) {
+                                                       unsigned* dirty) {
+  constexpr bool chain_major = CHAIN_MAJOR;
+  // chain_major: a wave's swap partners on their way out, 64 draws (128 B) per lane; rows 16 B longer, so that the eight rows one store instruction reads start in
+  // different banks. RT_DRAWS_STAGE_BYTES of dynamic LDS per workgroup, asked for by chain_major launches only: held statically it costs the pixel-minor launches
+  // half their waves per SIMD (6.9 -> 7.9 ms per S1 frame, MEASUREMENTS R11).
+  extern __shared__ uint4 s_stage[];
   const unsigned pix = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= n_pixels) return;
+  const bool active = pix < n_pixels;  // (a predicate, not a return: every lane of a wave takes part in the staged write-out below)
   const SamplerSeg sg = segs[blockIdx.y];
   const unsigned long long pixel_index = pixel_index_of(fp, pix, explicit_pixel0, use_explicit);
   Pcg32 rng;
@@ -335,45 +349,68 @@ static __global__ void __launch_bounds__(256) k_sampler_draws(FrameParams fp, un
   const unsigned long long s0 = (rng.inc + 0x853c49e6748fea9bULL) * 0x5851f42d4c957f2dULL + rng.inc;  // state after set_sequence
   rng.state = sg.mul * s0 + sg.sum * rng.inc;
   const unsigned t = sg.table;
-  if (sg.n_scr == 1u) scrambles[(size_t)t * n_pixels + pix] = rng.next_u32();
-  else if (sg.n_scr == 2u) {
-    unsigned a = rng.next_u32(), b = rng.next_u32();
-    scrambles[(size_t)(dims + 2u * (t - dims)) * n_pixels + pix] = a;
-    scrambles[(size_t)(dims + 2u * (t - dims) + 1u) * n_pixels + pix] = b;
+  if (active) {
+    if (sg.n_scr == 1u) scrambles[(size_t)t * n_pixels + pix] = rng.next_u32();
+    else if (sg.n_scr == 2u) {
+      unsigned a = rng.next_u32(), b = rng.next_u32();
+      scrambles[(size_t)(dims + 2u * (t - dims)) * n_pixels + pix] = a;
+      scrambles[(size_t)(dims + 2u * (t - dims) + 1u) * n_pixels + pix] = b;
+    }
   }
   bool retry = false;
+  // one bounded(spp - i) draw of the shuffle: the swap partner of step i (b = spp - i is wave-uniform)
+  auto partner = [&](unsigned i) {
+    const unsigned b = spp - i;
+    const unsigned r = rng.next_u32();
+    retry |= r < ((~b + 1u) & b);
+    unsigned rem = 0u;
+    if (b > 1u) {
+      const unsigned q = __umulhi(r, magic[b]);  // floor(r / b) or one less
+      rem = r - q * b;
+      rem = rem >= b ? rem - b : rem;
+    }
+    return i + rem;
+  };
   if (sg.half == 0u) {
     // bounded(1): threshold 1, retried iff the draw is 0; the output function maps exactly xorshifted == 0 to 0
-    for (unsigned i = 0; i < seg_len; ++i) {
-      unsigned long long old = rng.state;
-      rng.state = old * 0x5851f42d4c957f2dULL + rng.inc;
-      retry |= (unsigned)(((old >> 18u) ^ old) >> 27u) == 0u;
+    if (active)
+      for (unsigned i = 0; i < seg_len; ++i) {
+        unsigned long long old = rng.state;
+        rng.state = old * 0x5851f42d4c957f2dULL + rng.inc;
+        retry |= (unsigned)(((old >> 18u) ^ old) >> 27u) == 0u;
+      }
+  } else if (!chain_major) {
+    // partners[table][i][pixel]: a wave's stores coalesce
+    if (active) {
+      unsigned short* dst = partners + ((size_t)t * spp + sg.i0) * n_pixels + pix;
+      for (unsigned k = 0; k < seg_len; ++k) dst[(size_t)k * n_pixels] = (unsigned short)partner(sg.i0 + k);
     }
   } else {
-    // partners[table][i][pixel]: a wave's stores coalesce. chain_major (the parallel replay, k_sampler_shuffle_par): partners[table][pixel][i] - a lane
-    // writes its segment as 16-byte stores of eight partners each; a wave's lanes work on 64 lines of their own for the whole segment, which L2 merges
-    unsigned short* dst = chain_major ? partners + ((size_t)t * n_pixels + pix) * spp + sg.i0 : partners + ((size_t)t * spp + sg.i0) * n_pixels + pix;
-    unsigned w8[4] = {0u, 0u, 0u, 0u};
-    for (unsigned k = 0; k < seg_len; ++k) {
-      const unsigned i = sg.i0 + k, b = spp - i;  // wave-uniform
-      const unsigned r = rng.next_u32();
-      retry |= r < ((~b + 1u) & b);
-      unsigned rem = 0u;
-      if (b > 1u) {
-        const unsigned q = __umulhi(r, magic[b]);  // floor(r / b) or one less
-        rem = r - q * b;
-        rem = rem >= b ? rem - b : rem;
+    // chain_major (the parallel replay, k_sampler_shuffle_par): partners[table][pixel][i], a row per chain. A lane is a pixel, so what a wave draws in step belongs
+    // to 64 rows: written from the lanes as they come, every 128-byte line was put together in L2 from eight 16-byte stores 64 draws apart, of eight different
+    // instructions each - 16.1 ms per S1 frame against 7.0 ms for the pixel-minor layout (MEASUREMENTS R11). Instead a lane parks 64 draws, one line of its row,
+    // in the wave's LDS stage, and the wave writes the 64 lines out whole: eight lanes per line, eight rows per store instruction.
+    // (seg_len is a multiple of 64 wherever chain_major is used: spp >= 64.) The stage is the wave's own: no workgroup barrier, every lane reaches the wave's.
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint4(*const st)[9] = (uint4(*)[9])s_stage + 64u * wv;
+    const unsigned pix0 = blockIdx.x * blockDim.x + 64u * wv;  // the wave's first row
+    for (unsigned k0 = 0; k0 < seg_len; k0 += 64u) {
+      for (unsigned k8 = 0; k8 < 64u; k8 += 8u) {
+        unsigned v[8];
+#pragma unroll
+        for (unsigned j = 0; j < 8u; ++j) v[j] = partner(sg.i0 + k0 + k8 + j);
+        st[lane][k8 >> 3] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
       }
-      if (!chain_major) dst[(size_t)k * n_pixels] = (unsigned short)(i + rem);
-      else {  // (seg_len is a multiple of 8 wherever chain_major is used: spp >= 64)
-        const unsigned v = i + rem, h = (k & 7u) >> 1;
-        const unsigned add = (k & 1u) ? (v << 16) : v;
-        w8[0] = h == 0u ? (w8[0] | add) : w8[0]; w8[1] = h == 1u ? (w8[1] | add) : w8[1]; w8[2] = h == 2u ? (w8[2] | add) : w8[2]; w8[3] = h == 3u ? (w8[3] | add) : w8[3];
-        if ((k & 7u) == 7u) { *(uint4*)(dst + (k - 7u)) = make_uint4(w8[0], w8[1], w8[2], w8[3]); w8[0] = w8[1] = w8[2] = w8[3] = 0u; }
+      wave_sync_lds();
+#pragma unroll
+      for (unsigned q = 0; q < 8u; ++q) {
+        const unsigned row = 8u * q + (lane >> 3), piece = lane & 7u;
+        if (pix0 + row < n_pixels) *(uint4*)(partners + ((size_t)t * n_pixels + pix0 + row) * spp + sg.i0 + k0 + 8u * piece) = st[row][piece];
       }
+      wave_sync_lds();  // the stage is free again
     }
   }
-  if (retry) mark_dirty(dirty, pix);
+  if (retry && active) mark_dirty(dirty, pix);
 }
 
 // K0b. Step i of the shuffle: swap(a[i], a[other_i]). The LDS round trip of one step would serialise the chain,
@@ -469,34 +506,37 @@ static __global__ void __launch_bounds__(64) k_sampler_shuffle(unsigned n_pixels
   }
 }
 
-// K0b', the exact PARALLEL replay of the Fisher-Yates chain (round 4). k_sampler_shuffle walks a chain of spp dependent swaps with one
-// lane and a 2 * spp-byte permutation in LDS: 64 chains fill 128 KB, so a CU holds one such wave and runs it at the latency of one LDS round trip per eight
-// swaps - 57 ms per S1 frame alone, and while it overlaps path kernels its 128 KB workgroups evict theirs. Here ONE WAVE replays ONE chain, 64 steps at a time:
+// K0b', the exact PARALLEL replay of the Fisher-Yates chain (round 4; round 11: without its counting sort). k_sampler_shuffle walks a chain of
+// spp dependent swaps with one lane and a 2 * spp-byte permutation in LDS: 64 chains fill 128 KB, so a CU holds one such wave and runs it at the latency of one LDS
+// round trip per eight swaps - 57 ms per S1 frame alone, and while it overlaps path kernels its 128 KB workgroups evict theirs. Here ONE WAVE replays ONE chain:
 //   step i does swap(a[i], a[o_i]), o_i >= i. Position p only changes when a step w < p with o_w = p (a "writer" of p) puts there what a[w] held before step w,
 //   R(w); at step p itself a[p] becomes final. So, with p's writers in order w_1 < w_2 < ... < w_k (the self-swap w = p, if any, last):
 //       perm[w_1] = p,   perm[w_{m+1}] = R(w_m),   R(j) = j if j has no writer below j, else R(L(j)) with L(j) = the last writer of j below j.
-//   Every step is a writer of exactly one position, so this names every perm[i] once. The writers are grouped by target with a counting sort in LDS (packed
-//   16-bit counters, one atomic per step; the groups come out in ascending order, which is checked), L is read off the groups and R is found by pointer
-//   jumping (a chain of L links is ~2 long: 3 - 5 rounds). Everything is straight-line code over the lane's E steps: a dozen dependent LDS round trips per
-//   chain instead of 1024. (A first version with per-target loops - insertion sort, pointer chase - took 131 ms per S1 frame: loops of dependent LDS reads.) The result goes through an LDS tile so that 16 chains leave as 32-byte runs of perms[table][sample][pixel].
-// MEASURED (S1's batches, 524 288 pixels x 8 tables, alone on the GPU): 15.4 ms against the chain kernel's 23.2 - and 4.4 ms more in k_sampler_draws for the
-// chain-major partner layout it needs; under path kernels, where a frame builds all tables but the first batch's, it costs the frame more than the chain
-// kernel does at 64 ... 512 spp (rtx_hip.hip, launch_sampler_tables). DEFAULT: used for every batch of a 1024-spp frame (together with a short leading batch: S1 679.5 ->
-// 667.5 ms, end of round 4), not used at other sample counts; RTX_K0_PARALLEL=1 forces it on for 64 <= spp <= 1024, =0 forces the chain kernel everywhere.
+//   Every step is a writer of exactly one position, so this names every perm[i] once. Both facts a step needs - pred(i), the writer before it at its target, and
+//   L(j) - come from ONE returning atomic per step, max(last[o_i], i + 1) on a zeroed word array, because the steps are issued in ascending order (iterations m in
+//   program order, the lanes of one instruction in lane order): the value returned is pred(i) + 1 (0: first writer), and afterwards last[p] - 1 is p's last writer -
+//   L(p) itself when it lies below p, the self-swap when it equals p (then L(p) = pred(p), which the same lane holds), nobody when last[p] is 0. R is found by pointer
+//   jumping (a chain of L links is ~2 long: 3 - 5 rounds; 11 at worst). Rounds 4 - 10 read the same facts off a counting sort of the writers by target: 14 E of the
+//   kernel's 26 E LDS operations per lane and chain, eight of its thirteen dependent stages, 57 KB of LDS. (A first version with per-target loops - insertion sort,
+//   pointer chase - took 131 ms per S1 frame: loops of dependent LDS reads.) The result goes through an LDS tile so that 16 chains leave as 32-byte runs of
+//   perms[table][sample][pixel].
+// The lane order inside one atomic instruction is not architected, so it is CHECKED: if the lanes that name one word were served in any other order, some lane is
+// served after a larger one and reads back a value above its own i + 1. Such a wave (never seen) replays its chain sequentially with one lane, and is counted.
+// LDS: the tile, 16 x (N + 2) x 2 B, and one word array of N per wave - `last` first and, once every lane holds its last[p] in registers, the 16-bit R array:
+// 49 216 B at E = 16, three workgroups per CU.
+// DEFAULT: used for every batch of a 1024-spp frame (together with a short leading batch: S1 679.5 -> 667.5 ms, end of round 4), not used at other sample counts;
+// RTX_K0_PARALLEL=1 forces it on for 64 <= spp <= 1024, =0 forces the chain kernel everywhere (rtx_hip.hip, launch_sampler_tables; MEASUREMENTS R4, R11).
 // Exact: the same permutation as the sequential replay for every partner sequence (tests: the sampler tables stay bit-equal to the oracle's, retry pixels
-// included). E = spp / 64 steps per lane: instantiated for spp 64 ... 1024; other sample counts keep k_sampler_shuffle.
+// included; rt_sampler_replay runs it on rows no random stream produces). E = spp / 64 steps per lane: instantiated for spp 64 ... 1024; other sample counts keep
+// k_sampler_shuffle.
 #define RT_SHUF_PIX 16
-RT_DEV void wave_sync_lds() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 template <int E>
 __global__ void __launch_bounds__(256) k_sampler_shuffle_par(unsigned n_pixels, const unsigned short* __restrict__ partners, unsigned short* __restrict__ perms, unsigned* __restrict__ n_resorted, unsigned long long tables, unsigned force_resort) {
-  constexpr unsigned N = 64u * E, NONE = 0xffffu;
+  constexpr unsigned N = 64u * E;
   __shared__ unsigned short tile[RT_SHUF_PIX][N + 2];  // (+2: rows an odd number of words apart, the transposed read-out is conflict-free)
-  __shared__ unsigned short s_o[4][N];                 // per wave: R (the pointer-jumping array)
-  __shared__ unsigned s_cnt[4][N / 2 + 64 + 1];        // per wave: packed 16-bit counters per target (target p at index CI(p) = p + 2 * (p / E)), then exclusive bases
-  __shared__ unsigned short s_wl[4][N];                // per wave: writers grouped by target
+  __shared__ unsigned s_last[4][N];                    // per wave: last[p] = 1 + the last writer of p; then, as 16-bit entries, R (the pointer-jumping array)
   const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, t = (unsigned)(tables >> (4u * blockIdx.y)) & 15u, pix0 = blockIdx.x * RT_SHUF_PIX;
-  unsigned short* const o = s_o[wv]; unsigned* const cnt = s_cnt[wv]; unsigned short* const wl = s_wl[wv];
-  const unsigned short* const cnt16 = (const unsigned short*)cnt;
+  unsigned* const last = s_last[wv]; unsigned short* const o = (unsigned short*)s_last[wv];
   // the partners of the workgroup's 16 chains, all requested at once (one memory latency per workgroup, not one per chain): each chain's row of the tile holds
   // its partners until the chain is replayed and its permutation afterwards
   {  // 16-byte loads, all of a thread's in flight together: thread tid takes 16-byte piece tid, tid + 256, ... of the workgroup's 16 x 2 N bytes
@@ -519,86 +559,46 @@ __global__ void __launch_bounds__(256) k_sampler_shuffle_par(unsigned n_pixels, 
   for (unsigned c = wv; c < RT_SHUF_PIX; c += 4u) {
     const unsigned pix = pix0 + c;
     if (pix >= n_pixels) break;  // (wave-uniform)
-    for (unsigned k = lane; k < N / 2u + 64u; k += 64u) cnt[k] = 0u;
-    wave_sync_lds();
-    // Step i = 64 m + lane. Its rank among the writers of its target is the value its atomic returns: iterations run in order of m, and the lanes of ONE
-    // atomic instruction that name the same counter are served in lane order on this hardware - so the rank is the writer's position in ascending order and
-    // the groups come out sorted. That order is not architected: it is CHECKED below (every writer against its predecessor) and a wave that finds it broken
-    // sorts its groups the slow way.
     // Every phase below is written in STAGES over the lane's E steps - all loads of a stage first, then what depends on them - so that a stage costs one LDS
-    // round trip, not E of them (written step by step the compiler kept the steps' dependent reads in order: 19 500 cycles per chain, all of it LDS latency
-    // at the two waves per SIMD the workgroup's 57 KB allow).
-    unsigned pk[E], rk[E];
+    // round trip, not E of them (written step by step the compiler kept the steps' dependent reads in order: 19 500 cycles per chain, all of it LDS latency).
+    unsigned pk[E], pr[E];
 #pragma unroll
-    for (int m = 0; m < E; ++m) pk[m] = tile[c][64u * (unsigned)m + lane];
-#pragma unroll
-    for (int m = 0; m < E; ++m) {
-      const unsigned ci = pk[m] + 2u * (pk[m] / (unsigned)E);
-      rk[m] = atomicAdd(&cnt[ci >> 1], (pk[m] & 1u) ? 0x10000u : 1u);
-    }
-#pragma unroll
-    for (int m = 0; m < E; ++m) rk[m] = (pk[m] & 1u) ? (rk[m] >> 16) : (rk[m] & 0xffffu);
+    for (int m = 0; m < E; ++m) { last[64u * (unsigned)m + lane] = 0u; pk[m] = tile[c][64u * (unsigned)m + lane]; }
     wave_sync_lds();
-    if (force_resort) {  // test knob (RTX_K0_FORCE_RESORT=1): hand every group its ranks in DESCENDING order, what an atomic unit that served lanes the other way round would
-                         // return - the check below then fails for every group of two or more writers and the wave takes the re-sort branch (that branch is
-                         // "never seen" on this hardware and would otherwise never be exercised)
+    // Step i = 64 m + lane: what its atomic returns is 1 + the writer before it at its target (see above; iterations run in order of m, and the lanes of ONE atomic
+    // instruction that name the same word are served in lane order on this hardware - checked right below)
 #pragma unroll
-      for (int m = 0; m < E; ++m) rk[m] = (unsigned)cnt16[pk[m] + 2u * (pk[m] / (unsigned)E)] - 1u - rk[m];
-    }
-    {  // exclusive scan of the counts over the targets: lane l scans its targets [l * E, (l + 1) * E) (CI skews the counters by one word per E targets, so
-       // that the 64 lanes' chunks start in different banks), one wave scan joins the lanes' sums
-      unsigned x[E], local[E]; unsigned sum = 0u;
+    for (int m = 0; m < E; ++m) pr[m] = atomicMax(&last[pk[m]], 64u * (unsigned)m + lane + 1u);
+    bool unsorted = force_resort != 0u;  // test knob (RTX_K0_FORCE_RESORT=1): every wave takes the sequential branch ("never seen" on this hardware, so
+                                         // otherwise never exercised)
 #pragma unroll
-      for (int m = 0; m < E; ++m) x[m] = cnt16[lane * (E + 2u) + (unsigned)m];
-#pragma unroll
-      for (int m = 0; m < E; ++m) { local[m] = sum; sum += x[m]; }
-      unsigned incl = sum;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const unsigned v = __shfl_up(incl, off); if ((int)lane >= off) incl += v; }
-      const unsigned excl = incl - sum;
-      wave_sync_lds();  // every lane has read its counts
-#pragma unroll
-      for (int m = 0; m < E; ++m) ((unsigned short*)cnt)[lane * (E + 2u) + (unsigned)m] = (unsigned short)(excl + local[m]);
-    }
+    for (int m = 0; m < E; ++m) unsorted |= pr[m] > 64u * (unsigned)m + lane;
     wave_sync_lds();
-    unsigned bs[E];
-#pragma unroll
-    for (int m = 0; m < E; ++m) bs[m] = cnt16[pk[m] + 2u * (pk[m] / (unsigned)E)];
-#pragma unroll
-    for (int m = 0; m < E; ++m) wl[bs[m] + rk[m]] = (unsigned short)(64u * (unsigned)m + lane);
-    wave_sync_lds();
-    unsigned pred[E];  // the writer before step i in its group (sorted: its predecessor in arrival order), NONE for the first
-#pragma unroll
-    for (int m = 0; m < E; ++m) pred[m] = wl[bs[m] + (rk[m] > 0u ? rk[m] - 1u : 0u)];
-    bool unsorted = false;
-#pragma unroll
-    for (int m = 0; m < E; ++m) { if (rk[m] == 0u) pred[m] = NONE; else unsorted |= pred[m] >= 64u * (unsigned)m + lane; }
-    if (__ballot(unsorted) != 0ull) {  // never seen; kept exact: sort every group, then every step finds its place
-      if (lane == 0u && n_resorted) atomicAdd(n_resorted, 1u);
+    if (__ballot(unsorted) != 0ull) {  // never seen; kept exact: the chain's swaps in order, by one lane, on a permutation in the wave's word array
+      if (lane == 0u) {
+        if (n_resorted) atomicAdd(n_resorted, 1u);
+        // (not unrolled: unrolled, the copy loops' loads all go out first and the kernel is allocated a register per entry)
 #pragma unroll 1
-      for (int m = 0; m < E; ++m) {
-        const unsigned p = 64u * (unsigned)m + lane, g = cnt16[p + 2u * (p / (unsigned)E)], k = (p + 1u < N ? (unsigned)cnt16[p + 1u + 2u * ((p + 1u) / (unsigned)E)] : N) - g;
-        for (unsigned a = 1; a < k; ++a) {
-          const unsigned v = wl[g + a]; unsigned b = a;
-          while (b > 0u && wl[g + b - 1u] > v) { wl[g + b] = wl[g + b - 1u]; --b; }
-          wl[g + b] = (unsigned short)v;
-        }
+        for (unsigned i = 0; i < N; ++i) o[i] = (unsigned short)i;
+#pragma unroll 1
+        for (unsigned i = 0; i < N; ++i) { const unsigned p = tile[c][i]; const unsigned short a = o[i], b = o[p]; o[i] = b; o[p] = a; }
+#pragma unroll 1
+        for (unsigned i = 0; i < N; ++i) tile[c][i] = o[i];
       }
       wave_sync_lds();
-#pragma unroll 1
-      for (int m = 0; m < E; ++m) { unsigned a = 0; while (wl[bs[m] + a] != 64u * (unsigned)m + lane) ++a; pred[m] = a > 0u ? (unsigned)wl[bs[m] + a - 1u] : NONE; }
+      continue;
     }
-    {  // R, first as "the last writer of j below j, or j itself" (its array: o, free once the partners are in registers)
-      unsigned g[E], gn[E], last[E], prev[E];
+    {  // R, first as "the last writer of j below j, or j itself": every lane reads its positions' words, then the array is reused for 16-bit entries
+      unsigned lw[E];
 #pragma unroll
-      for (int m = 0; m < E; ++m) { const unsigned p = 64u * (unsigned)m + lane; g[m] = cnt16[p + 2u * (p / (unsigned)E)]; gn[m] = p + 1u < N ? (unsigned)cnt16[p + 1u + 2u * ((p + 1u) / (unsigned)E)] : N; }
-#pragma unroll
-      for (int m = 0; m < E; ++m) { const unsigned k = gn[m] - g[m]; last[m] = wl[k > 0u ? gn[m] - 1u : 0u]; prev[m] = wl[k > 1u ? gn[m] - 2u : 0u]; }
+      for (int m = 0; m < E; ++m) lw[m] = last[64u * (unsigned)m + lane];
+      wave_sync_lds();  // every lane has read its words
 #pragma unroll
       for (int m = 0; m < E; ++m) {
-        const unsigned p = 64u * (unsigned)m + lane, k = gn[m] - g[m];
-        const unsigned L = (k > 0u && last[m] < p) ? last[m] : ((k > 1u) ? prev[m] : NONE);  // (last == p: the self-swap; the writer before it)
-        o[p] = (unsigned short)(L == NONE ? p : L);
+        const unsigned p = 64u * (unsigned)m + lane;
+        // last == p + 1: the self-swap, always p's last writer - the writer before it is the step's own predecessor; nothing above p writes p (o_i >= i)
+        const unsigned L1 = lw[m] == p + 1u ? pr[m] : lw[m];  // 1 + L(p), or 0
+        o[p] = (unsigned short)(L1 != 0u ? L1 - 1u : p);
       }
     }
     wave_sync_lds();
@@ -618,9 +618,9 @@ __global__ void __launch_bounds__(256) k_sampler_shuffle_par(unsigned n_pixels, 
     {  // perm[i]: the target's own index for its first writer, else what the writer before it moved there
       unsigned val[E];
 #pragma unroll
-      for (int m = 0; m < E; ++m) val[m] = o[pred[m] != NONE ? pred[m] : 0u];
+      for (int m = 0; m < E; ++m) val[m] = o[pr[m] != 0u ? pr[m] - 1u : 0u];
 #pragma unroll
-      for (int m = 0; m < E; ++m) tile[c][64u * (unsigned)m + lane] = (unsigned short)(pred[m] != NONE ? val[m] : pk[m]);
+      for (int m = 0; m < E; ++m) tile[c][64u * (unsigned)m + lane] = (unsigned short)(pr[m] != 0u ? val[m] : pk[m]);
     }
     wave_sync_lds();
   }

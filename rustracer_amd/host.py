@@ -1328,6 +1328,19 @@ def sampler_tables(spp, dims, pixel0, n_pixels, plain=False):
     return sc, pm
 
 
+def sampler_replay(partners, kernel=1):
+    """The shuffle replay alone on caller-supplied swap partners: `partners` (n_chains, spp) u16 with i <= partners[c, i] < spp, spp a power of two. kernel 0: the
+    chain kernel (one lane per chain), 1: the parallel replay (one wave per chain, 64 <= spp <= 1024). Returns the permutations, (n_chains, spp) u16."""
+    o = np.ascontiguousarray(partners, np.uint16)
+    if o.ndim != 2:
+        raise ValueError("sampler_replay: partners must be (n_chains, spp)")
+    pm = np.zeros_like(o)
+    rc = hip_lib().rt_sampler_replay(C.c_int32(o.shape[1]), C.c_int32(o.shape[0]), _p(o, C.c_uint16), _p(pm, C.c_uint16), C.c_int32(kernel))
+    if rc < 0:
+        raise BackendError(f"rt_sampler_replay failed ({rc}): {hip_lib().rt_last_error().decode(errors='replace')}")
+    return pm
+
+
 def frame_plan(owned_pixels, spp, dims, pass_log2=29, batch_log2=19, lead_on=None, fixed_cut=None, n_cu=256):
     """rt_frame_plan (host only, no device): the cut of `owned_pixels` pixels x `spp` samples into batches and passes, as
     dict(batch_pixels, lead_pixels, pass_samples, cap, shard_cap, n_slots, multi_batch, batches=[(first pixel, pixels, samples per pass)]).
