@@ -537,6 +537,52 @@ int rt_render_rays_ao(rt_scene* scene, const float* rays, int32_t width, int32_t
 int rt_render_ao(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_ao_desc* ao,
                  const rt_shard* shard /* may be NULL */, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats /* may be NULL */);
 
+/* The Whitted integrator (integrator/whitted.rs:41-99, integrator/mod.rs:49-142). li(ray, depth): on a miss the sum of the lights' le(ray) (infinite lights only), nothing
+ * drawn. On a hit compute_scattering_functions(.., allow_multiple_lobes = false) - smooth glass is a SpecularReflection lobe over a dielectric Fresnel (1, eta) and a
+ * SpecularTransmission lobe (glass.rs:73-100), not the path integrator's single FresnelSpecular lobe - then isect.le(wo); then for EVERY light of the scene's list, in list
+ * order, u = get_2d() (consumed for delta lights too), sample_li(hit, u), skipped where li is black or pdf == 0, f = bsdf.f(wo, wi, ALL), and where f is not black and the
+ * segment is unoccluded (scene.intersect_p: alpha and shadow-alpha masks) f * li * |wi . n| / pdf with the shading normal as it was BEFORE a bump map; then, if
+ * depth + 1 < max_depth, specular_reflection and specular_transmission: sample_f(wo, get_2d(), SPECULAR | REFLECTION or TRANSMISSION) - the draw is consumed whether or
+ * not a lobe matches, and chooses among the matching lobes where a mix holds several - and where pdf > 0, f is not black and |wi . ns| != 0 the term
+ * f * li(spawn_ray(wi), depth + 1) * |wi . ns| / pdf. The camera ray is depth 0: max_depth = 1 never recurses. Unlisted emitters are seen through isect.le, never sampled.
+ * No light distribution is built. Draws are consumed depth-first, exactly as the recursion consumes them: a vertex's lights, its reflection draw, its whole reflection
+ * subtree, its transmission draw, its transmission subtree; the k-th get_2d() of a camera sample is rt_render_rays_ao's (table value 2D#(2 + k) while 2 + k < dimensions,
+ * then two draws of the sample's keyed stream in (second, first) order). The terms of a sample are added in DFS preorder, within a node Le then the lights in list order,
+ * each weighted by the product of the f |cos| / pdf factors above it; no float atomics.
+ * Stated divergence: the reflected and refracted rays carry no differentials (the reference propagates them, mod.rs:64-83, 107-136): every derivative at depth >= 1 is
+ * zero and image maps are looked up at zero width there, as at the later vertices of this backend's path frames. The first vertex reads the ray's.
+ * rt_whitted_desc: max_depth in [1, RT_WHITTED_MAX_DEPTH] (Whitted::new(n)); reserved must be 0. (Declared as a struct and a typedef of it: 8 bytes, rt_sizeof("rt_whitted_desc").)
+ *
+ * rt_render_rays_whitted: Whitted::li along the caller's rays. rays, width, height, sample0, n_samples and the sampler are rt_render_rays' - records of 8 floats, or
+ * RT_RAY_DIFF_FLOATS with RT_FLAG_RAY_DIFFERENTIALS, whose differentials enter the first vertex as in rt_render_rays; the virtual film keying; RT_RAYS_MAX; a ray with
+ * t_max not > 0 is skipped. Calls over sample ranges that add up to a range give that range's call bit for bit.
+ *   radiance  [H][W][n_samples][4] floats: L rgb as li returns it, then the status - 0, 1 scrubbed (NaN, negative luminance or infinite: renderer.rs:115-126), 2 not traced.
+ *   info      NULL, or [H][W][n_samples][RT_WHITTED_INFO_WORDS] uint32: the li invocations of the sample (tree nodes, misses included; 0 for a skipped ray) and the get_2d()
+ *             draws it consumed after the camera sample.
+ * rt_stats: camera_rays, rays_closest = every li ray, rays_shadow = the visibility segments cast, the nodes_ / tris_ counters under RT_FLAG_COUNT_TRAVERSAL, under
+ * RT_FLAG_TIME_KERNELS ms_trace_closest, ms_trace_any and ms_shade = the vertex kernel; launches_trace_path, launches_trace_shadow, launches_shade as issued;
+ * paths_scrubbed. RT_FLAG_FILM_ON_DEVICE: rays, radiance and info are device pointers. RT_ERR_INVALID with a message before any device work: what rt_render_rays refuses; a
+ * NULL whitted, max_depth < 1, reserved != 0; RT_FLAG_REF_STREAM. max_depth > RT_WHITTED_MAX_DEPTH: RT_ERR_UNSUPPORTED. Single device.
+ *
+ * rt_render_whitted: the perspective camera's frame of this integrator into rt_render's (X, Y, Z, weight) film - the same camera rays (with their differentials at the
+ * first vertex), film positions, pixel filter, max_sample_luminance, rt_shard bands and scrubbing; rt_camera_rays' records fed to rt_render_rays_whitted give its
+ * samples. Every sample of the film's sample bounds is rendered (Whitted::new leaves pixel_bounds at the empty default, whitted.rs:22-27; taken as "no crop").
+ * Refusals as above and as rt_render's. */
+#define RT_WHITTED_MAX_DEPTH 16
+#define RT_WHITTED_INFO_WORDS 2
+#define RT_WHITTED_STACK_BUDGET (1ull << 30) /* bytes of pending vertices per pass (64 B x (max_depth - 1) x paths): above it the pass is halved, the stack stays dense */
+struct rt_whitted_desc { int32_t max_depth; int32_t reserved; };
+typedef struct rt_whitted_desc rt_whitted_desc;
+int rt_render_rays_whitted(rt_scene* scene, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples,
+                           const rt_sampler_desc* sampler, const rt_whitted_desc* whitted, uint32_t flags, void* stream,
+                           float* radiance, uint32_t* info /* may be NULL */, rt_stats* stats /* may be NULL */);
+int rt_render_whitted(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_whitted_desc* whitted,
+                      const rt_shard* shard /* may be NULL */, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats /* may be NULL */);
+/* How a Whitted call sizes its passes, on numbers alone (no device): *stack_bytes (may be NULL) = 64 * (max_depth - 1) * cap, the pending stack of a pass of `cap` paths;
+ * returns 1 if such a pass, cut at 2^pass_log2 paths, is halved because the stack would exceed budget_bytes (RT_WHITTED_STACK_BUDGET in a call), else 0 - never below the
+ * smallest pass of 2^14 paths. */
+int rt_whitted_stack_plan(int32_t max_depth, uint64_t cap, int32_t pass_log2, uint64_t budget_bytes, uint64_t* stack_bytes);
+
 /* The perspective camera's rays, as a camera frame generates them - what k_raygen and bounce 0's shade kernels compute - for samples [sample0, sample0 + n_samples) of every
  * pixel of the film's sample bounds (W x H pixels, pixel_index = row * W + column): for a caller who bends them (lens distortion, a stereo offset, a rolling shutter) and
  * feeds them to rt_render_rays or a ray frame, and as the exact source of the camera's differentials.
@@ -750,7 +796,9 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
                                            then regenerate the camera ray's at bounce 0 in the frames of a camera, and load the caller's from the ray records in a call or ray-frame step with
                                            RT_FLAG_RAY_DIFFERENTIALS; without the flag caller-supplied rays have none */,
        RT_QUERY_LDS_SPEC = 7 /* the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC, read by rt_scene_create; 0: leaf holders wait,
-                                1: they keep walking up to the next leaf), 0 for every other scene */ };
+                                1: they keep walking up to the next leaf), 0 for every other scene */,
+       RT_QUERY_WHITTED_LAUNCHED = 8 /* the vertex kernel the scene's last rt_render_whitted / rt_render_rays_whitted launched: 1 k_whitted_vertex<false> (plain triangles),
+                                        2 k_whitted_vertex<true> (quadrics, object instances or masked emitters), 0 before the first call */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

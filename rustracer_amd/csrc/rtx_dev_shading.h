@@ -460,8 +460,11 @@ RT_DEV Lobe mk_spec_t(rgb3 t, float ea, float eb) {
 }
 RT_DEV Lobe mk_lambert(int kind, rgb3 r) { Lobe l = lobe_zero(kind); l.r = r; return l; }
 
-// Fills the lobes of one non-mix material; returns eta.
-RT_DEVN float material_lobes(const DScene& sc, const DMaterial& m, const SurfaceInteraction& si, Bsdf& b) {
+// Fills the lobes of one non-mix material; returns eta. MULTI: compute_scattering_functions' allow_multiple_lobes - read by glass alone (glass.rs:72-101). true is
+// what the path integrator passes (path.rs:145) and what every caller but the Whitted integrator's kernels gets: material_lobes / build_bsdf below are that form
+// under the names they had.
+template <bool MULTI>
+RT_DEV float material_lobes_body(const DScene& sc, const DMaterial& m, const SurfaceInteraction& si, Bsdf& b) {
   float eta = 1.0f;
   const int* s = m.slot;
   switch (m.kind) {
@@ -504,13 +507,16 @@ RT_DEVN float material_lobes(const DScene& sc, const DMaterial& m, const Surface
       if (!is_black(R)) { Lobe l = lobe_zero(LB_SPEC_R); l.r = R; bsdf_add(b, l); }
       break;
     }
-    case 4: {  // glass.rs:53-106, allow_multiple_lobes = true (path.rs:145)
+    case 4: {  // glass.rs:53-106; MULTI = allow_multiple_lobes (true: path.rs:145, false: whitted.rs:57)
       eta = tex_eval_f(sc, s[8], si);
       float ur = tex_eval_f(sc, s[6], si), vr = tex_eval_f(sc, s[7], si);
       rgb3 r = tex_eval(sc, s[2], si), t = tex_eval(sc, s[3], si);
       if (!is_black(r) || !is_black(t)) {
-        if (ur == 0.0f && vr == 0.0f) {
+        if (MULTI && ur == 0.0f && vr == 0.0f) {
           Lobe l = lobe_zero(LB_FRESNEL_SPEC); l.r = r; l.t = t; l.eta_a = 1.0f; l.eta_b = eta; bsdf_add(b, l);
+        } else if (!MULTI && ur == 0.0f && vr == 0.0f) {  // SpecularReflection over a dielectric Fresnel (1, eta), then SpecularTransmission (glass.rs:80-99)
+          if (!is_black(r)) { Lobe l = lobe_zero(LB_SPEC_R); l.r = r; l.fr_kind = FR_DIELECTRIC; l.fr_ei = 1.0f; l.fr_et = eta; bsdf_add(b, l); }
+          if (!is_black(t)) bsdf_add(b, mk_spec_t(t, 1.0f, eta));
         } else {
           if (m.remap) { ur = tr_roughness_to_alpha(ur); vr = tr_roughness_to_alpha(vr); }
           if (!is_black(r)) bsdf_add(b, mk_micro_r(r, ur, vr, FR_DIELECTRIC, 1.0f, eta));
@@ -624,6 +630,8 @@ RT_DEVN float material_lobes(const DScene& sc, const DMaterial& m, const Surface
   }
   return eta;
 }
+RT_DEVN float material_lobes(const DScene& sc, const DMaterial& m, const SurfaceInteraction& si, Bsdf& b) { return material_lobes_body<true>(sc, m, si, b); }
+RT_DEVN float material_lobes_single(const DScene& sc, const DMaterial& m, const SurfaceInteraction& si, Bsdf& b) { return material_lobes_body<false>(sc, m, si, b); }
 RT_DEV void scale_lobes(Bsdf& b, int first, int last, rgb3 s) {
   for (int i = first; i < last; ++i) {
     Lobe& l = b.lobes[i];
@@ -665,38 +673,56 @@ RT_DEV float material_apply(const DScene& sc, const DMaterial& m, SurfaceInterac
   if (m.bump >= 0) bump_map(sc, m.bump, si);
   return material_lobes(sc, m, si, b);
 }
-RT_DEVN void build_bsdf(const DScene& sc, int mat, SurfaceInteraction& si, Bsdf& b) {
-  b.n = 0;
-  const DMaterial& m = sc.materials[mat];
-  float eta;
-  if (m.kind != 7) eta = material_apply(sc, m, si, b);
-  else {
-    rgb3 s1 = clamp_pos(tex_eval(sc, m.slot[13], si)), s2 = clamp_pos(mkc(1, 1, 1) - s1);
-    eta = 1.0f;
-    SurfaceInteraction si2 = si;  // mat2 works on a clone taken before mat1 touches si (mixmat.rs:43); mat1's changes stay in si
-    for (int side = 0; side < 2; ++side) {
-      const DMaterial& c = sc.materials[side == 0 ? m.slot[14] : m.slot[15]];
-      SurfaceInteraction& cs = side == 0 ? si : si2;
-      int first = b.n;
-      float e;
-      if (c.kind != 7) e = material_apply(sc, c, cs, b);
-      else {
-        rgb3 c1 = clamp_pos(tex_eval(sc, c.slot[13], cs)), c2 = clamp_pos(mkc(1, 1, 1) - c1);
-        SurfaceInteraction cs2 = cs;
-        int f1 = b.n;
-        e = material_apply(sc, sc.materials[c.slot[14]], cs, b);
-        scale_lobes(b, f1, b.n, c1);
-        int f2_ = b.n;
-        (void)material_apply(sc, sc.materials[c.slot[15]], cs2, b);
-        scale_lobes(b, f2_, b.n, c2);
-      }
-      scale_lobes(b, first, b.n, side == 0 ? s1 : s2);
-      if (side == 0) eta = e;  // the Bsdf (frame, eta) of mat1 is kept, only its lobe list is replaced
-    }
-  }
-  b.eta = eta;
-  bsdf_init_frame(b, si.sh_n, si.hit.n, si.sh_dpdu);
+RT_DEV float material_apply_single(const DScene& sc, const DMaterial& m, SurfaceInteraction& si, Bsdf& b) {  // allow_multiple_lobes = false
+  if (m.bump >= 0) bump_map(sc, m.bump, si);
+  return material_lobes_single(sc, m, si, b);
 }
+// The body of build_bsdf, shared as text by its two forms (like rtx_shade_body.inl: the form every existing kernel calls stays the function it was, token for token).
+// RT_MATERIAL_APPLY: material_apply, or material_apply_single for allow_multiple_lobes = false.
+#define RT_BUILD_BSDF_BODY \
+  b.n = 0; \
+  const DMaterial& m = sc.materials[mat]; \
+  float eta; \
+  if (m.kind != 7) eta = RT_MATERIAL_APPLY(sc, m, si, b); \
+  else { \
+    rgb3 s1 = clamp_pos(tex_eval(sc, m.slot[13], si)), s2 = clamp_pos(mkc(1, 1, 1) - s1); \
+    eta = 1.0f; \
+    SurfaceInteraction si2 = si;  /* mat2 works on a clone taken before mat1 touches si (mixmat.rs:43); mat1's changes stay in si */ \
+    for (int side = 0; side < 2; ++side) { \
+      const DMaterial& c = sc.materials[side == 0 ? m.slot[14] : m.slot[15]]; \
+      SurfaceInteraction& cs = side == 0 ? si : si2; \
+      int first = b.n; \
+      float e; \
+      if (c.kind != 7) e = RT_MATERIAL_APPLY(sc, c, cs, b); \
+      else { \
+        rgb3 c1 = clamp_pos(tex_eval(sc, c.slot[13], cs)), c2 = clamp_pos(mkc(1, 1, 1) - c1); \
+        SurfaceInteraction cs2 = cs; \
+        int f1 = b.n; \
+        e = RT_MATERIAL_APPLY(sc, sc.materials[c.slot[14]], cs, b); \
+        scale_lobes(b, f1, b.n, c1); \
+        int f2_ = b.n; \
+        (void)RT_MATERIAL_APPLY(sc, sc.materials[c.slot[15]], cs2, b); \
+        scale_lobes(b, f2_, b.n, c2); \
+      } \
+      scale_lobes(b, first, b.n, side == 0 ? s1 : s2); \
+      if (side == 0) eta = e;  /* the Bsdf (frame, eta) of mat1 is kept, only its lobe list is replaced */ \
+    } \
+  } \
+  b.eta = eta; \
+  bsdf_init_frame(b, si.sh_n, si.hit.n, si.sh_dpdu);
+// Material::compute_scattering_functions(si, RADIANCE, allow_multiple_lobes). The plain call is allow_multiple_lobes = true (path.rs:145), as before; build_bsdf<false>
+// is the Whitted integrator's (whitted.rs:57), build_bsdf<true> the plain call.
+RT_DEVN void build_bsdf(const DScene& sc, int mat, SurfaceInteraction& si, Bsdf& b) {
+#define RT_MATERIAL_APPLY material_apply
+  RT_BUILD_BSDF_BODY
+#undef RT_MATERIAL_APPLY
+}
+RT_DEVN void build_bsdf_single(const DScene& sc, int mat, SurfaceInteraction& si, Bsdf& b) {
+#define RT_MATERIAL_APPLY material_apply_single
+  RT_BUILD_BSDF_BODY
+#undef RT_MATERIAL_APPLY
+}
+template <bool MULTI> RT_DEV void build_bsdf(const DScene& sc, int mat, SurfaceInteraction& si, Bsdf& b) { if (MULTI) build_bsdf(sc, mat, si, b); else build_bsdf_single(sc, mat, si, b); }
 
 // ---------------------------------------------------------------- distributions
 RT_DEV void d1_sample_continuous(const float* func, const float* cdf, float func_int, int n, float u, float& x, float& pdf, int& off) {  // distribution1d.rs:48-68

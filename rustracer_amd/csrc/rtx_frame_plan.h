@@ -23,6 +23,12 @@ struct FramePlan {
   size_t n_slots = 0;  // slots of a sharded queue (>= cap: bounce 0 of a fully traced pass uses slot = path id)
   bool multi_batch = false;
 };
+// The Whitted integrator's pending stack of a pass of `cap` paths (rtx_whitted_launch.h): four 16-byte records per level and path, max_depth - 1 levels, dense.
+static inline unsigned long long whitted_stack_bytes(int max_depth, unsigned long long cap) { return 64ull * (unsigned long long)(max_depth > 1 ? max_depth - 1 : 0) * cap; }
+// Must the pass be halved for the stack to stay within `budget` bytes? Never below the smallest pass frame_plan_cut makes (2^14 paths: 15 MiB of stack at depth 16).
+static inline bool whitted_pass_too_large(int max_depth, unsigned long long cap, int pass_log2, unsigned long long budget) {
+  return whitted_stack_bytes(max_depth, cap) > budget && pass_log2 > 14;
+}
 struct FrameBatch { unsigned long long first, pixels; unsigned pass_samples; };  // owned pixels [first, first + pixels); a short batch: more samples per pass, same paths
 
 static int frame_plan_cut(const FramePlanIn& in, FramePlan& p, const char*& why) {

@@ -23,6 +23,7 @@
 #include "rtx_cameras_launch.h"
 #include "rtx_light_eval_launch.h"
 #include "rtx_ao_launch.h"
+#include "rtx_whitted_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -108,6 +109,9 @@ struct rt_scene {
   DevBuf pfilm_in;                 // rt_frame_advance_rays*: the caller's host film positions in device memory ([pixel][sample of the step] 8 B)
   DevBuf rays_in, rays_skipped;    // rt_render_rays: the caller's host rays in device memory ([pixel][sample] 32 B), and the word k_rays_scan leaves (1: some ray is skipped)
   DevBuf ao_rays;                  // rt_render_rays_ao with a host ao_rays: [pixel][sample][occlusion sample] 32 B
+  DevBuf whitted_stack, whitted_info;  // the Whitted integrator: the pending vertices of a pass, [plane][level][path] 16 B (WhittedArgs::stack); rt_render_rays_whitted with a host info: [pixel][sample] 8 B
+  unsigned* whitted_pinned = nullptr;  // ... the shard counts of a step's queue of continuing samples, read back in pinned memory (run_whitted)
+  int whitted_launched = 0;            // ... 1 + GENERAL of the k_whitted_vertex instantiation the scene's last Whitted call launched (RT_QUERY_WHITTED_LAUNCHED)
   DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
   DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
   DevBuf bsdf_self, bsdf_tris;     // rt_bsdf_eval: a copy of `d` whose tri_p names two primitive records that carry nothing but the orientation flag (0, 1) - what a bump map reads of si.prim
@@ -126,6 +130,7 @@ struct rt_scene {
     for (int i = 0; i < 2; ++i) { for (int g = 0; g < 3; ++g) if (ev_tables[i][g]) (void)hipEventDestroy(ev_tables[i][g]); if (ev_batch_done[i]) (void)hipEventDestroy(ev_batch_done[i]); }
     if (ev_frame_begin) (void)hipEventDestroy(ev_frame_begin);
     if (aux_stream) (void)hipStreamDestroy(aux_stream);
+    if (whitted_pinned) (void)hipHostFree(whitted_pinned);
   }
 };
 
@@ -136,7 +141,7 @@ extern "C" int rt_sizeof(const char* name) {
   if (!name) return -1;
 #define RT_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);
   RT_SZ(rt_bvh_node) RT_SZ(rt_tri_meta) RT_SZ(rt_sphere) RT_SZ(rt_instance) RT_SZ(rt_texture) RT_SZ(rt_image) RT_SZ(rt_material) RT_SZ(rt_light) RT_SZ(rt_scene_desc)
-  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats) RT_SZ(rt_ao_desc)
+  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats) RT_SZ(rt_ao_desc) RT_SZ(rt_whitted_desc)
 #undef RT_SZ
   return -1;
 }
@@ -164,6 +169,7 @@ static void fill_ewa_lut() {
   rtx_shade_rays_set_ewa_lut(lut);  // ... and so has k_shade_rays'
   rtx_ref_set_ewa_lut(lut);    // ... and the reference-stream kernel's
   rtx_light_eval_set_ewa_lut(lut);  // ... and rt_light_eval's
+  rtx_whitted_set_ewa_lut(lut);     // ... and the Whitted integrator's
 }
 
 #include "rtx_bvh_build.h"
@@ -382,6 +388,7 @@ extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (what == RT_QUERY_BSDF_LAUNCHED) return s->bsdf_launched < 0 ? 0 : s->bsdf_launched + 1;
   if (what == RT_QUERY_NEEDS_DIFFERENTIALS) return s->d.needs_differentials ? 1 : 0;
   if (what == RT_QUERY_LDS_SPEC) return s->lds_spec;
+  if (what == RT_QUERY_WHITTED_LAUNCHED) return s->whitted_launched;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -1169,7 +1176,9 @@ enum FrameKind {
   FRAME_RAY_STEP,         // rt_frame_advance_rays*: ... of a ray frame, on the caller's rays and film positions
   FRAME_MODEL_STEP,       // rt_frame_advance* of a model frame: ... on the rays the frame's camera model generates
   FRAME_AO,               // rt_render_ao: rt_render's film of the ambient-occlusion integrator - bounce 0's trace, then run_ao in place of the shade launches
-  FRAME_RAYS_AO           // rt_render_rays_ao: that integrator (and Normal::li) along the caller's rays, per sample
+  FRAME_RAYS_AO,          // rt_render_rays_ao: that integrator (and Normal::li) along the caller's rays, per sample
+  FRAME_WHITTED,          // rt_render_whitted: rt_render's film of the Whitted integrator - raygen, then run_whitted's depth-first walk in place of the bounce loop
+  FRAME_RAYS_WHITTED      // rt_render_rays_whitted: Whitted::li along the caller's rays, per sample
 };
 struct FrameJob {
   FrameKind kind = FRAME_FILM;
@@ -1186,13 +1195,17 @@ struct FrameJob {
   rt_frame* frame = nullptr; unsigned step_end = 0;         // the steps
   const unsigned char* active_mask = nullptr; bool have_lock = false;
   const rt_ao_desc* ao = nullptr; float* ao_rays = nullptr;  // FRAME_AO, FRAME_RAYS_AO (the occlusion rays handed out, or NULL)
+  const rt_whitted_desc* whitted = nullptr; uint32_t* whitted_info = nullptr;  // FRAME_WHITTED, FRAME_RAYS_WHITTED (the node and draw counts handed out, or NULL)
 
   bool is_step() const { return kind == FRAME_STEP || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP; }
-  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP || kind == FRAME_RAYS_AO; }  // bounce 0 comes from ray records, not from the camera
+  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP || kind == FRAME_RAYS_AO || kind == FRAME_RAYS_WHITTED; }  // bounce 0 comes from ray records, not from the camera
   bool traces_paths() const { return kind != FRAME_CAMERA_RAYS; }
   bool masked() const { return active_mask != nullptr; }
   bool is_ao() const { return kind == FRAME_AO || kind == FRAME_RAYS_AO; }  // no shade launches, no light distribution: run_ao
-  bool to_film() const { return kind == FRAME_FILM || kind == FRAME_AO; }  // the filtered film is the call's output
+  bool is_whitted() const { return kind == FRAME_WHITTED || kind == FRAME_RAYS_WHITTED; }  // no shade launches, no light distribution: run_whitted
+  bool own_integrator() const { return is_ao() || is_whitted(); }  // the pass after ray generation is the integrator's own: fresh records written, no split shade kernels
+  bool rays_radiance() const { return kind == FRAME_RAYS || kind == FRAME_RAYS_WHITTED; }  // per-sample radiance along the caller's rays: k_raygen_rays in, k_sample_store out
+  bool to_film() const { return kind == FRAME_FILM || kind == FRAME_AO || kind == FRAME_WHITTED; }  // the filtered film is the call's output
   bool owns_film() const { return to_film() || kind == FRAME_SAMPLES; }  // the scene's film sums, own sums and filter table are reserved (a step has the frame's)
   bool stages_to_host() const { return !(flags & RT_FLAG_FILM_ON_DEVICE) && !is_step(); }  // the output goes through a device buffer of the scene's and is copied out
   bool frame_features() const { return is_step() && frame->features; }  // RT_FLAG_FRAME_FEATURES: the pass's features are summed into the frame's plane
@@ -1213,7 +1226,8 @@ struct FrameRun {
   bool all_in_bounds, has_infinite, count, shade_split, shade_live_args, ray_diff, resident, build_tables;
   ShadeRoute route; unsigned n_bins, pgrid; size_t counter_words, bin_stride; int lds_shade;
   FramePlan plan; std::vector<FrameBatch> batches;
-  double ms_ao = 0.0; float4* d_ao_rays = nullptr;  // the time of run_ao's own kernels (ms_shade of an AO call); where the occlusion rays go on the device
+  double ms_ao = 0.0; float4* d_ao_rays = nullptr;  // the time of run_ao's / run_whitted's own kernels (ms_shade of such a call); where the occlusion rays go on the device
+  uint2* d_whitted_info = nullptr; unsigned whitted_levels = 0;  // where the node and draw counts go on the device; levels of the pending stack (max_depth - 1)
   // the workspace and the outputs, bound
   float4 *d_out, *d_samples_rad, *d_cam_rays; float2 *d_samples_pf, *d_cam_pf; FeatureOut fo;
   const float4* d_rays; const float2* d_pfilm;  // (a ray step's film positions; NULL: pixel centres)
@@ -1298,7 +1312,7 @@ static int frame_setup(FrameRun& r) {
   r.tm = KTimer{(job.flags & RT_FLAG_TIME_KERNELS) != 0, r.stream, &s->event_pool};
   // integrator.preprocess (renderer.rs:30)
   r.tm.begin(&r.stats.ms_lightdist);
-  const int rc = (job.traces_paths() && !job.is_ao()) ? build_light_distribution(s, job.path->light_strategy, r.stream) : RT_OK;
+  const int rc = (job.traces_paths() && !job.own_integrator()) ? build_light_distribution(s, job.path->light_strategy, r.stream) : RT_OK;
   if (rc != RT_OK) return rc;
   r.tm.end();
   return RT_OK;
@@ -1357,7 +1371,7 @@ static void frame_route(FrameRun& r) {
   // A Lambert-only scene with its records in LDS (S1, C1) whose closest hits come from k_trace: that launch leaves a hit bit per queue entry (TraceIO::hit_mask), bounce 0
   // of a pass that traces every sample is shaded by k_shade_split<1> - k_raygen then writes neither the throughput nor the state record - and every later bounce by
   // k_shade_split<2>. RTX_SHADE_SPLIT=0 (measurement knob, read per call): k_shade<1, .., 1> for every bounce, no masks, raygen as before.
-  r.shade_split = s->lambert_only && s->lds_records && closest_is_k_trace(s, r.count) && !job.is_ao() && !env_is("RTX_SHADE_SPLIT", '0');
+  r.shade_split = s->lambert_only && s->lds_records && closest_is_k_trace(s, r.count) && !job.own_integrator() && !env_is("RTX_SHADE_SPLIT", '0');
   // RTX_SHADE_KARGS=0 (measurement knob, read per call): such a scene's three shade kernels in the form that keeps the kernel arguments live through the vertex (the
   // control of round 10: k_shade_const_live, k_shade_split_live); the other front-ends have one form, chosen at compile time (RT_SHADE_KARGS)
   r.shade_live_args = env_is("RTX_SHADE_KARGS", '0');
@@ -1399,6 +1413,14 @@ static int reserve_workspace(FrameRun& r) {
     if (r.route.use_bins) { want.push_back({&s->bin_words, (size_t)(r.fp.max_depth + 1) * r.bin_stride * 4}); want.push_back({&s->bin_sorted, (size_t)cap * 4}); want.push_back({&s->bin_at, (size_t)cap * 2}); }
     if (r.plan.multi_batch && !r.resident) { want.push_back({&s->scrambles[1], (size_t)batch_pixels * 3 * dims * 4}); want.push_back({&s->perms[1], (size_t)(batch_pixels * table_bytes_per_pixel)}); }
     if (job.frame_features()) want.push_back({&s->feat, cap * 32});
+    if (job.is_whitted()) {  // the pending stack of a pass, sized from max_depth; over the budget the PASS is halved, the stack stays dense
+      r.whitted_levels = (unsigned)(job.whitted->max_depth - 1);
+      const unsigned long long stack_bytes = whitted_stack_bytes(job.whitted->max_depth, cap);
+      const char* be = getenv("RTX_WHITTED_STACK_BUDGET");  // (test knob, read per call: the budget in bytes)
+      if (whitted_pass_too_large(job.whitted->max_depth, cap, in.pass_log2, be ? strtoull(be, nullptr, 10) : (unsigned long long)RT_WHITTED_STACK_BUDGET)) continue;
+      want.push_back({&s->whitted_stack, (size_t)stack_bytes});
+      if (job.whitted_info && job.stages_to_host()) want.push_back({&s->whitted_info, (size_t)nws * 8});
+    }
     if (job.stages_to_host()) {
       if (job.kind == FRAME_SAMPLE_FEATURES) want.push_back({&s->samples_feat, (size_t)nws * RT_FEATURE_FLOATS * 4});
       else if (job.kind == FRAME_CAMERA_RAYS) { want.push_back({&s->rays_in, (size_t)nws * r.rec_floats * 4}); if (job.cam_out->p_film) want.push_back({&s->pfilm_in, (size_t)nws * 8}); }  // (staged for the copy to the host)
@@ -1446,6 +1468,13 @@ static int bind_outputs(FrameRun& r) {
   if (job.ao_rays) {  // zeros for the rays of a miss or a skipped ray
     r.d_ao_rays = on_device ? (float4*)job.ao_rays : s->ao_rays.as<float4>();
     HIP_TRY(hipMemsetAsync(r.d_ao_rays, 0, (size_t)r.n_window_samples * (size_t)job.ao->n_samples * 32, r.stream));
+  }
+  if (job.is_whitted()) {
+    if (!s->whitted_pinned) HIP_TRY(hipHostMalloc((void**)&s->whitted_pinned, (size_t)RT_QSHARDS * RT_CNT_STRIDE * 4, hipHostMallocDefault));
+    if (job.whitted_info) {  // zeros for a skipped ray
+      r.d_whitted_info = on_device ? (uint2*)job.whitted_info : s->whitted_info.as<uint2>();
+      HIP_TRY(hipMemsetAsync(r.d_whitted_info, 0, (size_t)r.n_window_samples * 8, r.stream));
+    }
   }
   if (job.to_film()) {  // (no kernel of a per-sample kind reads the filter table or the film sums; a progressive frame keeps its own)
     HIP_TRY(hipMemcpyAsync(s->filter_table.p, job.film->filter_table, 1024, hipMemcpyHostToDevice, r.stream));
@@ -1653,6 +1682,68 @@ static int run_ao(FrameRun& r, int buf) {
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }
+// The Whitted integrator's pass after ray generation (Whitted::li, integrator/whitted.rs:41-99): a depth-first walk per camera sample, wavefront over samples. A step
+// advances every still-active sample by one node of its own tree: the scene's closest-hit launch over the samples' current rays - the launch of run_bounce and run_ao -,
+// then max(n_lights, 1) rounds of k_whitted_vertex (rtx_whitted_launch.h) - one light per round, so one shadow record per sample and round: the any-hit launch after a
+// round adds a clear record's term into lacc[path] without a race and in list order - the last of which moves the sample on and appends it to the next step's queue.
+// Launches per step: 1 + max(n_lights, 1) + n_lights. The two queues alternate between counter blocks 1 and 2 (block 0 is raygen's), zeroed before they are appended
+// to. After every step the eight shard counts of the next queue are read back into pinned memory; the pass ends when they are zero - 2^max_depth - 1 steps at the most,
+// never by that bound alone. Nothing is allocated between launches (reserve_workspace, bind_outputs).
+static int run_whitted(FrameRun& r, int buf) {
+  const FrameJob& job = r.job; rt_scene* const s = r.s; hipStream_t stream = r.stream; KTimer& tm = r.tm; rt_stats& stats = r.stats; PassState& ps = r.ps;
+  const unsigned pgrid = r.pgrid; const bool count = r.count;
+  unsigned* const cb = s->counters.as<unsigned>(); unsigned long long* const dstats = s->stats.as<unsigned long long>();
+  const size_t block_words = (size_t)RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;
+  ps.fresh = 0; ps.skip_dead_tail = 0;
+  r.io_path.hit_mask = nullptr;
+  WhittedArgs a{};
+  a.n_lights = s->d.n_lights; a.n_rounds = (unsigned)std::max(a.n_lights, 1); a.max_depth = job.whitted->max_depth;
+  a.wst = (uint4*)sraw(ps.mi.a); a.stack = s->whitted_stack.as<float4>(); a.levels = r.whitted_levels; a.stack_cap = (size_t)r.plan.cap;
+  if (r.ray_diff) a.rdiff = RayDiffSrc{r.d_rays, r.src.sample0, r.src.n_samples, r.rec_floats / 4u};
+  const bool general = s->has_spheres || s->has_instances || s->masked_emitters;
+  s->whitted_launched = general ? 2 : 1;
+  const unsigned max_steps = (1u << a.max_depth) - 1u;  // the nodes of a full binary tree of max_depth levels
+  for (unsigned step = 0; step < max_steps; ++step) {
+    a.step = step;
+    std::swap(ps.in, ps.out);  // what the previous stage appended is this step's input
+    ps.cnt_in = step == 0 ? (r.all_in_bounds ? nullptr : cb) : cb + (size_t)(1 + ((step - 1) & 1u)) * block_words;  // (step 0 of a pass that traces every sample: entry i is slot i is path i)
+    ps.cnt_out = cb + (size_t)(1 + (step & 1u)) * block_words;
+    r.io_path.ray_o = ps.in.o; r.io_path.ray_d = ps.in.d;
+    tm.begin(&stats.ms_trace_closest);
+    launch_trace<false>(s, count, r.io_path, ps.cnt_in, ps.cnt_in, ps.shard_cap, ps.cap, dstats, ST_RAYS_CLOSEST, ST_NODES_CLOSEST, ST_TRIS_CLOSEST, stream);
+    tm.end();
+    stats.launches_trace_closest += 1; stats.launches_trace_path += 1;
+    if (step == 0 && r.build_tables) for (int g = 1; g < 3; ++g) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][g], 0));  // 2-D tables 2 ...: the first draws
+    for (unsigned round = 0; round < a.n_rounds; ++round) {
+      a.round = round;
+      HIP_TRY(hipMemsetAsync(ps.cnt_out, 0, block_words * 4, stream));  // (the queue of continuing samples is appended to by the last round alone)
+      tm.begin(&r.ms_ao);
+      rtx_launch_whitted_vertex(general, pgrid, stream, *r.dsc, r.fp, ps, a);
+      tm.end();
+      stats.launches_shade += 1;
+      if ((int)round < a.n_lights) {
+        tm.begin(&stats.ms_trace_any);
+        launch_trace<true>(s, count, r.io_shadow, ps.q_shadow, ps.cnt_out + RT_QSHARDS * RT_CNT_STRIDE, ps.shard_cap, 0, dstats, ST_RAYS_SHADOW, ST_NODES_SHADOW, ST_TRIS_SHADOW, stream);
+        tm.end();
+        stats.launches_trace_shadow += 1;
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->whitted_pinned, ps.cnt_out, (size_t)RT_QSHARDS * RT_CNT_STRIDE * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned active = 0;
+    for (int k = 0; k < RT_QSHARDS; ++k) active += s->whitted_pinned[k * RT_CNT_STRIDE];
+    if (active == 0u) break;
+  }
+  if (r.d_whitted_info) {  // k_sample_store's indexing: the call's samples per pixel as the row length, its first sample as sample 0
+    PassState po = ps; po.spp = r.src.n_samples; po.s0 = ps.s0 - r.src.sample0;
+    tm.begin(&r.ms_ao);
+    rtx_launch_whitted_info(pgrid, stream, r.fp, po, a, r.wx0, r.wy0, r.wx1 - r.wx0, r.d_whitted_info);
+    tm.end();
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
 // tiles of 2^(8 - ts) pixels x 2^ts samples of k_raygen_rays / k_raygen_rays_film: ts = log2(min(16, the pass's samples rounded up))
 static unsigned ray_tile_samples_log2(unsigned n_samples) { unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < n_samples) ++ts_log2; return ts_log2; }
 // One pass - samples [s0, s0 + n_samples) of the batch's pixels: ray generation by kind, the bounces, and the pass's film or store kernel by kind
@@ -1665,7 +1756,7 @@ static int run_pass(FrameRun& r, int buf, unsigned s0, unsigned n_samples, unsig
   if (r.route.use_bins) HIP_TRY(hipMemsetAsync(s->bin_words.p, 0, (size_t)(fp.max_depth + 1) * r.bin_stride * 4, stream));
   ps.cnt_in = nullptr; ps.cnt_out = s->counters.as<unsigned>();  // raygen appends to block 0's `out` queue
   ps.all_in_bounds = r.all_in_bounds ? 1 : 0;
-  const int fresh_planes = (r.all_in_bounds && !job.is_ao()) ? ((s->lambert_only && s->lds_records) ? (r.shade_split ? 3 : RT_FRESH_RECORDS_LDS) : RT_FRESH_RECORDS) : 0;  // which records k_raygen leaves out (PassState::fresh; k_shade_split<1> reads neither)
+  const int fresh_planes = (r.all_in_bounds && !job.own_integrator()) ? ((s->lambert_only && s->lds_records) ? (r.shade_split ? 3 : RT_FRESH_RECORDS_LDS) : RT_FRESH_RECORDS) : 0;  // which records k_raygen leaves out (PassState::fresh; k_shade_split<1> reads neither)
   ps.fresh = fresh_planes;
   // a frame that counts node visits keeps the reference's closest-hit walk for every MIS ray, unless it is asked to count what a production frame walks
   const bool as_rendered = !r.count || (job.flags & RT_FLAG_COUNT_AS_RENDERED);
@@ -1694,18 +1785,19 @@ static int run_pass(FrameRun& r, int buf, unsigned s0, unsigned n_samples, unsig
     rtx_launch_raygen_rays_film(pgrid, stream, fp, ps, r.d_rays, r.d_pfilm, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), job.active_mask);
   }
   else if (job.masked()) hipLaunchKernelGGL(k_raygen_masked, dim3(pgrid), dim3(256), 0, stream, fp, ps, job.active_mask);
-  else if (job.kind == FRAME_RAYS || job.kind == FRAME_RAYS_AO) rtx_launch_raygen_rays(pgrid, stream, fp, ps, r.d_rays, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), r.d_samples_rad);
+  else if (job.rays_radiance() || job.kind == FRAME_RAYS_AO) rtx_launch_raygen_rays(pgrid, stream, fp, ps, r.d_rays, r.src.sample0, r.src.n_samples, rec4, ray_tile_samples_log2(ps.n_samples), r.d_samples_rad);
   else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
   tm.end();
   if (job.is_ao()) { const int rc = run_ao(r, buf); if (rc != RT_OK) return rc; }
-  const int last_bounce = job.is_ao() ? -1 : (job.kind == FRAME_SAMPLE_FEATURES ? 0 : fp.max_depth);
+  if (job.is_whitted()) { const int rc = run_whitted(r, buf); if (rc != RT_OK) return rc; }
+  const int last_bounce = job.own_integrator() ? -1 : (job.kind == FRAME_SAMPLE_FEATURES ? 0 : fp.max_depth);
   for (int bounce = 0; bounce <= last_bounce; ++bounce) {
     const int rc = run_bounce(r, buf, bounce, fresh_planes, skip_dead_tail);
     if (rc != RT_OK) return rc;
   }
   tm.begin(&stats.ms_film);
   if (job.kind == FRAME_SAMPLE_FEATURES || job.kind == FRAME_RAYS_AO) { }  // (the feature kernels / k_ao_finish wrote the output)
-  else if (job.kind == FRAME_RAYS) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
+  else if (job.rays_radiance()) {  // [pixel][sample of the call]: k_sample_store's indexing with the call's samples per pixel as the row length and its first sample as sample 0
     PassState po = ps; po.spp = r.src.n_samples; po.s0 = ps.s0 - r.src.sample0;
     hipLaunchKernelGGL(k_sample_store, dim3(pgrid), dim3(256), 0, stream, fp, po, r.wx0, r.wy0, r.wx1 - r.wx0, r.d_samples_rad, (float2*)nullptr);
   }
@@ -1803,6 +1895,7 @@ static int finish_frame(FrameRun& r) {
     HIP_TRY(hipMemcpyAsync(job.samples_rad, r.d_samples_rad, nws * 16, hipMemcpyDeviceToHost, stream));
     if (job.samples_pf) HIP_TRY(hipMemcpyAsync(job.samples_pf, r.d_samples_pf, nws * 8, hipMemcpyDeviceToHost, stream));
     if (job.ao_rays) HIP_TRY(hipMemcpyAsync(job.ao_rays, r.d_ao_rays, nws * (size_t)job.ao->n_samples * 32, hipMemcpyDeviceToHost, stream));
+    if (job.whitted_info) HIP_TRY(hipMemcpyAsync(job.whitted_info, r.d_whitted_info, nws * 8, hipMemcpyDeviceToHost, stream));
   }
   HIP_TRY(hipStreamSynchronize(stream));
   r.tm.collect();
@@ -1982,6 +2075,52 @@ extern "C" int rt_render_ao(rt_scene* s, const rt_camera* cam, const rt_film_des
   const rt_path_desc p = ao_path_desc(*film);
   FrameJob job = frame_job(FRAME_AO, s, cam, film, smp, &p, flags, stream_);
   job.shard = shard; job.film_xyzw = film_xyzw; job.ao = ao; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// The stack of a pass and whether the pass has to be halved for it (rtx_frame_plan.h), on numbers alone
+extern "C" int rt_whitted_stack_plan(int32_t max_depth, uint64_t cap, int32_t pass_log2, uint64_t budget_bytes, uint64_t* stack_bytes) {
+  if (stack_bytes) *stack_bytes = whitted_stack_bytes(max_depth, cap);
+  return whitted_pass_too_large(max_depth, cap, pass_log2, budget_bytes) ? 1 : 0;
+}
+// What both Whitted entry points refuse of their descriptor
+static int whitted_desc_check(const char* who, const rt_whitted_desc* w) {
+  const std::string n(who);
+  if (w->max_depth < 1) return fail(RT_ERR_INVALID, n + ": whitted->max_depth must be >= 1 (Whitted::new(n): the camera ray is depth 0)");
+  if (w->reserved != 0) return fail(RT_ERR_INVALID, n + ": whitted->reserved must be 0");
+  if (w->max_depth > RT_WHITTED_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, n + ": whitted->max_depth > RT_WHITTED_MAX_DEPTH (16)");
+  return RT_OK;
+}
+// a path descriptor of a Whitted call: depth 1 (two blocks of queue counters past raygen's, which the steps alternate between), nothing else of it is read
+static rt_path_desc whitted_path_desc(const rt_film_desc& film) { rt_path_desc p{}; memcpy(p.pixel_bounds, film.sample_bounds, 16); p.max_depth = 1; return p; }
+// Whitted::li along the caller's rays, over the virtual film of the batch.
+extern "C" int rt_render_rays_whitted(rt_scene* s, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, const rt_sampler_desc* smp,
+                                      const rt_whitted_desc* whitted, uint32_t flags, void* stream_, float* radiance, uint32_t* info, rt_stats* stats_out) {
+  // every refusal comes before any device work (and before the scene is looked at)
+  if (!s || !rays || !smp || !whitted || !radiance) return fail(RT_ERR_INVALID, "rt_render_rays_whitted: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_rays_whitted: the reference-stream frame has no per-sample output");
+  if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rt_render_rays_whitted: width, height and n_samples must be positive");
+  int rc = sample_range_check("rt_render_rays_whitted", smp, sample0, n_samples, (unsigned long long)width, (unsigned long long)height, "must lie inside");
+  if (rc != RT_OK) return rc;
+  if ((rc = whitted_desc_check("rt_render_rays_whitted", whitted)) != RT_OK) return rc;
+  const rt_camera cam{};
+  const rt_film_desc film = virtual_film(width, height);
+  const rt_path_desc p = whitted_path_desc(film);
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, ray_rec_floats(flags)};
+  FrameJob job = frame_job(FRAME_RAYS_WHITTED, s, &cam, &film, smp, &p, flags, stream_);
+  job.ray_src = &src; job.samples_rad = radiance; job.whitted = whitted; job.whitted_info = info; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// The perspective camera's frame of the Whitted integrator: rt_render's film with L = Whitted::li.
+extern "C" int rt_render_whitted(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_whitted_desc* whitted, const rt_shard* shard,
+                                 uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out) {
+  if (!s || !cam || !film || !smp || !whitted || !film_xyzw) return fail(RT_ERR_INVALID, "rt_render_whitted: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_whitted: the reference-stream frame renders the path integrator only");
+  int rc = sampler_check("rt_render_whitted", smp);
+  if (rc != RT_OK) return rc;
+  if ((rc = whitted_desc_check("rt_render_whitted", whitted)) != RT_OK) return rc;
+  const rt_path_desc p = whitted_path_desc(*film);
+  FrameJob job = frame_job(FRAME_WHITTED, s, cam, film, smp, &p, flags, stream_);
+  job.shard = shard; job.film_xyzw = film_xyzw; job.whitted = whitted; job.stats_out = stats_out;
   return render_frame(job);
 }
 // The perspective camera's rays (and film positions) of samples [sample0, sample0 + n_samples) of every pixel of the film's sample bounds, as a camera frame generates

@@ -1386,6 +1386,44 @@ int rtxh_render_ao(rtxh_scene* s, const rtxh_render_params* p, int32_t ao_sample
   rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
   return rt_render_ao(s->dev, &cf.cam, &cf.film, &smp, &ao, &shard, p->flags, stream, film_xyzw, stats);
 }
+// what rt_render_rays_whitted / rt_render_whitted refuse of the integrator's parameter, before the scene is uploaded
+static int whitted_params_check(const char* who, int32_t max_depth) {
+  if (max_depth < 1) return fail(RT_ERR_INVALID, std::string(who) + ": max_depth must be >= 1 (Whitted::new(n): the camera ray is depth 0)");
+  if (max_depth > RT_WHITTED_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": max_depth > RT_WHITTED_MAX_DEPTH (16)");
+  return RT_OK;
+}
+// Whitted::li along the caller's rays (rt_render_rays_whitted)
+int rtxh_render_rays_whitted(rtxh_scene* s, const rtxh_render_params* p, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, int32_t max_depth,
+                             void* stream, float* radiance, uint32_t* info, rt_stats* stats) {
+  if (!s || !p || !rays || !radiance) return fail(RT_ERR_INVALID, "rtxh_render_rays_whitted: null argument");
+  g_err.clear();
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_whitted_desc w{max_depth, 0};
+  {  // what rt_render_rays_whitted refuses, before the scene is uploaded for it
+    long long spp = 1; while (spp < (long long)std::max(p->spp, 1)) spp <<= 1;
+    if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rtxh_render_rays_whitted: width, height and n_samples must be positive");
+    if (sample0 < 0 || (long long)sample0 + (long long)n_samples > spp) return fail(RT_ERR_INVALID, "rtxh_render_rays_whitted: [sample0, sample0 + n_samples) must lie inside [0, spp)");
+    if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX / (unsigned long long)n_samples)
+      return fail(RT_ERR_INVALID, "rtxh_render_rays_whitted: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+    int rc = whitted_params_check("rtxh_render_rays_whitted", max_depth); if (rc != RT_OK) return rc;
+    if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_rays_whitted: the reference-stream frame has no per-sample output");
+  }
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_rays_whitted(s->dev, rays, width, height, sample0, n_samples, &smp, &w, p->flags, stream, radiance, info, stats);
+}
+// The frame of rtxh_render with the Whitted integrator (rt_render_whitted): camera and film exactly as rtxh_render sets them up.
+int rtxh_render_whitted(rtxh_scene* s, const rtxh_render_params* p, int32_t max_depth, void* stream, float* film_xyzw, rt_stats* stats) {
+  if (!s || !p || !film_xyzw) return fail(RT_ERR_INVALID, "rtxh_render_whitted: null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  if ((rc = whitted_params_check("rtxh_render_whitted", max_depth)) != RT_OK) return rc;
+  if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_whitted: the reference-stream frame renders the path integrator only");
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_whitted_desc w{max_depth, 0};
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  return rt_render_whitted(s->dev, &cf.cam, &cf.film, &smp, &w, &shard, p->flags, stream, film_xyzw, stats);
+}
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
 int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {

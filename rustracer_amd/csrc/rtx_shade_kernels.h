@@ -82,7 +82,9 @@ typedef SingleLambertT<false> SingleLambert;
 // (bsdf/mod.rs:94-251) restated over two named lobes; every lobe function is entered with its kind as a constant, so only that
 // kind's code is instantiated. Same operations in the same order as GenericBsdf (sums start from the same zero, the same component
 // choice and u remap), hence the same values.
-template <bool WIDE, bool CONST_TEX = false>  // WIDE: + glass, substrate and the opaque uber form (FresnelSpecular, FresnelBlend, microfacet transmission; a Bsdf eta); CONST_TEX: every texture parameter is a constant (no out-of-line image lookup is instantiated)
+// MULTI: compute_scattering_functions' allow_multiple_lobes, read by glass alone - true is the path integrator's (every shade kernel), false the Whitted integrator's form
+// (build_bsdf<false>, rtx_dev_shading.h): smooth glass as SpecularReflection + SpecularTransmission
+template <bool WIDE, bool CONST_TEX = false, bool MULTI = true>  // WIDE: + glass, substrate and the opaque uber form (FresnelSpecular, FresnelBlend, microfacet transmission; a Bsdf eta); CONST_TEX: every texture parameter is a constant (no out-of-line image lookup is instantiated)
 struct SmallBsdfT {
   static RT_DEV rgb3 tc(const DScene& sc, int id, const SurfaceInteraction& si) { if (CONST_TEX) { const DTexture& t = sc.textures[id]; return mkc(t.v[0], t.v[1], t.v[2]); } return tex_eval_c(sc, id, si); }
   static RT_DEV float tcf(const DScene& sc, int id, const SurfaceInteraction& si) { return tc(sc, id, si).r; }
@@ -91,13 +93,16 @@ struct SmallBsdfT {
   RT_DEV void build(const DScene& sc, int mat, SurfaceInteraction& si) {
     const DMaterial& m = sc.materials[mat]; const int* s = m.slot;
     n = 0; l0 = lobe_zero(LB_LAMBERT_R); l1 = l0; eta_ = 1.0f;
-    if (WIDE && m.kind == 4) {  // glass.rs:53-106, allow_multiple_lobes = true (path.rs:145): one FresnelSpecular lobe, or microfacet reflection + transmission
+    if (WIDE && m.kind == 4) {  // glass.rs:53-106, allow_multiple_lobes = MULTI (true: path.rs:145): one FresnelSpecular lobe, or microfacet reflection + transmission
       eta_ = tcf(sc, s[8], si);
       float ur = tcf(sc, s[6], si), vr = tcf(sc, s[7], si);
       rgb3 r = tc(sc, s[2], si), t = tc(sc, s[3], si);
       if (!is_black(r) || !is_black(t)) {
-        if (ur == 0.0f && vr == 0.0f) {
+        if (MULTI && ur == 0.0f && vr == 0.0f) {
           Lobe l = lobe_zero(LB_FRESNEL_SPEC); l.r = r; l.t = t; l.eta_a = 1.0f; l.eta_b = eta_; add(l);
+        } else if (!MULTI && ur == 0.0f && vr == 0.0f) {  // glass.rs:80-99: SpecularReflection over a dielectric Fresnel (1, eta), then SpecularTransmission
+          if (!is_black(r)) { Lobe l = lobe_zero(LB_SPEC_R); l.r = r; l.fr_kind = FR_DIELECTRIC; l.fr_ei = 1.0f; l.fr_et = eta_; add(l); }
+          if (!is_black(t)) add(mk_spec_t(t, 1.0f, eta_));
         } else {
           if (m.remap) { ur = tr_roughness_to_alpha(ur); vr = tr_roughness_to_alpha(vr); }
           if (!is_black(r)) add(mk_micro_r(r, ur, vr, FR_DIELECTRIC, 1.0f, eta_));
@@ -168,6 +173,7 @@ struct SmallBsdfT {
       case LB_FRESNEL_SPEC: if (WIDE) { c.kind = LB_FRESNEL_SPEC; return fn(c); } break;
       case LB_FRESNEL_BLEND: if (WIDE) { c.kind = LB_FRESNEL_BLEND; return fn(c); } break;
       case LB_MICRO_T: if (WIDE) { c.kind = LB_MICRO_T; return fn(c); } break;
+      case LB_SPEC_T: if (WIDE && !MULTI) { c.kind = LB_SPEC_T; return fn(c); } break;
       default: break;
     }
     c.kind = LB_LAMBERT_R; return fn(c);

@@ -48,6 +48,9 @@ RT_SAMPLES_MAX = 1 << 27
 RT_RAYS_MAX = 1 << 27       # rt_render_rays: rays per call (4 GiB of rays, 2 GiB of radiance); a larger job is cut by sample range
 RT_AO_FLOATS = 4            # rt_render_rays_ao: floats per ray of its output (ao, |d . n|, t, status)
 RT_AO_SAMPLES_MAX = 1024    # ... and the most occlusion rays per hit
+RT_WHITTED_MAX_DEPTH = 16   # rt_render_whitted / rt_render_rays_whitted: the deepest recursion (Whitted::new(n))
+RT_WHITTED_INFO_WORDS = 2   # rt_render_rays_whitted: uint32 per ray of its info output (li invocations, get_2d() draws)
+RT_QUERY_WHITTED_LAUNCHED = 8  # rt_scene_query: 1 + GENERAL of the k_whitted_vertex instantiation the scene's last Whitted call launched (0: none yet)
 RT_QUERY_LDS_SPEC = 7  # rt_scene_query: the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC: 0, 1)
 RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
 RT_QUERY_BSDF_LAUNCHED = 5# rt_scene_query: 1 + 2 * mode + const_tex of the k_bsdf_eval instantiation the scene's last bsdf_eval launched (0 generic, 3 / 5 / 6)
@@ -110,6 +113,11 @@ class RenderParams(C.Structure):
 class AoDesc(C.Structure):
     """rt_ao_desc (rtx_hip.h): the ambient-occlusion integrators' parameters."""
     _fields_ = [("n_samples", C.c_int32), ("max_distance", C.c_float)]
+
+
+class WhittedDesc(C.Structure):
+    """rt_whitted_desc (rtx_hip.h): the Whitted integrator's parameters."""
+    _fields_ = [("max_depth", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -870,6 +878,73 @@ class HostScene:
         p.flags = flags
         film = np.zeros((h, w, 4), np.float32)
         _check(L.rtxh_render_ao(self.h, C.byref(p), int(n_samples), float(max_distance), C.c_void_p(stream), _p(film), C.byref(stats)), "render_ao")
+        return film, stats.as_dict()
+
+    def render_rays_whitted(self, rays, max_depth=5, sample0=0, spp=None, with_info=False, device_out=None, stream=0, count_traversal=False, time_kernels=False,
+                            device_info_out=None):
+        """The Whitted integrator along caller-supplied rays (rt_render_rays_whitted: Whitted::li). `rays` as in `render_rays` - (H, W, ns, 8) float32, or 20 floats
+        whose differentials enter the first vertex; ray (x, y, sl) is sample sample0 + sl of pixel y * W + x of a virtual W x H film. `max_depth` is Whitted::new(n):
+        the camera ray is depth 0, 1 never recurses. Returns (L (H, W, ns, 4), info or None, stats): L rgb as li returns it and the status 0 / 1 scrubbed / 2 not traced
+        (t_max not > 0); `with_info`: info (H, W, ns, 2) uint32 - the li invocations of the sample (tree nodes, misses included) and the get_2d() draws it consumed after
+        the camera sample. `rays` may be a contiguous torch CUDA float32 tensor: `device_out` must then be one of shape (H, W, ns, 4), and with `with_info`
+        `device_info_out` an int32 one of shape (H, W, ns, 2) (RT_FLAG_FILM_ON_DEVICE: all stay in HBM); they are returned."""
+        p = self._render_params()
+        if spp is not None:
+            p.spp = int(spp)
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        on_device = hasattr(rays, "data_ptr")
+        if not on_device:
+            rays = np.ascontiguousarray(rays, np.float32)
+        if len(rays.shape) != 4 or rays.shape[3] not in (8, RT_RAY_DIFF_FLOATS):
+            raise BackendError(f"render_rays_whitted: rays must have shape (H, W, ns, 8 | {RT_RAY_DIFF_FLOATS}), not {tuple(rays.shape)}")
+        if rays.shape[3] == RT_RAY_DIFF_FLOATS:
+            p.flags |= RT_FLAG_RAY_DIFFERENTIALS
+        h, w, ns = (int(v) for v in rays.shape[:3])
+        if h * w * ns > RT_RAYS_MAX:
+            raise BackendError(f"render_rays_whitted: {h} x {w} x {ns} rays are more than RT_RAYS_MAX - cut the job by sample range")
+        L = lib()
+        L.rtxh_render_rays_whitted.restype = C.c_int
+        L.rtxh_render_rays_whitted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if on_device:
+            ok = device_out is not None and tuple(device_out.shape) == (h, w, ns, 4) and rays.is_contiguous() and device_out.is_contiguous() and rays.element_size() == 4 and device_out.element_size() == 4
+            if with_info:
+                ok = ok and device_info_out is not None and tuple(device_info_out.shape) == (h, w, ns, RT_WHITTED_INFO_WORDS) and device_info_out.is_contiguous() and device_info_out.element_size() == 4
+            if not ok:
+                raise BackendError("render_rays_whitted: device rays need a contiguous float32 device_out of shape (H, W, ns, 4), and with_info a 4-byte integer device_info_out of shape (H, W, ns, 2)")
+            p.flags |= RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_rays_whitted(self.h, C.byref(p), C.c_void_p(rays.data_ptr()), w, h, int(sample0), ns, int(max_depth), C.c_void_p(stream),
+                                              C.c_void_p(device_out.data_ptr()), C.c_void_p(device_info_out.data_ptr()) if with_info else None, C.byref(stats)), "render_rays_whitted")
+            return device_out, (device_info_out if with_info else None), stats.as_dict()
+        if device_out is not None or device_info_out is not None:
+            raise BackendError("render_rays_whitted: device outputs need device rays (RT_FLAG_FILM_ON_DEVICE names every pointer)")
+        rad = np.zeros((h, w, ns, 4), np.float32)
+        info = np.zeros((h, w, ns, RT_WHITTED_INFO_WORDS), np.uint32) if with_info else None
+        _check(L.rtxh_render_rays_whitted(self.h, C.byref(p), rays.ctypes.data_as(C.c_void_p), w, h, int(sample0), ns, int(max_depth), C.c_void_p(stream),
+                                          rad.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p) if with_info else None, C.byref(stats)), "render_rays_whitted")
+        return rad, info, stats.as_dict()
+
+    def render_whitted(self, max_depth=5, rank=0, world_size=1, count_traversal=False, time_kernels=False, device_out=None, stream=0):
+        """The frame of `render` with the Whitted integrator (rt_render_whitted): the same camera rays, film positions, pixel filter and shard bands, every sample's
+        L = Whitted::li(ray, 0) with recursion limit `max_depth`. Returns (film_xyzw (H, W, 4) over the cropped bounds, stats dict).
+        `device_out`: optional torch CUDA tensor (H, W, 4) float32 that receives the film in HBM."""
+        flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        st = self.setup(rank=rank, world_size=world_size)
+        cr = st["cropped"]
+        w, h = int(cr[2] - cr[0]), int(cr[3] - cr[1])
+        p = st["params"]
+        L = lib()
+        L.rtxh_render_whitted.restype = C.c_int
+        L.rtxh_render_whitted.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if device_out is not None:
+            assert tuple(device_out.shape) == (h, w, 4) and device_out.is_contiguous()
+            p.flags = flags | RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_whitted(self.h, C.byref(p), int(max_depth), C.c_void_p(stream), C.c_void_p(device_out.data_ptr()), C.byref(stats)), "render_whitted")
+            return device_out, stats.as_dict()
+        p.flags = flags
+        film = np.zeros((h, w, 4), np.float32)
+        _check(L.rtxh_render_whitted(self.h, C.byref(p), int(max_depth), C.c_void_p(stream), _p(film), C.byref(stats)), "render_whitted")
         return film, stats.as_dict()
 
     def texture_words(self, tex):

@@ -3,7 +3,7 @@
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
                                   [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials] [--device-camera]]
-                                  [--ao N [--ao-distance D]]
+                                  [--ao N [--ao-distance D]] [--whitted [MAXDEPTH]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -38,7 +38,10 @@ RT_FRAME_RGB8's bytes, a .pfm the frame's sums over their weights); honours --pr
 --ao N [--ao-distance D]: the file's camera, film, filter and sampler with the reference's ambient-occlusion integrator (rt_render_ao; integrator/ao.rs) in place of the
 file's Integrator: every camera sample's value is the clear fraction of N occlusion rays over the hemisphere of the first hit's geometric normal, rays of length D
 (default: infinite, the reference). A choice of this command line: the loader's Integrator handling is unchanged (it refuses "ambientocclusion" as it refuses
-"whitted"). One call, one device: --preview-every, --adaptive, --features, --samples, --devices and --camera-model do not combine with it."""
+"whitted"). One call, one device: --preview-every, --adaptive, --features, --samples, --devices and --camera-model do not combine with it.
+--whitted [MAXDEPTH]: the same with the reference's Whitted integrator (rt_render_whitted; integrator/whitted.rs): every light sampled at every vertex, mirrors and glass
+followed recursively up to MAXDEPTH (default 5, the reference's "maxdepth" default; the camera ray is depth 0). Also a choice of this command line - the loader keeps
+refusing Integrator "whitted" - and also one call on one device: it combines with none of the options --ao excludes, nor with --ao."""
 import argparse
 import os
 import sys
@@ -185,7 +188,14 @@ def main():
     ap.add_argument("--devices", default=None, metavar="0,1,...", help="with --preview-every / --adaptive: render the frame on these GPUs of this process")
     ap.add_argument("--ao", type=int, default=0, metavar="N", help="render with the ambient-occlusion integrator: N occlusion rays per camera sample")
     ap.add_argument("--ao-distance", type=float, default=float("inf"), metavar="D", help="with --ao: the length of the occlusion rays (default: infinite)")
+    ap.add_argument("--whitted", type=int, nargs="?", const=5, default=None, metavar="MAXDEPTH", help="render with the Whitted integrator, recursion limit MAXDEPTH (default 5)")
     a = ap.parse_args()
+    if a.whitted is not None and a.whitted < 1:
+        raise SystemExit("--whitted MAXDEPTH must be >= 1 (the camera ray is depth 0)")
+    if a.whitted and a.ao:
+        raise SystemExit("--whitted and --ao each replace the file's Integrator: give one of them")
+    if a.whitted and (a.samples or a.preview_every > 0 or a.adaptive is not None or a.features or a.devices or a.camera_model):
+        raise SystemExit("--whitted renders the file's camera in one call: it does not combine with --samples, --preview-every, --adaptive, --features, --devices or --camera-model")
     if a.ao and (a.samples or a.preview_every > 0 or a.adaptive is not None or a.features or a.devices or a.camera_model):
         raise SystemExit("--ao renders the file's camera in one call: it does not combine with --samples, --preview-every, --adaptive, --features, --devices or --camera-model")
     if a.ao_distance != float("inf") and not a.ao:
@@ -312,6 +322,10 @@ def main():
                 write(film)
                 print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
             save_features(frame)
+    elif a.whitted:
+        film, stats = s.render_whitted(a.whitted)
+        write(film)
+        print(f"{out}: Whitted, max depth {a.whitted}, {stats['rays_closest']} li rays and {stats['rays_shadow']} visibility segments from {stats['camera_rays']} camera samples")
     elif a.ao:
         film, stats = s.render_ao(a.ao, a.ao_distance)
         write(film)
