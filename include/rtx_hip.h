@@ -583,6 +583,60 @@ int rt_render_whitted(rt_scene* scene, const rt_camera* camera, const rt_film_de
  * smallest pass of 2^14 paths. */
 int rt_whitted_stack_plan(int32_t max_depth, uint64_t cap, int32_t pass_log2, uint64_t budget_bytes, uint64_t* stack_bytes);
 
+/* The direct-lighting integrator (integrator/directlighting.rs:89-143, integrator/mod.rs:145-318): Whitted's tree walk with estimate_direct at every vertex. li(ray, depth):
+ * on a miss the sum of the lights' le(ray) (infinite lights only), nothing drawn. On a hit compute_scattering_functions(.., allow_multiple_lobes = false) as Whitted; then
+ * isect.le(wo); then, if the scene lists any light, uniform_sample_all_light (RT_DIRECT_ALL) or uniform_sample_one_light(.., None) (RT_DIRECT_ONE); then, if
+ * depth + 1 < max_depth, specular_reflection and specular_transmission exactly as Whitted takes them - each consumes one get_2d() whether or not a lobe matches, in the
+ * order reflection draw, whole reflection subtree, transmission draw, transmission subtree. No ray differentials below depth 0: Whitted's stated divergence.
+ * estimate_direct(light, u_light, u_scattering), flags = ALL & !SPECULAR. Light half: sample_li(u_light); where pdf > 0 and li is not black f = bsdf.f(wo, wi, flags) *
+ * |wi . ns| and, where f is not black and the segment is unoccluded, f li / pdf for a delta light and f li power_heuristic(1, pdf, 1, bsdf.pdf(wo, wi, flags)) / pdf for
+ * any other. BSDF half (non-delta lights only): sample_f(wo, u_scattering, flags); where f |wi . ns| is not black and pdf > 0, light_pdf = light.pdf_li(wi) - zero ends the
+ * estimate -, the ray spawn_ray(wi) is cast as a closest-hit ray and li = hit.le(-wi) ONLY where the hit primitive's area light is this light (an emitter inside an object
+ * instance is in no light list: never), on a miss light.le(ray), else black; the term is f li power_heuristic(1, pdf, 1, light_pdf) / pdf. ns is isect.shading.n AFTER
+ * compute_scattering_functions - a bump map has moved it; Whitted's light terms read it from before.
+ * RT_DIRECT_ALL (mod.rs:145-184): this backend carries no light `samples` parameter (neither rt_light nor the scene-file loader has one), so n_light_samples[j] =
+ * round_count(1) = 1 for every light and an array is sobol_2d(1, spp): one more (0,2) table. preprocess requests A = 2 * max_depth * n_lights of them
+ * (directlighting.rs:70-87); start_pixel fills them from the pixel's keyed stream directly after the 2 * dimensions tables (zerotwosequence.rs:86-102). array_2d_offset
+ * restarts at 0 for every sample and counts up over the sample's vertices in depth-first order, across branches: the v-th vertex of a sample that reaches
+ * uniform_sample_all_light (v = 0, 1, ...) reads light j's u_light from array 2 (v n_lights + j) and u_scattering from the next one, at the sample's index. A sample
+ * whose tree has more than max_depth such vertices finds the arrays exhausted (get_2d_array returns None): from then on each light takes u_light = get_2d(), then
+ * u_scattering = get_2d(). A > RT_DIRECT_MAX_ARRAYS: RT_ERR_UNSUPPORTED (use RT_DIRECT_ONE).
+ * RT_DIRECT_ONE (mod.rs:186-220): s = get_1d(), light = min(n - 1, (s n) as usize), then u_light = get_2d(), u_scattering = get_2d(); the estimate is divided by 1 / n.
+ * Draws: get_2d() number k after the camera sample is rt_render_rays_ao's (table 2D#(2 + k) while 2 + k < dimensions, then two draws of the sample's keyed stream in
+ * (second, first) order); get_1d() number k after the camera sample's time draw is table 1D#(1 + k) while 1 + k < dimensions, then one draw of that same stream; once both
+ * have left the tables they take from the ONE stream in call order (zerotwosequence.rs:158-180). Terms are added in depth-first preorder, within a node Le, then the
+ * lights in list order, light half before BSDF half; no float atomics.
+ * rt_direct_desc: max_depth in [1, RT_WHITTED_MAX_DEPTH]; strategy RT_DIRECT_ALL or RT_DIRECT_ONE; reserved must be 0. (16 bytes, rt_sizeof("rt_direct_desc").)
+ *
+ * rt_render_rays_direct / rt_render_direct: rt_render_rays_whitted's / rt_render_whitted's arguments, records (8 floats, or RT_RAY_DIFF_FLOATS with
+ * RT_FLAG_RAY_DIFFERENTIALS), virtual-film keying, RT_RAYS_MAX, status float, RT_FLAG_FILM_ON_DEVICE, rt_shard, pixel filter, max_sample_luminance and scrubbing.
+ *   info      NULL, or [H][W][n_samples][RT_DIRECT_INFO_WORDS] uint32: li invocations, get_2d() draws after the camera sample, get_1d() draws after it, and the vertices
+ *             that reached uniform_sample_all_light (RT_DIRECT_ALL; 0 under RT_DIRECT_ONE) - above max_depth the sample exhausted its arrays.
+ * rt_stats: rays_closest = li rays, rays_shadow = visibility segments cast, rays_mis = BSDF-sampled rays cast; ms_shade = the vertex kernel plus the array-table kernel
+ * (of it, ms_shade_bin = the array-table kernel alone: no queue is binned in such a call), ms_resolve = k_direct_probe; launches_trace_path, launches_shade (vertex kernel), launches_trace_shadow, launches_trace_mis (one k_direct_probe each) as issued.
+ * RT_ERR_INVALID with a message before any device work: what the Whitted entry points refuse; a NULL direct, max_depth < 1, a strategy outside {0, 1}, a non-zero reserved
+ * word; RT_FLAG_REF_STREAM. max_depth > RT_WHITTED_MAX_DEPTH: RT_ERR_UNSUPPORTED. Single device. */
+#define RT_DIRECT_ALL 0
+#define RT_DIRECT_ONE 1
+#define RT_DIRECT_MAX_ARRAYS 1024 /* 2 * max_depth * n_lights under RT_DIRECT_ALL; above it RT_ERR_UNSUPPORTED, the message names strategy "one" */
+#define RT_DIRECT_INFO_WORDS 4
+#define RT_DIRECT_TABLE_BUDGET (1ull << 30) /* bytes of array tables per batch of pixels: above it the batch is halved (RTX_DIRECT_TABLE_BUDGET), no bit of the film changes */
+#define RT_DIRECT_CHUNK_MIN 64              /* ... never below one workgroup's pixels */
+struct rt_direct_desc { int32_t max_depth; int32_t strategy; int32_t reserved[2]; };
+typedef struct rt_direct_desc rt_direct_desc;
+int rt_render_rays_direct(rt_scene* scene, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples,
+                          const rt_sampler_desc* sampler, const rt_direct_desc* direct, uint32_t flags, void* stream,
+                          float* radiance, uint32_t* info /* may be NULL */, rt_stats* stats /* may be NULL */);
+int rt_render_direct(rt_scene* scene, const rt_camera* camera, const rt_film_desc* film, const rt_sampler_desc* sampler, const rt_direct_desc* direct,
+                     const rt_shard* shard /* may be NULL */, uint32_t flags, void* stream, float* film_xyzw, rt_stats* stats /* may be NULL */);
+/* How a direct-lighting call sizes its array tables, on numbers alone (no device). n_arrays = 2 * max_depth * n_lights under RT_DIRECT_ALL, 0 under RT_DIRECT_ONE;
+ * *table_bytes_per_pixel = n_arrays * (spp * 2 + 8) with spp rounded up to a power of two (a u16 permutation entry per sample and two u32 scrambles per array);
+ * *chunk_pixels = the pixels of a batch: `pixels` halved while its tables exceed budget_bytes (RT_DIRECT_TABLE_BUDGET in a call), never below RT_DIRECT_CHUNK_MIN (or
+ * `pixels`, if that is less); *stack_bytes = rt_whitted_stack_plan's for a pass of `cap` paths. Any output may be NULL. Returns RT_OK, RT_ERR_INVALID for a max_depth,
+ * strategy, n_lights or spp outside its range, RT_ERR_UNSUPPORTED for n_arrays > RT_DIRECT_MAX_ARRAYS. */
+int rt_direct_plan(int32_t max_depth, int32_t n_lights, int32_t strategy, int32_t spp, uint64_t pixels, uint64_t cap, uint64_t budget_bytes,
+                   uint64_t* table_bytes_per_pixel, uint64_t* chunk_pixels, uint64_t* stack_bytes);
+
 /* The perspective camera's rays, as a camera frame generates them - what k_raygen and bounce 0's shade kernels compute - for samples [sample0, sample0 + n_samples) of every
  * pixel of the film's sample bounds (W x H pixels, pixel_index = row * W + column): for a caller who bends them (lens distortion, a stereo offset, a rolling shutter) and
  * feeds them to rt_render_rays or a ray frame, and as the exact source of the camera's differentials.
@@ -798,7 +852,8 @@ enum { RT_QUERY_LDS_RESIDENT = 0, RT_QUERY_LDS_NODES_TESTED = 1 /* LDS-resident 
        RT_QUERY_LDS_SPEC = 7 /* the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC, read by rt_scene_create; 0: leaf holders wait,
                                 1: they keep walking up to the next leaf), 0 for every other scene */,
        RT_QUERY_WHITTED_LAUNCHED = 8 /* the vertex kernel the scene's last rt_render_whitted / rt_render_rays_whitted launched: 1 k_whitted_vertex<false> (plain triangles),
-                                        2 k_whitted_vertex<true> (quadrics, object instances or masked emitters), 0 before the first call */ };
+                                        2 k_whitted_vertex<true> (quadrics, object instances or masked emitters), 0 before the first call */,
+       RT_QUERY_DIRECT_LAUNCHED = 9 /* the same of k_direct_vertex and the scene's last rt_render_direct / rt_render_rays_direct */ };
 int rt_scene_query(rt_scene* scene, int32_t what);
 /* The tables rt_scene_create hands the stackless LDS walks of a small (<= 256 nodes, <= 128 primitives) or mid-size (<= 2816 / 1408) scene, computed on the host alone - no
  * device is touched (tests, offline inspection). link_kept / link_full: 9 * n_nodes + 9 words each (rows 0 - 7: closest hit by direction octant, their 8 start nodes,

@@ -178,6 +178,15 @@ int rtxh_render_rays_whitted(rtxh_scene*, const rtxh_render_params*, const float
 /* The frame rtxh_render would render, with the Whitted integrator (rt_render_whitted in rtx_hip.h): camera, film, sampler, rank / world_size and flags as for
  * rtxh_render; the path integrator's parameters and the pixel bounds are not read. */
 int rtxh_render_whitted(rtxh_scene*, const rtxh_render_params*, int32_t max_depth, void* hip_stream, float* film_xyzw, rt_stats* stats);
+/* The direct-lighting integrator along the caller's rays (rt_render_rays_direct in rtx_hip.h): rays, radiance and the parameters read as for rtxh_render_rays_whitted;
+ * strategy RT_DIRECT_ALL or RT_DIRECT_ONE; info NULL or height x width x n_samples x RT_DIRECT_INFO_WORDS uint32 (li invocations, get_2d() draws, get_1d() draws, vertices
+ * that reached uniform_sample_all_light). What rt_render_rays_direct refuses - the count of sample arrays of the scene's listed lights included - is refused before the
+ * scene is uploaded for it, identically on a machine without a device. */
+int rtxh_render_rays_direct(rtxh_scene*, const rtxh_render_params*, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, int32_t max_depth,
+                            int32_t strategy, void* hip_stream, float* radiance, uint32_t* info /* may be NULL */, rt_stats* stats);
+/* The frame rtxh_render would render, with the direct-lighting integrator (rt_render_direct in rtx_hip.h): camera, film, sampler, rank / world_size and flags as for
+ * rtxh_render; the path integrator's parameters and the pixel bounds are not read. */
+int rtxh_render_direct(rtxh_scene*, const rtxh_render_params*, int32_t max_depth, int32_t strategy, void* hip_stream, float* film_xyzw, rt_stats* stats);
 /* The same frame in steps (rt_frame_* in rtx_hip.h): camera, film and pixel bounds are set up as for rtxh_render, rank / world_size and the flags of the
  * parameters are the frame's. table_budget_bytes: 0 = the default budget for resident sampler tables. The frame must be ended before its scene is freed;
  * rtxh_frame_end(NULL) is a no-op. what / scale / flags / out of rtxh_frame_read and what / value of rtxh_frame_query as in rt_frame_read / rt_frame_query. */

@@ -29,6 +29,16 @@ static inline unsigned long long whitted_stack_bytes(int max_depth, unsigned lon
 static inline bool whitted_pass_too_large(int max_depth, unsigned long long cap, int pass_log2, unsigned long long budget) {
   return whitted_stack_bytes(max_depth, cap) > budget && pass_log2 > 14;
 }
+// The direct-lighting integrator's array tables (rtx_direct_launch.h): 2 * max_depth * n_lights (0,2) tables per pixel under strategy "all" (0), none under "one";
+// a table is spp u16 permutation entries and two u32 scrambles.
+static inline unsigned direct_n_arrays(int max_depth, int n_lights, int strategy) { return strategy == 0 ? 2u * (unsigned)max_depth * (unsigned)n_lights : 0u; }
+static inline unsigned long long direct_table_bytes_per_pixel(unsigned n_arrays, unsigned spp) { return (unsigned long long)n_arrays * ((unsigned long long)spp * 2ull + 8ull); }
+// The pixels of a batch: `pixels` halved while the batch's array tables exceed `budget` bytes, never below one workgroup's pixels (64).
+static inline unsigned long long direct_chunk_pixels(unsigned n_arrays, unsigned spp, unsigned long long pixels, unsigned long long budget) {
+  unsigned long long c = pixels;
+  while (c > 64ull && c * direct_table_bytes_per_pixel(n_arrays, spp) > budget) c = std::max<unsigned long long>(64ull, (c + 1ull) / 2ull);
+  return c;
+}
 struct FrameBatch { unsigned long long first, pixels; unsigned pass_samples; };  // owned pixels [first, first + pixels); a short batch: more samples per pass, same paths
 
 static int frame_plan_cut(const FramePlanIn& in, FramePlan& p, const char*& why) {

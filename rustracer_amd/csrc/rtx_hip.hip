@@ -24,6 +24,7 @@
 #include "rtx_light_eval_launch.h"
 #include "rtx_ao_launch.h"
 #include "rtx_whitted_launch.h"
+#include "rtx_direct_launch.h"
 
 using namespace rtx;
 #include "rtx_scene_plan.h"
@@ -111,6 +112,9 @@ struct rt_scene {
   DevBuf ao_rays;                  // rt_render_rays_ao with a host ao_rays: [pixel][sample][occlusion sample] 32 B
   DevBuf whitted_stack, whitted_info;  // the Whitted integrator: the pending vertices of a pass, [plane][level][path] 16 B (WhittedArgs::stack); rt_render_rays_whitted with a host info: [pixel][sample] 8 B
   unsigned* whitted_pinned = nullptr;  // ... the shard counts of a step's queue of continuing samples, read back in pinned memory (run_whitted)
+  DevBuf direct_scrambles, direct_perms, direct_info;  // the direct-lighting integrator: a batch's array tables (DirectArgs::arr: scrambles [2 a][pixel], perms [a][sample][pixel]); rt_render_rays_direct with a host info: [pixel][sample] 16 B
+  std::vector<unsigned char> light_delta;  // ... per listed light: is it a delta light (run_direct: such a light has no probe launch)
+  int direct_launched = 0;             // ... 1 + GENERAL of the k_direct_vertex instantiation the scene's last direct-lighting call launched (RT_QUERY_DIRECT_LAUNCHED)
   int whitted_launched = 0;            // ... 1 + GENERAL of the k_whitted_vertex instantiation the scene's last Whitted call launched (RT_QUERY_WHITTED_LAUNCHED)
   DevBuf samples_feat;             // rt_render_sample_features with a host output: [window pixel][sample] RT_FEATURE_FLOATS floats
   DevBuf feat;                     // a feature frame's step: [path id] (normal | depth), then [path id] (albedo | hit) (FeatureOut::nd / ah)
@@ -141,7 +145,7 @@ extern "C" int rt_sizeof(const char* name) {
   if (!name) return -1;
 #define RT_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);
   RT_SZ(rt_bvh_node) RT_SZ(rt_tri_meta) RT_SZ(rt_sphere) RT_SZ(rt_instance) RT_SZ(rt_texture) RT_SZ(rt_image) RT_SZ(rt_material) RT_SZ(rt_light) RT_SZ(rt_scene_desc)
-  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats) RT_SZ(rt_ao_desc) RT_SZ(rt_whitted_desc)
+  RT_SZ(rt_camera) RT_SZ(rt_film_desc) RT_SZ(rt_sampler_desc) RT_SZ(rt_path_desc) RT_SZ(rt_shard) RT_SZ(rt_stats) RT_SZ(rt_ao_desc) RT_SZ(rt_whitted_desc) RT_SZ(rt_direct_desc)
 #undef RT_SZ
   return -1;
 }
@@ -170,6 +174,7 @@ static void fill_ewa_lut() {
   rtx_ref_set_ewa_lut(lut);    // ... and the reference-stream kernel's
   rtx_light_eval_set_ewa_lut(lut);  // ... and rt_light_eval's
   rtx_whitted_set_ewa_lut(lut);     // ... and the Whitted integrator's
+  rtx_direct_set_ewa_lut(lut);      // ... and the direct-lighting integrator's
 }
 
 #include "rtx_bvh_build.h"
@@ -389,6 +394,7 @@ extern "C" int rt_scene_query(rt_scene* s, int32_t what) {
   if (what == RT_QUERY_NEEDS_DIFFERENTIALS) return s->d.needs_differentials ? 1 : 0;
   if (what == RT_QUERY_LDS_SPEC) return s->lds_spec;
   if (what == RT_QUERY_WHITTED_LAUNCHED) return s->whitted_launched;
+  if (what == RT_QUERY_DIRECT_LAUNCHED) return s->direct_launched;
   return fail(RT_ERR_INVALID, "unknown rt_scene_query item");
 }
 
@@ -553,6 +559,8 @@ static int scene_from_plan(const RtScenePlan& p, const rt_scene_desc* desc, int 
   s->device = dev;
   hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, dev) == hipSuccess) s->n_cu = prop.multiProcessorCount;
   s->n_nodes = desc->n_nodes; s->n_tris = desc->n_tris; s->n_lights = (int)desc->n_lights; s->n_materials = desc->n_materials;
+  s->light_delta.resize(desc->n_lights);
+  for (uint32_t k = 0; k < desc->n_lights; ++k) s->light_delta[k] = desc->lights[k].kind == RT_LIGHT_POINT || desc->lights[k].kind == RT_LIGHT_DISTANT;
   s->small = p.small; s->mid = p.mid; s->general_prims = p.general_prims; s->obj_general = p.obj_general; s->has_masks = p.has_masks; s->has_spheres = p.has_spheres;
   s->has_instances = p.has_instances; s->masked_emitters = p.masked_emitters; s->lambert_only = p.lambert_only; s->lambert_materials = p.lambert_materials;
   s->lean_shade = p.lean_shade; s->lean_qlights = p.lean_qlights; s->lds_records = p.lds_records; s->lds_records_q = p.lds_records_q; s->lds_tables = p.lds_tables;
@@ -1178,7 +1186,9 @@ enum FrameKind {
   FRAME_AO,               // rt_render_ao: rt_render's film of the ambient-occlusion integrator - bounce 0's trace, then run_ao in place of the shade launches
   FRAME_RAYS_AO,          // rt_render_rays_ao: that integrator (and Normal::li) along the caller's rays, per sample
   FRAME_WHITTED,          // rt_render_whitted: rt_render's film of the Whitted integrator - raygen, then run_whitted's depth-first walk in place of the bounce loop
-  FRAME_RAYS_WHITTED      // rt_render_rays_whitted: Whitted::li along the caller's rays, per sample
+  FRAME_RAYS_WHITTED,     // rt_render_rays_whitted: Whitted::li along the caller's rays, per sample
+  FRAME_DIRECT,           // rt_render_direct: rt_render's film of the direct-lighting integrator - raygen, then run_direct's walk in place of the bounce loop
+  FRAME_RAYS_DIRECT       // rt_render_rays_direct: DirectLightingIntegrator::li along the caller's rays, per sample
 };
 struct FrameJob {
   FrameKind kind = FRAME_FILM;
@@ -1195,17 +1205,21 @@ struct FrameJob {
   rt_frame* frame = nullptr; unsigned step_end = 0;         // the steps
   const unsigned char* active_mask = nullptr; bool have_lock = false;
   const rt_ao_desc* ao = nullptr; float* ao_rays = nullptr;  // FRAME_AO, FRAME_RAYS_AO (the occlusion rays handed out, or NULL)
+  const rt_direct_desc* direct = nullptr;  // FRAME_DIRECT, FRAME_RAYS_DIRECT: `whitted` then holds its max_depth (the walk, the stack and the info hand-out are Whitted's)
   const rt_whitted_desc* whitted = nullptr; uint32_t* whitted_info = nullptr;  // FRAME_WHITTED, FRAME_RAYS_WHITTED (the node and draw counts handed out, or NULL)
 
   bool is_step() const { return kind == FRAME_STEP || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP; }
-  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP || kind == FRAME_RAYS_AO || kind == FRAME_RAYS_WHITTED; }  // bounce 0 comes from ray records, not from the camera
+  bool from_rays() const { return kind == FRAME_RAYS || kind == FRAME_RAY_STEP || kind == FRAME_MODEL_STEP || kind == FRAME_RAYS_AO || kind == FRAME_RAYS_WHITTED || kind == FRAME_RAYS_DIRECT; }  // bounce 0 comes from ray records, not from the camera
   bool traces_paths() const { return kind != FRAME_CAMERA_RAYS; }
   bool masked() const { return active_mask != nullptr; }
   bool is_ao() const { return kind == FRAME_AO || kind == FRAME_RAYS_AO; }  // no shade launches, no light distribution: run_ao
-  bool is_whitted() const { return kind == FRAME_WHITTED || kind == FRAME_RAYS_WHITTED; }  // no shade launches, no light distribution: run_whitted
+  bool is_direct() const { return kind == FRAME_DIRECT || kind == FRAME_RAYS_DIRECT; }  // the same walk with estimate_direct at every vertex: run_direct
+  bool is_whitted() const { return kind == FRAME_WHITTED || kind == FRAME_RAYS_WHITTED || is_direct(); }  // no shade launches, no light distribution: run_whitted / run_direct
+  bool direct_all() const { return is_direct() && direct->strategy == RT_DIRECT_ALL; }  // ... that reads array tables
+  unsigned info_words() const { return is_direct() ? (unsigned)RT_DIRECT_INFO_WORDS : (unsigned)RT_WHITTED_INFO_WORDS; }
   bool own_integrator() const { return is_ao() || is_whitted(); }  // the pass after ray generation is the integrator's own: fresh records written, no split shade kernels
-  bool rays_radiance() const { return kind == FRAME_RAYS || kind == FRAME_RAYS_WHITTED; }  // per-sample radiance along the caller's rays: k_raygen_rays in, k_sample_store out
-  bool to_film() const { return kind == FRAME_FILM || kind == FRAME_AO || kind == FRAME_WHITTED; }  // the filtered film is the call's output
+  bool rays_radiance() const { return kind == FRAME_RAYS || kind == FRAME_RAYS_WHITTED || kind == FRAME_RAYS_DIRECT; }  // per-sample radiance along the caller's rays: k_raygen_rays in, k_sample_store out
+  bool to_film() const { return kind == FRAME_FILM || kind == FRAME_AO || kind == FRAME_WHITTED || kind == FRAME_DIRECT; }  // the filtered film is the call's output
   bool owns_film() const { return to_film() || kind == FRAME_SAMPLES; }  // the scene's film sums, own sums and filter table are reserved (a step has the frame's)
   bool stages_to_host() const { return !(flags & RT_FLAG_FILM_ON_DEVICE) && !is_step(); }  // the output goes through a device buffer of the scene's and is copied out
   bool frame_features() const { return is_step() && frame->features; }  // RT_FLAG_FRAME_FEATURES: the pass's features are summed into the frame's plane
@@ -1227,6 +1241,7 @@ struct FrameRun {
   ShadeRoute route; unsigned n_bins, pgrid; size_t counter_words, bin_stride; int lds_shade;
   FramePlan plan; std::vector<FrameBatch> batches;
   double ms_ao = 0.0; float4* d_ao_rays = nullptr;  // the time of run_ao's / run_whitted's own kernels (ms_shade of such a call); where the occlusion rays go on the device
+  unsigned direct_arrays = 0;  // array tables per pixel of a direct-lighting call under RT_DIRECT_ALL (2 * max_depth * n_lights), else 0
   uint2* d_whitted_info = nullptr; unsigned whitted_levels = 0;  // where the node and draw counts go on the device; levels of the pending stack (max_depth - 1)
   // the workspace and the outputs, bound
   float4 *d_out, *d_samples_rad, *d_cam_rays; float2 *d_samples_pf, *d_cam_pf; FeatureOut fo;
@@ -1394,6 +1409,13 @@ static int reserve_workspace(FrameRun& r) {
   FramePlanIn in{r.owned_pixels, r.spp, r.dims, tp_log2, bp_log2, lead_env ? lead_env[0] == '1' : r.spp == 1024u, fixed, fixed ? fr->batch_pixels : 0ull, fixed ? fr->lead_pixels : 0ull, (unsigned)s->n_cu};
   const unsigned long long table_bytes_per_pixel = 2ull * r.dims * r.spp * 2ull, nws = r.n_window_samples;
   const unsigned dims = r.dims;
+  if (job.direct_all()) {  // the batch is cut so that its array tables stay within the budget: the sampler tables are keyed by pixel, so the cut changes no bit
+    r.direct_arrays = direct_n_arrays(job.direct->max_depth, s->n_lights, RT_DIRECT_ALL);
+    const char* be = getenv("RTX_DIRECT_TABLE_BUDGET");  // (test knob, read per call: the budget in bytes)
+    const unsigned long long whole = std::max<unsigned long long>(1, std::min<unsigned long long>(r.owned_pixels, 1ull << bp_log2));
+    const unsigned long long chunk = direct_chunk_pixels(r.direct_arrays, r.spp, whole, be ? strtoull(be, nullptr, 10) : (unsigned long long)RT_DIRECT_TABLE_BUDGET);
+    if (chunk < whole) { in.fixed = true; in.fixed_batch_pixels = chunk; in.fixed_lead_pixels = 0; }
+  }
   for (int shrink = 0;; ++shrink) {
     in.pass_log2 = tp_log2 - shrink;
     const char* why = nullptr;
@@ -1419,7 +1441,8 @@ static int reserve_workspace(FrameRun& r) {
       const char* be = getenv("RTX_WHITTED_STACK_BUDGET");  // (test knob, read per call: the budget in bytes)
       if (whitted_pass_too_large(job.whitted->max_depth, cap, in.pass_log2, be ? strtoull(be, nullptr, 10) : (unsigned long long)RT_WHITTED_STACK_BUDGET)) continue;
       want.push_back({&s->whitted_stack, (size_t)stack_bytes});
-      if (job.whitted_info && job.stages_to_host()) want.push_back({&s->whitted_info, (size_t)nws * 8});
+      if (job.whitted_info && job.stages_to_host()) want.push_back({job.is_direct() ? &s->direct_info : &s->whitted_info, (size_t)nws * 4 * job.info_words()});
+      if (r.direct_arrays) { want.push_back({&s->direct_scrambles, (size_t)batch_pixels * 2 * r.direct_arrays * 4}); want.push_back({&s->direct_perms, (size_t)batch_pixels * r.direct_arrays * r.spp * 2}); }
     }
     if (job.stages_to_host()) {
       if (job.kind == FRAME_SAMPLE_FEATURES) want.push_back({&s->samples_feat, (size_t)nws * RT_FEATURE_FLOATS * 4});
@@ -1472,8 +1495,8 @@ static int bind_outputs(FrameRun& r) {
   if (job.is_whitted()) {
     if (!s->whitted_pinned) HIP_TRY(hipHostMalloc((void**)&s->whitted_pinned, (size_t)RT_QSHARDS * RT_CNT_STRIDE * 4, hipHostMallocDefault));
     if (job.whitted_info) {  // zeros for a skipped ray
-      r.d_whitted_info = on_device ? (uint2*)job.whitted_info : s->whitted_info.as<uint2>();
-      HIP_TRY(hipMemsetAsync(r.d_whitted_info, 0, (size_t)r.n_window_samples * 8, r.stream));
+      r.d_whitted_info = on_device ? (uint2*)job.whitted_info : (job.is_direct() ? s->direct_info.as<uint2>() : s->whitted_info.as<uint2>());
+      HIP_TRY(hipMemsetAsync(r.d_whitted_info, 0, (size_t)r.n_window_samples * 4 * job.info_words(), r.stream));
     }
   }
   if (job.to_film()) {  // (no kernel of a per-sample kind reads the filter table or the film sums; a progressive frame keeps its own)
@@ -1744,6 +1767,79 @@ static int run_whitted(FrameRun& r, int buf) {
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }
+// The direct-lighting integrator's pass after ray generation (DirectLightingIntegrator::li, integrator/directlighting.rs:89-143): run_whitted's walk - a step per node,
+// the closest-hit launch, the rounds, the two alternating counter blocks, the read-back of the active count - with k_direct_vertex (rtx_direct_launch.h) in the rounds.
+// Under RT_DIRECT_ALL round j is light j of the list, under RT_DIRECT_ONE the one round is the light each sample picks. After a light round: the any-hit launch over the
+// round's shadow records (the light half), then - unless every light the round can name is a delta light - the closest-hit launch over its probe records (the BSDF-sampled
+// rays: launch_trace<false>, counted as MIS rays) and k_direct_probe, which adds term * le where a probe ends on its own light or leaves the scene toward an infinite one.
+// Both are done before the next round starts, so a sample's terms are added in list order, light half before BSDF half.
+static int run_direct(FrameRun& r, int buf) {
+  const FrameJob& job = r.job; rt_scene* const s = r.s; hipStream_t stream = r.stream; KTimer& tm = r.tm; rt_stats& stats = r.stats; PassState& ps = r.ps;
+  const unsigned pgrid = r.pgrid; const bool count = r.count;
+  unsigned* const cb = s->counters.as<unsigned>(); unsigned long long* const dstats = s->stats.as<unsigned long long>();
+  const size_t block_words = (size_t)RT_NQ * RT_QSHARDS * RT_CNT_STRIDE;
+  ps.fresh = 0; ps.skip_dead_tail = 0;
+  r.io_path.hit_mask = nullptr;
+  DirectArgs a{};
+  const bool one = job.direct->strategy == RT_DIRECT_ONE;
+  a.n_lights = s->d.n_lights; a.max_depth = job.direct->max_depth; a.strategy = job.direct->strategy;
+  a.n_rounds = one ? 1u : (unsigned)std::max(a.n_lights, 1);
+  a.wst = (uint4*)sraw(ps.mi.c); a.stack = s->whitted_stack.as<float4>(); a.levels = r.whitted_levels; a.stack_cap = (size_t)r.plan.cap;
+  a.arr = Tables{s->direct_scrambles.as<unsigned>(), s->direct_perms.as<unsigned short>(), r.spp, 0u, ps.n_pixels}; a.n_arrays = r.direct_arrays;
+  if (r.ray_diff) a.rdiff = RayDiffSrc{r.d_rays, r.src.sample0, r.src.n_samples, r.rec_floats / 4u};
+  const bool general = s->has_spheres || s->has_instances || s->masked_emitters;
+  s->direct_launched = general ? 2 : 1;
+  bool any_area = false;
+  for (int k = 0; k < a.n_lights; ++k) any_area = any_area || !s->light_delta[(size_t)k];
+  const unsigned max_steps = (1u << a.max_depth) - 1u;  // the nodes of a full binary tree of max_depth levels
+  for (unsigned step = 0; step < max_steps; ++step) {
+    a.step = step;
+    std::swap(ps.in, ps.out);  // what the previous stage appended is this step's input
+    ps.cnt_in = step == 0 ? (r.all_in_bounds ? nullptr : cb) : cb + (size_t)(1 + ((step - 1) & 1u)) * block_words;
+    ps.cnt_out = cb + (size_t)(1 + (step & 1u)) * block_words;
+    r.io_path.ray_o = ps.in.o; r.io_path.ray_d = ps.in.d;
+    tm.begin(&stats.ms_trace_closest);
+    launch_trace<false>(s, count, r.io_path, ps.cnt_in, ps.cnt_in, ps.shard_cap, ps.cap, dstats, ST_RAYS_CLOSEST, ST_NODES_CLOSEST, ST_TRIS_CLOSEST, stream);
+    tm.end();
+    stats.launches_trace_closest += 1; stats.launches_trace_path += 1;
+    if (step == 0 && r.build_tables) for (int g = 1; g < 3; ++g) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][g], 0));  // 2-D tables 2 ..., 1-D tables 1 ...: the first draws
+    for (unsigned round = 0; round < a.n_rounds; ++round) {
+      a.round = round;
+      HIP_TRY(hipMemsetAsync(ps.cnt_out, 0, block_words * 4, stream));  // (the queue of continuing samples is appended to by the last round alone)
+      tm.begin(&r.ms_ao);
+      rtx_launch_direct_vertex(general, pgrid, stream, *r.dsc, r.fp, ps, a);
+      tm.end();
+      stats.launches_shade += 1;
+      if ((int)round >= a.n_lights) continue;
+      tm.begin(&stats.ms_trace_any);
+      launch_trace<true>(s, count, r.io_shadow, ps.q_shadow, ps.cnt_out + RT_QSHARDS * RT_CNT_STRIDE, ps.shard_cap, 0, dstats, ST_RAYS_SHADOW, ST_NODES_SHADOW, ST_TRIS_SHADOW, stream);
+      tm.end();
+      stats.launches_trace_shadow += 1;
+      if (one ? !any_area : s->light_delta[round] != 0) continue;  // a delta light has no BSDF half
+      tm.begin(&stats.ms_trace_mis);
+      launch_trace<false>(s, count, r.io_mis, ps.q_mis, ps.cnt_out + 2 * RT_QSHARDS * RT_CNT_STRIDE, ps.shard_cap, 0, dstats, ST_RAYS_MIS, ST_NODES_MIS, ST_TRIS_MIS, stream);
+      tm.end();
+      tm.begin(&stats.ms_resolve);
+      rtx_launch_direct_probe(s->has_spheres || s->has_instances, pgrid, stream, *r.dsc, ps);
+      tm.end();
+      stats.launches_trace_closest += 1; stats.launches_trace_mis += 1;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->whitted_pinned, ps.cnt_out, (size_t)RT_QSHARDS * RT_CNT_STRIDE * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned active = 0;
+    for (int k = 0; k < RT_QSHARDS; ++k) active += s->whitted_pinned[k * RT_CNT_STRIDE];
+    if (active == 0u) break;
+  }
+  if (r.d_whitted_info) {  // k_sample_store's indexing: the call's samples per pixel as the row length, its first sample as sample 0
+    PassState po = ps; po.spp = r.src.n_samples; po.s0 = ps.s0 - r.src.sample0;
+    tm.begin(&r.ms_ao);
+    rtx_launch_direct_info(pgrid, stream, r.fp, po, a, r.wx0, r.wy0, r.wx1 - r.wx0, (uint4*)r.d_whitted_info);
+    tm.end();
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
 // tiles of 2^(8 - ts) pixels x 2^ts samples of k_raygen_rays / k_raygen_rays_film: ts = log2(min(16, the pass's samples rounded up))
 static unsigned ray_tile_samples_log2(unsigned n_samples) { unsigned ts_log2 = 0; while (ts_log2 < 4u && (1u << ts_log2) < n_samples) ++ts_log2; return ts_log2; }
 // One pass - samples [s0, s0 + n_samples) of the batch's pixels: ray generation by kind, the bounces, and the pass's film or store kernel by kind
@@ -1789,7 +1885,8 @@ static int run_pass(FrameRun& r, int buf, unsigned s0, unsigned n_samples, unsig
   else hipLaunchKernelGGL(k_raygen, dim3(pgrid), dim3(256), 0, stream, fp, ps);
   tm.end();
   if (job.is_ao()) { const int rc = run_ao(r, buf); if (rc != RT_OK) return rc; }
-  if (job.is_whitted()) { const int rc = run_whitted(r, buf); if (rc != RT_OK) return rc; }
+  if (job.is_direct()) { const int rc = run_direct(r, buf); if (rc != RT_OK) return rc; }
+  else if (job.is_whitted()) { const int rc = run_whitted(r, buf); if (rc != RT_OK) return rc; }
   const int last_bounce = job.own_integrator() ? -1 : (job.kind == FRAME_SAMPLE_FEATURES ? 0 : fp.max_depth);
   for (int bounce = 0; bounce <= last_bounce; ++bounce) {
     const int rc = run_bounce(r, buf, bounce, fresh_planes, skip_dead_tail);
@@ -1857,6 +1954,12 @@ static int run_batches(FrameRun& r) {
       if (batch_no >= 1 && !resident) HIP_TRY(hipStreamWaitEvent(aux, s->ev_batch_done[buf ^ 1], 0));
       launch_tables(batch_no + 1, buf ^ 1);
     }
+    if (r.direct_arrays) {  // the batch's array tables (RT_DIRECT_ALL), in stream order behind the previous batch's passes: one buffer; part of ms_shade as ms_shade_bin
+      r.tm.begin(&r.stats.ms_shade_bin);
+      const hipError_t e = rtx_launch_sampler_array_tables(stream, r.fp, (unsigned)b.pixels, r.spp, dims, r.direct_arrays, s->direct_scrambles.as<unsigned>(), s->direct_perms.as<unsigned short>());
+      r.tm.end();
+      HIP_TRY(e);
+    }
     if (tables_rc != RT_OK) { (void)hipDeviceSynchronize(); return tables_rc; }
     if (build_tables) HIP_TRY(hipStreamWaitEvent(stream, s->ev_tables[buf][0], 0));  // the tables the camera samples read; the others are waited for where they are first read
     for (unsigned s0 = r.s_begin; s0 < r.s_end; s0 += b.pass_samples) {
@@ -1895,7 +1998,7 @@ static int finish_frame(FrameRun& r) {
     HIP_TRY(hipMemcpyAsync(job.samples_rad, r.d_samples_rad, nws * 16, hipMemcpyDeviceToHost, stream));
     if (job.samples_pf) HIP_TRY(hipMemcpyAsync(job.samples_pf, r.d_samples_pf, nws * 8, hipMemcpyDeviceToHost, stream));
     if (job.ao_rays) HIP_TRY(hipMemcpyAsync(job.ao_rays, r.d_ao_rays, nws * (size_t)job.ao->n_samples * 32, hipMemcpyDeviceToHost, stream));
-    if (job.whitted_info) HIP_TRY(hipMemcpyAsync(job.whitted_info, r.d_whitted_info, nws * 8, hipMemcpyDeviceToHost, stream));
+    if (job.whitted_info) HIP_TRY(hipMemcpyAsync(job.whitted_info, r.d_whitted_info, nws * 4 * job.info_words(), hipMemcpyDeviceToHost, stream));
   }
   HIP_TRY(hipStreamSynchronize(stream));
   r.tm.collect();
@@ -2121,6 +2224,69 @@ extern "C" int rt_render_whitted(rt_scene* s, const rt_camera* cam, const rt_fil
   const rt_path_desc p = whitted_path_desc(*film);
   FrameJob job = frame_job(FRAME_WHITTED, s, cam, film, smp, &p, flags, stream_);
   job.shard = shard; job.film_xyzw = film_xyzw; job.whitted = whitted; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// What a direct-lighting call's tables and stack take, on numbers alone (rtx_frame_plan.h)
+static int direct_numbers_check(const std::string& n, int32_t max_depth, int32_t strategy, int64_t n_lights) {
+  if (max_depth < 1) return fail(RT_ERR_INVALID, n + ": direct->max_depth must be >= 1 (the camera ray is depth 0)");
+  if (strategy != RT_DIRECT_ALL && strategy != RT_DIRECT_ONE) return fail(RT_ERR_INVALID, n + ": direct->strategy must be RT_DIRECT_ALL (0) or RT_DIRECT_ONE (1)");
+  if (max_depth > RT_WHITTED_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, n + ": direct->max_depth > RT_WHITTED_MAX_DEPTH (16)");
+  if (n_lights < 0) return fail(RT_ERR_INVALID, n + ": n_lights must be >= 0");
+  if (strategy == RT_DIRECT_ALL && 2ll * max_depth * n_lights > (long long)RT_DIRECT_MAX_ARRAYS)
+    return fail(RT_ERR_UNSUPPORTED, n + ": strategy \"all\" needs 2 * max_depth * n_lights = " + std::to_string(2ll * max_depth * n_lights) +
+                " sample arrays per pixel, more than RT_DIRECT_MAX_ARRAYS (1024): use strategy \"one\" (RT_DIRECT_ONE)");
+  return RT_OK;
+}
+extern "C" int rt_direct_plan(int32_t max_depth, int32_t n_lights, int32_t strategy, int32_t spp, uint64_t pixels, uint64_t cap, uint64_t budget_bytes,
+                              uint64_t* table_bytes_per_pixel, uint64_t* chunk_pixels, uint64_t* stack_bytes) {
+  const int rc = direct_numbers_check("rt_direct_plan", max_depth, strategy, n_lights);
+  if (rc != RT_OK) return rc;
+  if (spp < 1 || spp > 16384) return fail(RT_ERR_INVALID, "rt_direct_plan: spp must lie in [1, 16384]");
+  const unsigned spp2 = next_pow2((unsigned)spp), na = direct_n_arrays(max_depth, n_lights, strategy);
+  if (table_bytes_per_pixel) *table_bytes_per_pixel = direct_table_bytes_per_pixel(na, spp2);
+  if (chunk_pixels) *chunk_pixels = direct_chunk_pixels(na, spp2, pixels, budget_bytes);
+  if (stack_bytes) *stack_bytes = whitted_stack_bytes(max_depth, cap);
+  return RT_OK;
+}
+// What both direct-lighting entry points refuse of their descriptor (the scene's light count is read, nothing of the device)
+static int direct_desc_check(const char* who, const rt_direct_desc* d) {
+  const std::string n(who);
+  if (d->reserved[0] != 0 || d->reserved[1] != 0) return fail(RT_ERR_INVALID, n + ": direct->reserved must be 0");
+  return direct_numbers_check(n, d->max_depth, d->strategy, 0);
+}
+// DirectLightingIntegrator::li along the caller's rays, over the virtual film of the batch.
+extern "C" int rt_render_rays_direct(rt_scene* s, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, const rt_sampler_desc* smp,
+                                     const rt_direct_desc* direct, uint32_t flags, void* stream_, float* radiance, uint32_t* info, rt_stats* stats_out) {
+  // every refusal of the arguments comes before any device work (and before the scene is looked at)
+  if (!s || !rays || !smp || !direct || !radiance) return fail(RT_ERR_INVALID, "rt_render_rays_direct: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_rays_direct: the reference-stream frame has no per-sample output");
+  if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rt_render_rays_direct: width, height and n_samples must be positive");
+  int rc = sample_range_check("rt_render_rays_direct", smp, sample0, n_samples, (unsigned long long)width, (unsigned long long)height, "must lie inside");
+  if (rc != RT_OK) return rc;
+  if ((rc = direct_desc_check("rt_render_rays_direct", direct)) != RT_OK) return rc;
+  if ((rc = direct_numbers_check("rt_render_rays_direct", direct->max_depth, direct->strategy, s->n_lights)) != RT_OK) return rc;
+  const rt_camera cam{};
+  const rt_film_desc film = virtual_film(width, height);
+  const rt_path_desc p = whitted_path_desc(film);
+  const rt_whitted_desc w{direct->max_depth, 0};
+  const RaySource src{rays, (unsigned)sample0, (unsigned)n_samples, nullptr, (flags & RT_FLAG_FILM_ON_DEVICE) != 0, ray_rec_floats(flags)};
+  FrameJob job = frame_job(FRAME_RAYS_DIRECT, s, &cam, &film, smp, &p, flags, stream_);
+  job.ray_src = &src; job.samples_rad = radiance; job.whitted = &w; job.direct = direct; job.whitted_info = info; job.stats_out = stats_out;
+  return render_frame(job);
+}
+// The perspective camera's frame of the direct-lighting integrator: rt_render's film with L = DirectLightingIntegrator::li.
+extern "C" int rt_render_direct(rt_scene* s, const rt_camera* cam, const rt_film_desc* film, const rt_sampler_desc* smp, const rt_direct_desc* direct, const rt_shard* shard,
+                                uint32_t flags, void* stream_, float* film_xyzw, rt_stats* stats_out) {
+  if (!s || !cam || !film || !smp || !direct || !film_xyzw) return fail(RT_ERR_INVALID, "rt_render_direct: null argument");
+  if (flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rt_render_direct: the reference-stream frame renders the path integrator only");
+  int rc = sampler_check("rt_render_direct", smp);
+  if (rc != RT_OK) return rc;
+  if ((rc = direct_desc_check("rt_render_direct", direct)) != RT_OK) return rc;
+  if ((rc = direct_numbers_check("rt_render_direct", direct->max_depth, direct->strategy, s->n_lights)) != RT_OK) return rc;
+  const rt_path_desc p = whitted_path_desc(*film);
+  const rt_whitted_desc w{direct->max_depth, 0};
+  FrameJob job = frame_job(FRAME_DIRECT, s, cam, film, smp, &p, flags, stream_);
+  job.shard = shard; job.film_xyzw = film_xyzw; job.whitted = &w; job.direct = direct; job.stats_out = stats_out;
   return render_frame(job);
 }
 // The perspective camera's rays (and film positions) of samples [sample0, sample0 + n_samples) of every pixel of the film's sample bounds, as a camera frame generates

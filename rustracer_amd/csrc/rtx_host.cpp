@@ -1424,6 +1424,50 @@ int rtxh_render_whitted(rtxh_scene* s, const rtxh_render_params* p, int32_t max_
   rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
   return rt_render_whitted(s->dev, &cf.cam, &cf.film, &smp, &w, &shard, p->flags, stream, film_xyzw, stats);
 }
+// what rt_render_rays_direct / rt_render_direct refuse of the integrator's parameters, before the scene is uploaded (the listed lights are the host scene's)
+static int direct_params_check(const char* who, const rtxh_scene* s, int32_t max_depth, int32_t strategy) {
+  const std::string n(who);
+  if (max_depth < 1) return fail(RT_ERR_INVALID, n + ": max_depth must be >= 1 (the camera ray is depth 0)");
+  if (strategy != RT_DIRECT_ALL && strategy != RT_DIRECT_ONE) return fail(RT_ERR_INVALID, n + ": strategy must be RT_DIRECT_ALL (0) or RT_DIRECT_ONE (1)");
+  if (max_depth > RT_WHITTED_MAX_DEPTH) return fail(RT_ERR_UNSUPPORTED, n + ": max_depth > RT_WHITTED_MAX_DEPTH (16)");
+  const long long arrays = 2ll * max_depth * (long long)s->lights.size();
+  if (strategy == RT_DIRECT_ALL && arrays > (long long)RT_DIRECT_MAX_ARRAYS)
+    return fail(RT_ERR_UNSUPPORTED, n + ": strategy \"all\" needs 2 * max_depth * n_lights = " + std::to_string(arrays) +
+                " sample arrays per pixel, more than RT_DIRECT_MAX_ARRAYS (1024): use strategy \"one\" (RT_DIRECT_ONE)");
+  return RT_OK;
+}
+// DirectLightingIntegrator::li along the caller's rays (rt_render_rays_direct)
+int rtxh_render_rays_direct(rtxh_scene* s, const rtxh_render_params* p, const float* rays, int32_t width, int32_t height, int32_t sample0, int32_t n_samples, int32_t max_depth,
+                            int32_t strategy, void* stream, float* radiance, uint32_t* info, rt_stats* stats) {
+  if (!s || !p || !rays || !radiance) return fail(RT_ERR_INVALID, "rtxh_render_rays_direct: null argument");
+  g_err.clear();
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_direct_desc d{max_depth, strategy, {0, 0}};
+  {  // what rt_render_rays_direct refuses, before the scene is uploaded for it
+    long long spp = 1; while (spp < (long long)std::max(p->spp, 1)) spp <<= 1;
+    if (width <= 0 || height <= 0 || n_samples <= 0) return fail(RT_ERR_INVALID, "rtxh_render_rays_direct: width, height and n_samples must be positive");
+    if (sample0 < 0 || (long long)sample0 + (long long)n_samples > spp) return fail(RT_ERR_INVALID, "rtxh_render_rays_direct: [sample0, sample0 + n_samples) must lie inside [0, spp)");
+    if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)RT_RAYS_MAX / (unsigned long long)n_samples)
+      return fail(RT_ERR_INVALID, "rtxh_render_rays_direct: the call holds more than RT_RAYS_MAX (2^27) rays - cut it by sample range");
+    int rc = direct_params_check("rtxh_render_rays_direct", s, max_depth, strategy); if (rc != RT_OK) return rc;
+    if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_rays_direct: the reference-stream frame has no per-sample output");
+  }
+  if (!s->dev) { int rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  return rt_render_rays_direct(s->dev, rays, width, height, sample0, n_samples, &smp, &d, p->flags, stream, radiance, info, stats);
+}
+// The frame of rtxh_render with the direct-lighting integrator (rt_render_direct): camera and film exactly as rtxh_render sets them up.
+int rtxh_render_direct(rtxh_scene* s, const rtxh_render_params* p, int32_t max_depth, int32_t strategy, void* stream, float* film_xyzw, rt_stats* stats) {
+  if (!s || !p || !film_xyzw) return fail(RT_ERR_INVALID, "rtxh_render_direct: null argument");
+  g_err.clear();
+  CamFilm cf; int rc = setup_camera_film(p, cf); if (rc != RT_OK) return rc;
+  if ((rc = direct_params_check("rtxh_render_direct", s, max_depth, strategy)) != RT_OK) return rc;
+  if (p->flags & RT_FLAG_REF_STREAM) return fail(RT_ERR_INVALID, "rtxh_render_direct: the reference-stream frame renders the path integrator only");
+  if (!s->dev) { rc = rtxh_scene_upload(s, -1); if (rc != RT_OK) return rc; }
+  rt_sampler_desc smp{p->spp, p->sampler_dims};
+  rt_direct_desc d{max_depth, strategy, {0, 0}};
+  rt_shard shard{p->rank, p->world_size > 0 ? p->world_size : 1};
+  return rt_render_direct(s->dev, &cf.cam, &cf.film, &smp, &d, &shard, p->flags, stream, film_xyzw, stats);
+}
 // A progressive frame of the scene (rt_frame_* in rtx_hip.h): camera, film and pixel bounds exactly as rtxh_render sets them up.
 struct rtxh_frame { rt_frame* f = nullptr; };
 int rtxh_frame_begin(rtxh_scene* s, const rtxh_render_params* p, uint64_t table_budget_bytes, rtxh_frame** out) {

@@ -50,6 +50,11 @@ RT_AO_FLOATS = 4            # rt_render_rays_ao: floats per ray of its output (a
 RT_AO_SAMPLES_MAX = 1024    # ... and the most occlusion rays per hit
 RT_WHITTED_MAX_DEPTH = 16   # rt_render_whitted / rt_render_rays_whitted: the deepest recursion (Whitted::new(n))
 RT_WHITTED_INFO_WORDS = 2   # rt_render_rays_whitted: uint32 per ray of its info output (li invocations, get_2d() draws)
+RT_DIRECT_ALL, RT_DIRECT_ONE = 0, 1  # rt_direct_desc.strategy: uniform_sample_all_light / uniform_sample_one_light
+RT_DIRECT_STRATEGIES = {"all": RT_DIRECT_ALL, "one": RT_DIRECT_ONE}
+RT_DIRECT_MAX_ARRAYS = 1024 # ... 2 * max_depth * n_lights under "all": above it the call is refused
+RT_DIRECT_INFO_WORDS = 4    # rt_render_rays_direct: uint32 per ray of its info output (li invocations, get_2d() draws, get_1d() draws, array vertices)
+RT_QUERY_DIRECT_LAUNCHED = 9   # rt_scene_query: the same of k_direct_vertex and the last direct-lighting call
 RT_QUERY_WHITTED_LAUNCHED = 8  # rt_scene_query: 1 + GENERAL of the k_whitted_vertex instantiation the scene's last Whitted call launched (0: none yet)
 RT_QUERY_LDS_SPEC = 7  # rt_scene_query: the form of the closest-hit link walk of an LDS-resident scene of plain triangles (RTX_LDS_SPEC: 0, 1)
 RT_QUERY_NEEDS_DIFFERENTIALS = 6  # rt_scene_query: 1 if some texture or bump map of the scene reads ray differentials
@@ -118,6 +123,11 @@ class AoDesc(C.Structure):
 class WhittedDesc(C.Structure):
     """rt_whitted_desc (rtx_hip.h): the Whitted integrator's parameters."""
     _fields_ = [("max_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DirectDesc(C.Structure):
+    """rt_direct_desc (rtx_hip.h): the direct-lighting integrator's parameters."""
+    _fields_ = [("max_depth", C.c_int32), ("strategy", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Stats(C.Structure):
@@ -945,6 +955,80 @@ class HostScene:
         p.flags = flags
         film = np.zeros((h, w, 4), np.float32)
         _check(L.rtxh_render_whitted(self.h, C.byref(p), int(max_depth), C.c_void_p(stream), _p(film), C.byref(stats)), "render_whitted")
+        return film, stats.as_dict()
+
+    def _direct_strategy(self, who, strategy):
+        if strategy in RT_DIRECT_STRATEGIES:
+            return RT_DIRECT_STRATEGIES[strategy]
+        if isinstance(strategy, int) and not isinstance(strategy, bool):
+            return strategy  # (the library answers for a number outside {0, 1})
+        raise BackendError(f"{who}: strategy must be 'all' or 'one', not {strategy!r}")
+
+    def render_rays_direct(self, rays, max_depth=5, strategy="all", sample0=0, spp=None, with_info=False, device_out=None, stream=0, count_traversal=False,
+                           time_kernels=False, device_info_out=None):
+        """The direct-lighting integrator along caller-supplied rays (rt_render_rays_direct: DirectLightingIntegrator::li). `rays`, `max_depth`, `sample0`, `spp` and the
+        device-pointer form as in `render_rays_whitted`; `strategy` "all" (every light at every vertex, from the sampler's arrays) or "one" (one light picked uniformly).
+        Returns (L (H, W, ns, 4), info or None, stats): `with_info`: info (H, W, ns, 4) uint32 - li invocations, get_2d() draws and get_1d() draws after the camera
+        sample, and the vertices that reached uniform_sample_all_light (above max_depth the sample exhausted its arrays; 0 under "one")."""
+        p = self._render_params()
+        if spp is not None:
+            p.spp = int(spp)
+        p.flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        st = self._direct_strategy("render_rays_direct", strategy)
+        on_device = hasattr(rays, "data_ptr")
+        if not on_device:
+            rays = np.ascontiguousarray(rays, np.float32)
+        if len(rays.shape) != 4 or rays.shape[3] not in (8, RT_RAY_DIFF_FLOATS):
+            raise BackendError(f"render_rays_direct: rays must have shape (H, W, ns, 8 | {RT_RAY_DIFF_FLOATS}), not {tuple(rays.shape)}")
+        if rays.shape[3] == RT_RAY_DIFF_FLOATS:
+            p.flags |= RT_FLAG_RAY_DIFFERENTIALS
+        h, w, ns = (int(v) for v in rays.shape[:3])
+        if h * w * ns > RT_RAYS_MAX:
+            raise BackendError(f"render_rays_direct: {h} x {w} x {ns} rays are more than RT_RAYS_MAX - cut the job by sample range")
+        L = lib()
+        L.rtxh_render_rays_direct.restype = C.c_int
+        L.rtxh_render_rays_direct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if on_device:
+            ok = device_out is not None and tuple(device_out.shape) == (h, w, ns, 4) and rays.is_contiguous() and device_out.is_contiguous() and rays.element_size() == 4 and device_out.element_size() == 4
+            if with_info:
+                ok = ok and device_info_out is not None and tuple(device_info_out.shape) == (h, w, ns, RT_DIRECT_INFO_WORDS) and device_info_out.is_contiguous() and device_info_out.element_size() == 4
+            if not ok:
+                raise BackendError("render_rays_direct: device rays need a contiguous float32 device_out of shape (H, W, ns, 4), and with_info a 4-byte integer device_info_out of shape (H, W, ns, 4)")
+            p.flags |= RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_rays_direct(self.h, C.byref(p), C.c_void_p(rays.data_ptr()), w, h, int(sample0), ns, int(max_depth), st, C.c_void_p(stream),
+                                             C.c_void_p(device_out.data_ptr()), C.c_void_p(device_info_out.data_ptr()) if with_info else None, C.byref(stats)), "render_rays_direct")
+            return device_out, (device_info_out if with_info else None), stats.as_dict()
+        if device_out is not None or device_info_out is not None:
+            raise BackendError("render_rays_direct: device outputs need device rays (RT_FLAG_FILM_ON_DEVICE names every pointer)")
+        rad = np.zeros((h, w, ns, 4), np.float32)
+        info = np.zeros((h, w, ns, RT_DIRECT_INFO_WORDS), np.uint32) if with_info else None
+        _check(L.rtxh_render_rays_direct(self.h, C.byref(p), rays.ctypes.data_as(C.c_void_p), w, h, int(sample0), ns, int(max_depth), st, C.c_void_p(stream),
+                                         rad.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p) if with_info else None, C.byref(stats)), "render_rays_direct")
+        return rad, info, stats.as_dict()
+
+    def render_direct(self, max_depth=5, strategy="all", rank=0, world_size=1, count_traversal=False, time_kernels=False, device_out=None, stream=0):
+        """The frame of `render` with the direct-lighting integrator (rt_render_direct): the same camera rays, film positions, pixel filter and shard bands, every sample's
+        L = DirectLightingIntegrator::li(ray, 0) with recursion limit `max_depth` and light strategy "all" or "one". Returns (film_xyzw (H, W, 4) over the cropped
+        bounds, stats dict). `device_out`: optional torch CUDA tensor (H, W, 4) float32 that receives the film in HBM."""
+        flags = (RT_FLAG_COUNT_TRAVERSAL if count_traversal else 0) | (RT_FLAG_TIME_KERNELS if time_kernels else 0)
+        strat = self._direct_strategy("render_direct", strategy)
+        st = self.setup(rank=rank, world_size=world_size)
+        cr = st["cropped"]
+        w, h = int(cr[2] - cr[0]), int(cr[3] - cr[1])
+        p = st["params"]
+        L = lib()
+        L.rtxh_render_direct.restype = C.c_int
+        L.rtxh_render_direct.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        stats = Stats()
+        if device_out is not None:
+            assert tuple(device_out.shape) == (h, w, 4) and device_out.is_contiguous()
+            p.flags = flags | RT_FLAG_FILM_ON_DEVICE
+            _check(L.rtxh_render_direct(self.h, C.byref(p), int(max_depth), strat, C.c_void_p(stream), C.c_void_p(device_out.data_ptr()), C.byref(stats)), "render_direct")
+            return device_out, stats.as_dict()
+        p.flags = flags
+        film = np.zeros((h, w, 4), np.float32)
+        _check(L.rtxh_render_direct(self.h, C.byref(p), int(max_depth), strat, C.c_void_p(stream), _p(film), C.byref(stats)), "render_direct")
         return film, stats.as_dict()
 
     def texture_words(self, tex):

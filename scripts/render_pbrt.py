@@ -3,7 +3,7 @@
     python scripts/render_pbrt.py scene.pbrt [out.png|out.pfm] [--spp N] [--samples out.npy] [--preview-every N]
                                   [--adaptive T [--min-samples M] [--noise-floor F] [--sample-map out.npy]] [--devices 0,1,...] [--features out.npy]
                                   [--camera-model orthographic|environment [--seed N] [--ray-frame] [--ray-differentials] [--device-camera]]
-                                  [--ao N [--ao-distance D]] [--whitted [MAXDEPTH]]
+                                  [--ao N [--ao-distance D]] [--whitted [MAXDEPTH]] [--direct [MAXDEPTH] [--direct-strategy all|one]]
 
 What `rustracer scene.pbrt` does, with the C++ host's parser (rtxh_pbrt_load) in front of the HIP path. Without an output
 name the image goes where the reference writes it: "rt-" + the Film's filename, or image.png (rc/film.rs:118-123), as an
@@ -41,7 +41,11 @@ file's Integrator: every camera sample's value is the clear fraction of N occlus
 "whitted"). One call, one device: --preview-every, --adaptive, --features, --samples, --devices and --camera-model do not combine with it.
 --whitted [MAXDEPTH]: the same with the reference's Whitted integrator (rt_render_whitted; integrator/whitted.rs): every light sampled at every vertex, mirrors and glass
 followed recursively up to MAXDEPTH (default 5, the reference's "maxdepth" default; the camera ray is depth 0). Also a choice of this command line - the loader keeps
-refusing Integrator "whitted" - and also one call on one device: it combines with none of the options --ao excludes, nor with --ao."""
+refusing Integrator "whitted" - and also one call on one device: it combines with none of the options --ao excludes, nor with --ao.
+--direct [MAXDEPTH] [--direct-strategy all|one]: the same with the reference's direct-lighting integrator (rt_render_direct; integrator/directlighting.rs): every light
+("all", the default: from the sampler's stratified arrays) or one uniformly picked light ("one") sampled at every vertex with multiple importance sampling - soft shadows
+from area and environment lights, no global illumination -, mirrors and glass followed up to MAXDEPTH (default 5). The loader keeps refusing Integrator
+"directlighting"; one call on one device, with the exclusions of --whitted, and not with --whitted or --ao."""
 import argparse
 import os
 import sys
@@ -189,7 +193,17 @@ def main():
     ap.add_argument("--ao", type=int, default=0, metavar="N", help="render with the ambient-occlusion integrator: N occlusion rays per camera sample")
     ap.add_argument("--ao-distance", type=float, default=float("inf"), metavar="D", help="with --ao: the length of the occlusion rays (default: infinite)")
     ap.add_argument("--whitted", type=int, nargs="?", const=5, default=None, metavar="MAXDEPTH", help="render with the Whitted integrator, recursion limit MAXDEPTH (default 5)")
+    ap.add_argument("--direct", type=int, nargs="?", const=5, default=None, metavar="MAXDEPTH", help="render with the direct-lighting integrator, recursion limit MAXDEPTH (default 5)")
+    ap.add_argument("--direct-strategy", choices=("all", "one"), default=None, help="with --direct: sample every light at every vertex (all, the default) or one picked light (one)")
     a = ap.parse_args()
+    if a.direct is not None and a.direct < 1:
+        raise SystemExit("--direct MAXDEPTH must be >= 1 (the camera ray is depth 0)")
+    if a.direct_strategy and a.direct is None:
+        raise SystemExit("--direct-strategy needs --direct")
+    if a.direct and (a.ao or a.whitted):
+        raise SystemExit("--direct, --whitted and --ao each replace the file's Integrator: give one of them")
+    if a.direct and (a.samples or a.preview_every > 0 or a.adaptive is not None or a.features or a.devices or a.camera_model):
+        raise SystemExit("--direct renders the file's camera in one call: it does not combine with --samples, --preview-every, --adaptive, --features, --devices or --camera-model")
     if a.whitted is not None and a.whitted < 1:
         raise SystemExit("--whitted MAXDEPTH must be >= 1 (the camera ray is depth 0)")
     if a.whitted and a.ao:
@@ -322,6 +336,11 @@ def main():
                 write(film)
                 print(f"{out}: {frame.samples_done} / {spp} samples per pixel", flush=True)
             save_features(frame)
+    elif a.direct:
+        film, stats = s.render_direct(a.direct, a.direct_strategy or "all")
+        write(film)
+        print(f"{out}: direct lighting, strategy {a.direct_strategy or 'all'}, max depth {a.direct}, {stats['rays_closest']} li rays, {stats['rays_shadow']} visibility segments and "
+              f"{stats['rays_mis']} BSDF-sampled rays from {stats['camera_rays']} camera samples")
     elif a.whitted:
         film, stats = s.render_whitted(a.whitted)
         write(film)
